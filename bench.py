@@ -26,11 +26,20 @@ a real exchange step, and total work is fixed: strong scaling).
 callback over gloo, every rank on the one GPU there is (a test transport: it
 checks the multi-rank path end to end on a 1-GPU box, it measures no scaling).
 
-The JSON line also carries the dominant kernel's roofline (the MFMA fp64
-trailing update of the reduced-system Cholesky, timed with HIP events around
-each of its launches inside the timed region) and a CPU baseline: the CPU
-oracle (oracle/, a C port of the same algorithm, NOT Ceres) timed on a
-bounded sample of the same workload on this host.
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) sets up, warms
+up, times the K solves and prints the JSON line: the headline figures, what
+the timed solves' own summaries hold (termination, reduced system, cold setup)
+and the dominant kernel's roofline (the MFMA fp64 trailing update of the
+reduced-system Cholesky, timed with HIP events around each of its launches
+inside the timed region: no run of its own).  `--dump-outputs DIR` also writes
+what the last timed solve returned to its caller as DIR/<name>.npy (float64).
+
+`--full` adds everything that takes runs of its own, after the timed region
+and outside it: one more solve with the per-phase events on
+(phase_ms_per_solve), the box fingerprint, the incremental cfg2 flow, the cfg5
+localize batch, and a CPU baseline: the CPU oracle (oracle/, a C port of the
+same algorithm, NOT Ceres) timed on the same workload on this host.  The
+--no-* options trim a --full run; without --full none of these runs.
 """
 from __future__ import annotations
 
@@ -179,6 +188,12 @@ def bench_localize(args, world, rank, side=False):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0 and not side:
+        # the timed solves download nothing; every solve restarts from the resident initial
+        # state, so one more solve with the download on repeats the last timed step
+        pose, dres, _ = loc.solve()
+        dump_outputs(args.dump_outputs, pose=pose, status=dres["status"], num_iterations=dres["num_iterations"],
+                     final_cost=dres["final_cost"])
     q_iters = int(res["num_iterations"].sum())
     k_obs = b.n_obs / b.n_query
     bytes_per_qi = 2 * k_obs * (72 + 48) + 48
@@ -210,7 +225,7 @@ def bench_localize(args, world, rank, side=False):
                                      "frac": achieved / HBM_PEAK_GBS,
                                      "bytes_per_query_iteration": bytes_per_qi}},
            "cpu_baseline": None}
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         # (as the side key of the default line: a 4 s sample, so the line stays within minutes)
         from oracle import oracle as O
         O.build()
@@ -227,6 +242,14 @@ def bench_localize(args, world, rank, side=False):
         return out
     if rank == 0:
         print(json.dumps(out), flush=True)
+
+
+def dump_outputs(dirname, **arrays):
+    """--dump-outputs: each array as DIR/<name>.npy in float64 (whole arrays: a cfg3 solve returns
+    under 1 MB), so two builds run with the same arguments can be compared output for output."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def load_pmc_localize():
@@ -362,6 +385,14 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="cfg3")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline does not need: the per-phase solve, the "
+                         "box fingerprint, the incremental cfg2 flow, the cfg5 batch and the CPU baselines "
+                         "(each can be dropped again with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float64): "
+                         "camera, cap, tag and the LM cost trace (cfg5: pose, status, num_iterations, final_cost); "
+                         "with N ranks rank 0 writes, and a capture another rank owns keeps its initial pose")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-incremental", action="store_true", help="skip the solveIncremental (cfg2) side line")
     ap.add_argument("--no-localize", action="store_true", help="skip the cfg5 batched-localize side key")
@@ -474,9 +505,15 @@ def main():
 
     iters = sum(s["num_linear_solves"] for s in sums)
     last = sums[-1]
-    # one more solve, untimed, with the per-phase events on: the phase breakdown
-    rp.set_options(phase_timing=1, **opts)
-    phased = rp.solve()
+    if args.dump_outputs and rank == 0:
+        # the last timed solve's write-back (nothing has solved since) and its cost trace
+        dump_outputs(args.dump_outputs, camera=rp.camera, cap=rp.cap, tag=rp.tag,
+                     cost_trace=[it["cost"] for it in last["iterations"]])
+    phased = None
+    if args.full:
+        # one more solve, untimed, with the per-phase events on: the phase breakdown
+        rp.set_options(phase_timing=1, **opts)
+        phased = rp.solve()
     dom_ms = sum(s["t_dominant_ms"] for s in sums)
     dom_launches = sum(s["n_dominant_launches"] for s in sums)
     dom_flops = sum(s["dominant_flops"] for s in sums)
@@ -560,22 +597,22 @@ def main():
                          ("RCCL, one GPU per rank" if world > 1 else
                           "RCCL, one-rank communicator, multi-rank path forced (debug)" if args.rccl_one_rank else None),
             "phase_ms_per_solve": {k: phased[f"t_{k}_ms"] for k in
-                                   ("linearize", "schur", "cholesky", "solve", "backsub", "cost")},
+                                   ("linearize", "schur", "cholesky", "solve", "backsub", "cost")} if phased else None,
             "roofline": roofline,
             "cpu_baseline": None,
             "library": lm.library_info(),
         }
-        if not args.no_fingerprint:   # which kind of MI355X box this line ran on (a few ms, untimed)
+        if args.full and not args.no_fingerprint:   # which kind of MI355X box this line ran on (a few ms, untimed)
             out["box_fingerprint"] = lm.box_fingerprint(device)
-        if world == 1 and not args.no_incremental and args.config == "cfg3":
+        if args.full and world == 1 and not args.no_incremental and args.config == "cfg3":
             print("bench: incremental cfg2 flow", file=sys.stderr, flush=True)
             out["incremental_cfg2"] = bench_incremental("cfg2")
             # the same flow eliminating every capture (rounds 3-5's default)
             out["incremental_cfg2_captures"] = bench_incremental("cfg2", elimination=1)
-        if world == 1 and args.config == "cfg3" and not args.no_localize:
+        if args.full and world == 1 and args.config == "cfg3" and not args.no_localize:
             print("bench: cfg5 localize batch", file=sys.stderr, flush=True)
             out["localize_cfg5"] = bench_localize(args, world, rank, side=True)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # every CPU this process is granted: the box gives one GPU's share of the node
             # (OMP_NUM_THREADS, 16 on the GPU box) while nproc / lscpu report the whole node
             # (recorded beside it); more threads than the share only oversubscribe it
