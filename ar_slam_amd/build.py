@@ -83,7 +83,8 @@ def _build_locked(verbose):
     extra = os.environ.get("ARSLAM_EXTRA_FLAGS", "")
     objdir = os.path.join(HERE, "_obj" + ("_" + "".join(c for c in extra if c.isalnum()) if extra else ""))
     os.makedirs(objdir, exist_ok=True)
-    flags = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-munsafe-fp-atomics",
+    # (-fconstexpr-steps: schur_store_table.h builds its 33,280 descriptors at compile time)
+    flags = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-munsafe-fp-atomics", "-fconstexpr-steps=100000000",
              "-Wall", "-Wno-unused-function", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
              f'-DARSLAM_BUILD_ID="{build_id()}"'] + os.environ.get("ARSLAM_EXTRA_FLAGS", "").split()
     objs = []

@@ -2,6 +2,7 @@
 // one device stage in isolation so the parity tests can pin it to the oracle.
 #include <chrono>
 #include "lm_internal.h"
+#include "schur_store_table.h"
 #include "arslam_lm.h"
 #include "arslam_lm_debug.h"
 
@@ -448,6 +449,21 @@ extern "C" int arslam_debug_mixed_groups(const arslam_soa_problem *p, int out[4]
 extern "C" int arslam_debug_schur_stamps(unsigned long long out[16]) {
   if (!out) return ARSLAM_E_INVALID_ARG;
   arslam::debug_read_schur_stamps(out);
+  return ARSLAM_OK;
+}
+
+// host only: k_schur<false>'s output-stage descriptors (the host copy of the table the kernel reads)
+extern "C" int arslam_debug_schur_store_table(int nblk, int *off, unsigned char *stored) {
+  static constexpr arslam::SchurStoreTable kTable = arslam::make_schur_store_table();
+  if (!off || !stored || nblk < 1 || nblk > arslam::kSchurMfmaBlocks) {
+    arslam::set_last_error("arslam_debug_schur_store_table: nblk outside 1..kSchurMfmaBlocks or a null array");
+    return ARSLAM_E_INVALID_ARG;
+  }
+  const uint32_t *e = &kTable.e[nblk - 1][0][0][0];
+  for (int s = 0; s < arslam::kSchurStoreTiles * arslam::kWave * 4; ++s) {
+    off[s] = (int)((e[s] & arslam::kSchurStoreMask) >> 3);
+    stored[s] = (e[s] >> 31) ? 0 : 1;
+  }
   return ARSLAM_OK;
 }
 

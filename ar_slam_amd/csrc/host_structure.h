@@ -189,16 +189,16 @@ struct SchurContrib {
   int tr, ld;   // tr: the block is stored transposed (local U < V); ld: its row length
 };
 // local block of local column x (m = 1 + 6 nblk: the rhs row)
-ARSLAM_HD inline int schur_blk(int x, int m) { return x == 0 ? 0 : (x == m ? 1 + (m - 1) / 6 : 1 + (x - 1) / 6); }
-ARSLAM_HD inline int schur_blk_size(int U, int nblk) { return (U == 0 || U == nblk + 1) ? 1 : 6; }
-ARSLAM_HD inline int schur_blk_start(int U, int nblk) { return U == 0 ? 0 : (U <= nblk ? 1 + 6 * (U - 1) : 1 + 6 * nblk); }
+ARSLAM_HD constexpr int schur_blk(int x, int m) { return x == 0 ? 0 : (x == m ? 1 + (m - 1) / 6 : 1 + (x - 1) / 6); }
+ARSLAM_HD constexpr int schur_blk_size(int U, int nblk) { return (U == 0 || U == nblk + 1) ? 1 : 6; }
+ARSLAM_HD constexpr int schur_blk_start(int U, int nblk) { return U == 0 ? 0 : (U <= nblk ? 1 + 6 * (U - 1) : 1 + 6 * nblk); }
 // first element of block (U, V), U >= V: row blocks before U, then the blocks
 // (U, V') with V' < V (their columns = the local start of V)
-ARSLAM_HD inline long schur_block_off(int U, int V, int nblk) {
+ARSLAM_HD constexpr long schur_block_off(int U, int V, int nblk) {
   const long R = U == 0 ? 0 : 1 + 6L * (U - 1) + 18L * U * (U - 1);
   return R + (long)schur_blk_size(U, nblk) * schur_blk_start(V, nblk);
 }
-ARSLAM_HD inline long schur_slab_size(int nblk) { return 3 + 12L * nblk + 18L * nblk * (nblk + 1); }
+ARSLAM_HD constexpr long schur_slab_size(int nblk) { return 3 + 12L * nblk + 18L * nblk * (nblk + 1); }
 // A destination with more than kSchurChunk contributions per lane group of its
 // k_schur_gather wave (gather_partition) is summed in pieces
 // (work items writing partial sums, then one combine per split destination

@@ -81,6 +81,26 @@ constexpr size_t schur_lds_bytes(int nblk) {
          sizeof(int) * (kObsChunk + 2) + 2 * sizeof(double) + 64;
 }
 static_assert(schur_lds_bytes(kMaxSchurBlocks) <= 160 * 1024, "k_schur's LDS at kMaxSchurBlocks");
+// That layout's arrays as indices of doubles from the start of the wave's LDS
+// (stage is at 0), for a capture of nblk distinct tags: k_schur's pointers and
+// the LDS indices in its output stage's descriptor table (schur_store_table.h)
+struct SchurLds {
+  int tscale, U, Ui, Etr, W, Ftr, FF, lblk, ff00;
+};
+__host__ __device__ constexpr SchurLds schur_lds(int nblk) {
+  const int m = 1 + 6 * nblk;
+  SchurLds l{};
+  l.tscale = 6 * (m + 1 < kWave ? m + 1 : kWave);
+  l.U = l.tscale + 6 * kObsChunk;
+  l.Ui = l.U + 36;
+  l.Etr = l.Ui + 36;
+  l.W = l.Etr + 8;
+  l.Ftr = l.W + 6 * m;
+  l.FF = l.Ftr + m + (m & 1);
+  l.lblk = l.FF + 28 * nblk;            // kObsChunk ints
+  l.ff00 = l.lblk + kObsChunk / 2;
+  return l;
+}
 
 // number of per-capture partial sums written by the per-capture kernels
 enum PartIdx {

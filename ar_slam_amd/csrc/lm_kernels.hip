@@ -19,6 +19,7 @@
 // bit-identical run to run.
 #include "lm_internal.h"
 #include "projection.h"
+#include "schur_store_table.h"
 
 #include <cfloat>
 #include <mutex>
@@ -52,6 +53,8 @@ void debug_read_schur_stamps(unsigned long long *out) {
 
 namespace {
 
+// k_schur<false>'s output-stage descriptors: a constant of the code object
+__device__ const SchurStoreTable g_schur_store = make_schur_store_table();
 
 __device__ __forceinline__ long slot_cap(const DevProblem &P, int c) { return 3 + 6L * c; }
 __device__ __forceinline__ long slot_tag(const DevProblem &P, int t) { return 3 + 6L * P.nc + 6L * t; }
@@ -509,16 +512,17 @@ __global__ __launch_bounds__(kWave) void k_schur(DevProblem P, const double *__r
   // straight into the MFMA operand registers), so ~8 KB per wave at 8 tags:
   // 4-5 waves per SIMD instead of the 2.75 the 13.5 KB row-staging layout
   // allowed (latency-bound kernel)
-  double *stage = sm;                            // 6 min(m + 1, 64): the MFMA product's Z operand
-  double *tscale = stage + 6 * min(m + 1, kWave);   // 6 kObsChunk: the chunk's observations' tag column scales
-  double *U = tscale + 6 * kObsChunk;            // 36
-  double *Ui = U + 36;                           // 36
-  double *Etr = Ui + 36;                         // 8
-  double *W = Etr + 8;                           // 6*m
-  double *Ftr = W + 6 * m;                       // m (+pad)
-  double *FF = Ftr + m + (m & 1);                // 28 per tag block: F_u'F_u (21, packed), F_0'F_u (6), pad
-  int *lblk = (int *)(FF + 28 * nblk);           // kObsChunk: the chunk's observations' tag blocks
-  double *ff00 = reinterpret_cast<double *>(lblk + kObsChunk);     // F_0'F_0
+  const SchurLds lds = schur_lds(nblk);
+  double *stage = sm;                    // 6 min(m + 1, 64): the MFMA product's Z operand
+  double *tscale = sm + lds.tscale;      // 6 kObsChunk: the chunk's observations' tag column scales
+  double *U = sm + lds.U;                // 36
+  double *Ui = sm + lds.Ui;              // 36
+  double *Etr = sm + lds.Etr;            // 8
+  double *W = sm + lds.W;                // 6*m
+  double *Ftr = sm + lds.Ftr;            // m (+pad)
+  double *FF = sm + lds.FF;              // 28 per tag block: F_u'F_u (21, packed), F_0'F_u (6), pad
+  int *lblk = (int *)(sm + lds.lblk);    // kObsChunk: the chunk's observations' tag blocks
+  double *ff00 = sm + lds.ff00;          // F_0'F_0
 
   // the first eight observations' Jacobian rows (the Gram loop's operands
   // below) are loaded before the prologue's dependent loads (obs_tag -> the
@@ -735,6 +739,15 @@ __global__ __launch_bounds__(kWave) void k_schur(DevProblem P, const double *__r
     }
   };
   const bool one_chunk = !kBig;   // (m + 1 <= kWave)
+  // the output stage's descriptors (schur_store_table.h), one 16-byte entry per
+  // tile and lane: the first tile row's are fetched before z is formed
+  typedef unsigned int u4v __attribute__((ext_vector_type(4)));
+  const u4v *desc = reinterpret_cast<const u4v *>(&g_schur_store.e[one_chunk ? nblk - 1 : 0][0][lane][0]);
+  u4v dsc[4];
+  if (one_chunk) {
+    dsc[0] = desc[0];
+    dsc[1] = desc[kWave];
+  }
   double z[6];
   if (one_chunk) make_z(lane, z);
   if (one_chunk) {
@@ -764,21 +777,21 @@ __global__ __launch_bounds__(kWave) void k_schur(DevProblem P, const double *__r
         Bop[r][kb] = in ? Zs[a * M + pq] : 0.0;
       }
     typedef double dbl4v __attribute__((ext_vector_type(4)));
+    typedef unsigned int u2v __attribute__((ext_vector_type(2)));
+    // the capture's slab as a buffer: the stores below are range-checked
+    // against it (c, nblk and the slab base are wave-uniform)
+    const __amdgpu_buffer_rsrc_t slab_rsrc =
+        __builtin_amdgcn_make_buffer_rsrc(out, 0, (int)(schur_slab_size(nblk) * sizeof(double)), 0x00020000);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       if (16 * r >= M) break;
-      // this lane's rows p = 16 r + lk + 4 reg: block row, row inside it, last stored column
-      int pU[4], pI[4], pEnd[4];
-      long pOff[4];
+      // the next tile row's descriptors are fetched beside this row's products
+      // (the table holds all 13 tiles for every nblk: no bound to check)
+      u4v dn[4];
+      if (r < 3) {
 #pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int pp = 16 * r + lk + 4 * reg;
-        const int up = pp >= 1 && pp < m ? (pp - 1) / 6 : -1;
-        const int U = pp == 0 ? 0 : (pp < m ? 1 + up : nblk + 1);
-        pU[reg] = U;
-        pI[reg] = up >= 0 ? pp - 1 - 6 * up : 0;
-        pEnd[reg] = pp == 0 ? 1 : (pp < m ? 7 + 6 * up : M);   // columns q < pEnd are stored
-        pOff[reg] = schur_block_off(U, 0, nblk);               // the block row's first element
+        for (int cc = 0; cc < 4; ++cc)
+          if (cc <= r + 2) dn[cc] = desc[(schur_store_row_tile(r + 1) + cc) * kWave];
       }
 #pragma unroll
       for (int cc = 0; cc < 4; ++cc) {
@@ -786,31 +799,23 @@ __global__ __launch_bounds__(kWave) void k_schur(DevProblem P, const double *__r
         dbl4v acc = {0, 0, 0, 0};
         acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Aop[r][0], Bop[cc][0], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Aop[r][1], Bop[cc][1], acc, 0, 0, 0);
-        const int q = 16 * cc + li;
-        const int uq = q >= 1 && q < m ? (q - 1) / 6 : -1;   // q's tag block
-        const int V = q == 0 ? 0 : (q < m ? 1 + uq : nblk + 1);
-        const int sV = schur_blk_size(V, nblk), q0V = schur_blk_start(V, nblk);
+        // element (16 r + lk + 4 reg, 16 cc + li): its F'F / F'r / f'F / f'f
+        // term (a zero word where it has none) minus the product, to its slot
+        // (a "not stored" entry's offset is past the slab: the store is dropped)
+        double ff[4];
 #pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          const int pp = 16 * r + lk + 4 * reg;
-          if (pp >= M || q >= pEnd[reg]) continue;
-          const int U = pU[reg], sU = schur_blk_size(U, nblk);
-          double ff = 0.0;
-          if (pp == 0) {
-            ff = *ff00;                                     // (q == 0 only)
-          } else if (pp == m) {
-            ff = q < m ? Ftr[q] : 0.0;
-          } else {
-            const int up = U - 1, i = pI[reg];
-            if (q == 0) {
-              ff = FF[28 * up + 21 + i];                    // f'F_u
-            } else if (uq == up) {                          // F_u'F_u packed upper (a <= b)
-              const int iq = q - 1 - 6 * uq, lo = min(i, iq), hi = max(i, iq);
-              ff = FF[28 * up + lo * 6 - lo * (lo - 1) / 2 + (hi - lo)];
-            }
-          }
-          out[pOff[reg] + (long)sU * q0V + pI[reg] * sV + (q - q0V)] = ff - acc[reg];
-        }
+        for (int reg = 0; reg < 4; ++reg)
+          ff[reg] = *reinterpret_cast<const double *>(
+              reinterpret_cast<const char *>(sm) + ((dsc[cc][reg] >> kSchurStoreLdsShift) & kSchurStoreMask));
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg)
+          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2v, ff[reg] - acc[reg]), slab_rsrc,
+                                                (int)(dsc[cc][reg] & kSchurStoreMask), 0, 0);
+      }
+      if (r < 3) {
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc)
+          if (cc <= r + 2) dsc[cc] = dn[cc];
       }
     }
   } else

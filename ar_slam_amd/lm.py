@@ -51,7 +51,7 @@ EXPORTS = ["arslam_lm_options_init", "arslam_lm_create", "arslam_lm_destroy",
            "arslam_debug_mixed_groups",
            "arslam_debug_dag_simulate", "arslam_debug_dag_simulate_started", "arslam_debug_dag_workgroup_limit",
            "arslam_debug_dag_fault_detail", "arslam_debug_box_fingerprint",
-           "arslam_debug_rank_split", "arslam_debug_gather_extend",
+           "arslam_debug_rank_split", "arslam_debug_gather_extend", "arslam_debug_schur_store_table",
            "arslam_localize_many", "arslam_localizer_create", "arslam_localizer_destroy",
            "arslam_localizer_load", "arslam_localizer_solve",
            "arslam_slam_create", "arslam_slam_destroy", "arslam_slam_set_verbose", "arslam_slam_load_yaml",
@@ -233,6 +233,8 @@ def lib():
     L.arslam_lm_debug_break_dependency.argtypes = [C.c_void_p, C.c_long, C.POINTER(C.c_long)]
     if hasattr(L, "arslam_lm_debug_tag_pair_tile"):   # (absent from older variant builds under A/B)
         L.arslam_lm_debug_tag_pair_tile.argtypes = [C.c_void_p, _dp, _dp, C.POINTER(C.c_int)]
+    if hasattr(L, "arslam_debug_schur_store_table"):   # (likewise)
+        L.arslam_debug_schur_store_table.argtypes = [C.c_int, _ip, C.POINTER(C.c_ubyte)]
     _lib = L
     return L
 
@@ -599,6 +601,17 @@ def debug_gather_extend(camera, cap, tag, obs_cap, obs_tag, corners, c0):
     same, nd = C.c_int(0), C.c_int(0)
     _check(lib().arslam_debug_gather_extend(C.byref(A.s), c0, C.byref(same), C.byref(nd)))
     return bool(same.value), nd.value
+
+
+def debug_schur_store_table(nblk):
+    """Host-only: k_schur's output-stage descriptors for captures of nblk distinct tags (1..10), in
+    kernel order [tile (r, cc), cc <= r + 1][lane][register]: (offset, stored) -- the element's offset
+    in the capture's block-packed slab and whether the lane stores it."""
+    off = np.zeros((13, 64, 4), np.int32)
+    stored = np.zeros((13, 64, 4), np.uint8)
+    _check(lib().arslam_debug_schur_store_table(int(nblk), off.ctypes.data_as(_ip),
+                                                stored.ctypes.data_as(C.POINTER(C.c_ubyte))))
+    return off, stored
 
 
 class SplitInfo(C.Structure):

@@ -176,6 +176,14 @@ int arslam_debug_rank_split(const arslam_soa_problem *p, int nranks, int rank, a
  * same layout.  *identical = 1 when every array agrees; *n_dest the
  * destinations of the full plan. */
 int arslam_debug_gather_extend(const arslam_soa_problem *p, int c0, int *identical, int *n_dest);
+/* Host only: the descriptors of the Schur kernel's output stage for a capture
+ * of nblk distinct tags (1..10), as the kernel reads them: 13 tiles (r, cc),
+ * cc <= r + 1, of its 16x16 output product in that order, 64 lanes, 4
+ * registers -- lane (lk, li) holds element (16 r + lk + 4 reg, 16 cc + li) of
+ * the capture's local system.  off[13*64*4]: the element's offset in the
+ * capture's block-packed slab; stored[13*64*4]: 1 where the lane stores it
+ * (the lower block triangle), 0 elsewhere (off is then meaningless). */
+int arslam_debug_schur_store_table(int nblk, int *off, unsigned char *stored);
 
 #ifdef __cplusplus
 }
