@@ -2,6 +2,7 @@
 // one device stage in isolation so the parity tests can pin it to the oracle.
 #include <chrono>
 #include "lm_internal.h"
+#include "loss.h"
 #include "schur_store_table.h"
 #include "arslam_lm.h"
 #include "arslam_lm_debug.h"
@@ -18,6 +19,9 @@ namespace arslam {
 void debug_read_schur_stamps(unsigned long long *out);
 void debug_residual_jacobian(int n, const double *cam, const double *cap, const double *tag,
                              const double *corners, double *r, double *J, hipStream_t s);
+void debug_residual_jacobian_loss(int n, const double *cam, const double *cap, const double *tag,
+                                  const double *corners, const unsigned char *kind, const double *a, double *r,
+                                  double *J, double *rho, hipStream_t s);
 void debug_angle_axis(int n, const double *w, const double *p, double *out, int *branch, hipStream_t s);
 }
 
@@ -56,6 +60,43 @@ extern "C" int arslam_debug_residual_jacobian(int n, const double *cam, const do
   (void)hipFree(d_r);
   (void)hipFree(d_J);
   return ARSLAM_OK;
+}
+
+extern "C" int arslam_debug_residual_jacobian_loss(int n, const double *cam, const double *cap,
+                                                   const double *tag, const double *corners,
+                                                   const unsigned char *kind, const double *a, double *r,
+                                                   double *J, double *rho) {
+  if (n < 0 || (n && (!cam || !cap || !tag || !corners || !kind || !a || !r || !J || !rho))) return ARSLAM_E_INVALID_ARG;
+  for (int i = 0; i < n; ++i)
+    if (!arslam::loss_valid(kind[i], a[i])) return ARSLAM_E_INVALID_ARG;
+  if (n == 0) return ARSLAM_OK;
+  // inputs cam | cap | tag | corners | a, then outputs r | J | rho, in one buffer; the kinds in another
+  const size_t in_n = (size_t)n * 24, out_n = (size_t)n * (8 + 120 + 1);
+  double *d = nullptr;
+  unsigned char *d_k = nullptr;
+  std::vector<double> h(in_n);
+  std::memcpy(h.data(), cam, (size_t)n * 3 * sizeof(double));
+  std::memcpy(h.data() + 3L * n, cap, (size_t)n * 6 * sizeof(double));
+  std::memcpy(h.data() + 9L * n, tag, (size_t)n * 6 * sizeof(double));
+  std::memcpy(h.data() + 15L * n, corners, (size_t)n * 8 * sizeof(double));
+  std::memcpy(h.data() + 23L * n, a, (size_t)n * sizeof(double));
+  // (every step through one status, so both allocations are freed whichever step fails)
+  hipError_t e = hipMalloc(&d, (in_n + out_n) * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&d_k, (size_t)n);
+  if (e == hipSuccess) e = hipMemcpy(d, h.data(), in_n * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_k, kind, (size_t)n, hipMemcpyHostToDevice);
+  double *d_r = d + in_n, *d_J = d_r + 8L * n, *d_rho = d_J + 120L * n;
+  if (e == hipSuccess) {
+    arslam::debug_residual_jacobian_loss(n, d, d + 3L * n, d + 9L * n, d + 15L * n, d_k, d + 23L * n, d_r, d_J, d_rho, 0);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(r, d_r, (size_t)n * 8 * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(J, d_J, (size_t)n * 120 * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(rho, d_rho, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  (void)hipFree(d_k);
+  return hip_fail(e);
 }
 
 extern "C" int arslam_debug_angle_axis_rotate(int n, const double *w, const double *p, double *out,

@@ -730,7 +730,7 @@ void mixed_patch(HostProblem &h, const MixedProblem &m, const arslam_soa_problem
   }
 }
 
-HostProblem host_problem(const arslam_soa_problem *p, const ReduceSumF64 &tag_deg_sum) {
+HostProblem host_problem(const arslam_soa_problem *p, const ReduceSumF64 &tag_deg_sum, const ObsLoss *loss) {
   api_check(p != nullptr, ARSLAM_E_INVALID_ARG, "null problem");
   api_check(p->n_cap >= 0 && p->n_tag >= 0 && p->n_obs >= 0, ARSLAM_E_INVALID_ARG, "negative sizes");
   api_check(p->camera && (!p->n_cap || p->cap) && (!p->n_tag || p->tag), ARSLAM_E_INVALID_ARG,
@@ -777,6 +777,18 @@ HostProblem host_problem(const arslam_soa_problem *p, const ReduceSumF64 &tag_de
     h.maxblk = std::max(h.maxblk, (int)h.blk_tag.size() - h.cap_blk_start[c]);
   }
   h.cap_blk_start[nc] = (int)h.blk_tag.size();
+  // the losses in the same order (kept only when some observation has one)
+  bool any_loss = false;
+  if (loss && loss->kind && loss->a)
+    for (int b = 0; b < nb && !any_loss; ++b) any_loss = loss->kind[b] != ARSLAM_LOSS_NONE;
+  if (any_loss) {
+    h.loss_kind.resize(nb);
+    h.loss_a.resize(nb);
+    for (int q = 0; q < nb; ++q) {
+      h.loss_kind[q] = loss->kind[order[q]];
+      h.loss_a[q] = loss->a[order[q]];
+    }
+  }
   api_check(h.maxblk <= kMaxSchurBlocks, ARSLAM_E_UNSUPPORTED,
             "an eliminated block (capture, or tag under tag elimination) couples more than 256 distinct blocks");
   // tag CSR over the capture-major order

@@ -56,6 +56,10 @@ struct HostProblem {
   std::vector<int> tag_obs;         // [nb]
   std::vector<int> obs_tpos;        // [nb] position of observation q in the tag CSR (tag_obs[obs_tpos[q]] = q)
   std::vector<double> corners;      // [8 nb] capture-major
+  // the observations' robust losses (ObsLoss), capture-major like corners;
+  // both empty when no observation has one
+  std::vector<unsigned char> loss_kind;   // [nb] ARSLAM_LOSS_*
+  std::vector<double> loss_a;             // [nb]
   std::vector<unsigned char> slot_free, obs_active;
   std::vector<double> x0;           // [n] initial slots
   long nb_global = 0;
@@ -75,7 +79,16 @@ std::vector<int> rcm_order(int n, const std::vector<std::vector<int>> &adj);
 std::vector<std::vector<int>> nd_parts(int n, const std::vector<std::vector<int>> &adj, int leaf,
                                        const std::vector<double> &xyz = {}, bool fast = false);
 
-HostProblem host_problem(const arslam_soa_problem *p, const ReduceSumF64 &tag_deg_sum);
+// The robust loss of each observation of an arslam_soa_problem, in its
+// observation order (kind ARSLAM_LOSS_*, scale a); both null: none.  It stays
+// beside the problem through swap_roles and mixed_problem, which keep the
+// observation order.
+struct ObsLoss {
+  const unsigned char *kind = nullptr;
+  const double *a = nullptr;
+};
+HostProblem host_problem(const arslam_soa_problem *p, const ReduceSumF64 &tag_deg_sum,
+                         const ObsLoss *loss = nullptr);
 
 // Ceres 2.0's e-block set for DENSE_SCHUR with no user ordering
 // (ReorderProgramForSchurTypeLinearSolver -> ComputeStableSchurOrdering ->

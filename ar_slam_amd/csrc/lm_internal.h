@@ -180,8 +180,15 @@ struct DevProblem {
   // values are gathered from these
   const unsigned char *f_own = nullptr;
   double *jrows;             // [8 nb kJStored] unscaled Jacobian rows + residual at the linearization point
+                             // (an observation with a loss: its rows times sqrt(rho'), Ceres' corrector)
                              // (column-major per capture: (row, jrow_col(j)) at 8 o0 kJStored + jrow_col(j) 8k + row)
   double *cap_ui;            // [36 nc] (U_c + D_c^2)^{-1} of the current step (k_schur -> k_backsub)
+  // the observations' robust losses (loss.h), in the order of corners; both
+  // null when no observation of the loaded problem has one -- the host then
+  // launches the kLoss = false instances of k_linearize, k_cost and k_backsub
+  // (last in the struct: no other field's kernel-argument offset moves)
+  const unsigned char *obs_loss_kind = nullptr;   // [nb] ARSLAM_LOSS_*
+  const double *obs_loss_a = nullptr;             // [nb] scale a
 };
 
 // element (r, c), r >= c, of the compact-tiled reduced system

@@ -19,6 +19,7 @@
 // bit-identical run to run.
 #include "lm_internal.h"
 #include "projection.h"
+#include "loss.h"
 #include "schur_store_table.h"
 
 #include <cfloat>
@@ -73,6 +74,31 @@ __device__ __forceinline__ double lm_d2(const double *diag, long slot, double ra
   return d * d;
 }
 
+// The sum of v over an observation's 8 residual rows, which sit in 8
+// consecutive lanes (lane = 8 q + row): wave_reduce's first three steps, so
+// the 8 lanes end with the same bits.  The 8 lanes are active together.
+__device__ __forceinline__ double obs_sum8(double v) {
+  v += dpp_f64<0xB1>(v);    // lane ^ 1
+  v += dpp_f64<0x4E>(v);    // lane ^ 2
+  v += dpp_f64<0x141>(v);   // row_half_mirror: the other quad of the 8
+  return v;
+}
+
+// Ceres' corrector (corrector.cc, alpha = 0: every loss of loss.h has
+// rho'' <= 0) on one row of an observation whose 8 rows sit in 8 consecutive
+// lanes: r and its 13 Jacobian entries times sqrt(rho'(s)), s = |r|^2 over
+// the 8 rows.  Returns rho(s), the same in the 8 lanes.
+__device__ __forceinline__ double robustify_row(int kind, double a, double &r, double J[13]) {
+  const double s = obs_sum8(r * r);
+  double rho, rho1;
+  loss_eval(kind, a, s, &rho, &rho1);
+  const double w = sqrt(rho1);
+#pragma unroll
+  for (int j = 0; j < 13; ++j) J[j] *= w;
+  r *= w;
+  return rho;
+}
+
 // Fill LDS rows [nr][kRowStride] with rows [row0, row0 + nr) of capture c
 // (nrows rows in all, observations from o0): 13 Jacobian entries (scaled by
 // the Jacobi scale if scale != nullptr) and the residual in column 13.
@@ -80,8 +106,14 @@ __device__ __forceinline__ double lm_d2(const double *diag, long slot, double ra
 // (entry (row, j) at gout + 8 o0 kJStored + jrow_col(j) nrows + row, the
 // translation columns once): the Schur and back-substitution passes at the
 // same point reload them instead of re-evaluating the projection.
+// kLoss: the rows are the corrected ones, sqrt(rho') (J | r) per observation
+// (robustify_row), in LDS and in gout alike; with ocost, observation q of the
+// chunk also leaves its cost rho(s) / 2 in ocost[q] (from the corrected
+// residuals it would be rho' s / 2).
+template <bool kLoss = false>
 __device__ __forceinline__ void fill_rows(const DevProblem &P, const double *x, const double *scale, int c,
-                          int o0, int row0, int nr, int nrows, double *rows, double *gout = nullptr) {
+                          int o0, int row0, int nr, int nrows, double *rows, double *gout = nullptr,
+                          double *ocost = nullptr) {
   const double *cam = x;
   const double *cap = x + slot_cap(P, c);
   for (int lr = threadIdx.x; lr < nr; lr += kWave) {
@@ -94,8 +126,13 @@ __device__ __forceinline__ void fill_rows(const DevProblem &P, const double *x, 
     // (tag elimination: the e-block is the problem's tag -- projectCorner
     // still takes the capture first; the Jacobian halves come back as e|f)
     const bool sw = group_swapped(P, c);
-    const double r = residual_jacobian_row(cam, sw ? tag : cap, sw ? cap : tag, corner, comp,
-                                           P.corners[8L * obs + 2 * corner + comp], J);
+    double r = residual_jacobian_row(cam, sw ? tag : cap, sw ? cap : tag, corner, comp,
+                                     P.corners[8L * obs + 2 * corner + comp], J);
+    if (kLoss) {
+      // (nr is a multiple of 8: an observation's 8 lanes are in the loop together)
+      const double rho = robustify_row(P.obs_loss_kind[obs], P.obs_loss_a[obs], r, J);
+      if (ocost && (lr & 7) == 0) ocost[lr >> 3] = 0.5 * rho;
+    }
     if (sw) {
 #pragma unroll
       for (int j = 1; j < 7; ++j) {
@@ -176,10 +213,11 @@ __device__ __forceinline__ void load_rows_q(const DevProblem &P, const double *s
 // load_rows_q's rows evaluated again at x instead of read back (the same
 // products in the same order: fill_rows scales J as load_rows_q scales the
 // stored copy, and q is formed from the row as there)
+template <bool kLoss>
 __device__ __forceinline__ void eval_rows_q(const DevProblem &P, const double *x, const double *scale, const double *yF,
                                             double yf, int c, int o0, int row0, int nr, int nrows, double *rows,
                                             double *qv) {
-  fill_rows(P, x, scale, c, o0, row0, nr, nrows, rows);
+  fill_rows<kLoss>(P, x, scale, c, o0, row0, nr, nrows, rows);
   for (int lr = threadIdx.x; lr < nr; lr += kWave) {
     const int row = row0 + lr;
     const int tr = P.tag_row[P.obs_tag[o0 + (row >> 3)]];
@@ -192,7 +230,7 @@ __device__ __forceinline__ void eval_rows_q(const DevProblem &P, const double *x
     qv[lr] = q;
   }
 }
-#define ARSLAM_BACKSUB_ROWS(...) eval_rows_q(P, x, __VA_ARGS__)
+#define ARSLAM_BACKSUB_ROWS(...) eval_rows_q<kLoss>(P, x, __VA_ARGS__)
 #else
 #define ARSLAM_BACKSUB_ROWS(...) load_rows_q(P, __VA_ARGS__)
 #endif
@@ -267,6 +305,10 @@ __device__ __forceinline__ double row_prod(const double *rr, int ca, int cb) {
 // true, a second launch over those (DevProblem::chunk_caps), their rows
 // through LDS 64 at a time.  The rare large capture's loops then cost the
 // usual one no registers or branches.
+// kLoss = true: the loaded problem has robust losses (DevProblem::obs_loss_*);
+// false is the code without them, instruction for instruction.  k_backsub
+// reads the corrected rows k_linearize stored, so its kLoss only reaches the
+// fused candidate cost (and the ARSLAM_BACKSUB_RECOMPUTE rows).
 template <bool kChunked>
 __device__ __forceinline__ int chunk_capture(const DevProblem &P, int &k) {
   const int c = kChunked ? P.chunk_caps[blockIdx.x] : (int)blockIdx.x;
@@ -276,9 +318,14 @@ __device__ __forceinline__ int chunk_capture(const DevProblem &P, int &k) {
 
 // (4 waves per SIMD instead of the 3 its 143 VGPRs allow: a 28-byte spill,
 // 84 -> 71 us on cfg3; 5 waves spills 148 bytes and is slower)
+// (those figures are the compiler's of the time.  Today's gives, under the
+// same attribute, 96 VGPRs and no scratch for <false, false> -- 5 waves --
+// and 128 VGPRs and 12 bytes for <true, false>; with kLoss 98 / 0 and
+// 128 / 88, 4 waves: DESIGN §2b, profiles/loss/resource_usage.txt)
 // Linearize at x: per-observation tag gradient/column norms, per-capture
-// gradient/column norms, cost and camera partials.  Unscaled Jacobian.
-template <bool kChunked>
+// gradient/column norms, cost and camera partials.  Unscaled Jacobian (with
+// kLoss: corrected by sqrt(rho') per observation).
+template <bool kChunked, bool kLoss>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_linearize(DevProblem P, const double *__restrict__ x,
                                                      double *__restrict__ g,
                                                      double *__restrict__ colnorm,
@@ -302,7 +349,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(4, 8))) v
   // around the projection cost the single-chunk code spills)
   auto chunk = [&](int q0) __attribute__((always_inline)) {
     const int kc = min(kObsChunk, k - q0), nr = 8 * kc;
-    fill_rows(P, x, nullptr, c, o0, 8 * q0, nr, nrows, rows, P.jrows);
+    fill_rows<kLoss>(P, x, nullptr, c, o0, 8 * q0, nr, nrows, rows, P.jrows, kLoss ? ocost : nullptr);
     __syncthreads();
     // Every sum below is over rows of one product of two LDS columns (ca, cb),
     // picked per lane up front: one code path for the whole wave (a divergent
@@ -315,7 +362,9 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(4, 8))) v
       double s = 0.0;
 #pragma unroll
       for (int rr = 0; rr < 8; ++rr) s += rq[rr * kRowStride + ca] * rq[rr * kRowStride + cb];
-      if (it == 0) ocost[q] = 0.5 * s;
+      if (it == 0) {
+        if (!kLoss) ocost[q] = 0.5 * s;   // (kLoss: rho / 2, left there by fill_rows)
+      }
       else obs_tg[12L * P.obs_tpos[o0 + q0 + q] + (it - 1)] = s;   // (tag-major: k_lin_reduce reads a tag's at once)
     }
     // per capture: capture gradient (6: E'r), capture column norms (6), f gradient, f column norm
@@ -1047,7 +1096,7 @@ __global__ void k_own_copy(DevProblem P, long first, long count, const double *_
 // k_backsub just formed, held in LDS); camera and tags from x.
 // (kChunked: a capture of more than kObsChunk observations, its rows 64 at a
 // time; else at most one wave of rows)
-template <bool kChunked>
+template <bool kChunked, bool kLoss>
 __device__ __forceinline__ void capture_cost(const DevProblem &P, const double *__restrict__ x, const double *cap,
                                              int c, double *__restrict__ parts) {
   __shared__ double sq[kWave];
@@ -1079,6 +1128,11 @@ __device__ __forceinline__ void capture_cost(const DevProblem &P, const double *
       double s = 0.0;
 #pragma unroll
       for (int rr = 0; rr < 8; ++rr) s += sq[8 * lane + rr];
+      if (kLoss) {   // the cost is rho(s) / 2
+        const int obs = o0 + base / 8 + lane;
+        double rho1;
+        loss_eval(P.obs_loss_kind[obs], P.obs_loss_a[obs], s, &s, &rho1);
+      }
       ocost[lane] = 0.5 * s;
     }
     __syncthreads();
@@ -1099,18 +1153,18 @@ __device__ __forceinline__ void capture_cost(const DevProblem &P, const double *
   }
 }
 
-template <bool kChunked>
+template <bool kChunked, bool kLoss>
 __global__ __launch_bounds__(kWave) void k_cost(DevProblem P, const double *__restrict__ x,
                                                 double *__restrict__ parts) {
   int k;
   const int c = chunk_capture<kChunked>(P, k);
   if (c < 0) return;
-  capture_cost<kChunked>(P, x, x + slot_cap(P, c), c, parts);
+  capture_cost<kChunked, kLoss>(P, x, x + slot_cap(P, c), c, parts);
 }
 
 // Back substitution for capture c, candidate update of its slots and its
 // share of the model cost change.
-template <bool kChunked>
+template <bool kChunked, bool kLoss>
 __global__ __launch_bounds__(kWave) void k_backsub(DevProblem P, const double *__restrict__ x,
                                                    const double *__restrict__ scale,
                                                    const double *__restrict__ diag, double radius,
@@ -1258,7 +1312,7 @@ __global__ __launch_bounds__(kWave) void k_backsub(DevProblem P, const double *_
   // by k_update_f, launched before this kernel
   if (with_cost) {
     __syncthreads();
-    capture_cost<kChunked>(P, xc, capc, c, parts);
+    capture_cost<kChunked, kLoss>(P, xc, capc, c, parts);
   }
 }
 
@@ -1599,6 +1653,30 @@ __global__ void k_debug_rj(int n, const double *__restrict__ cam, const double *
   for (int j = 0; j < 12; ++j) out[3 + j] = j13[1 + j];
 }
 
+// the same rows corrected for each observation's loss (robustify_row, as
+// fill_rows<true> forms them) and rho(s) per observation; 8 n is a multiple of
+// 8, so an observation's 8 lanes are active together
+__global__ void k_debug_rj_loss(int n, const double *__restrict__ cam, const double *__restrict__ cap,
+                                const double *__restrict__ tag, const double *__restrict__ corners,
+                                const unsigned char *__restrict__ kind, const double *__restrict__ a,
+                                double *__restrict__ r, double *__restrict__ J, double *__restrict__ rho) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= 8L * n) return;
+  const long o = e / 8;
+  const int row = (int)(e % 8), corner = row >> 1, comp = row & 1;
+  double j13[13];
+  double rv = residual_jacobian_row(cam + 3 * o, cap + 6 * o, tag + 6 * o, corner, comp,
+                                    corners[8 * o + row], j13);
+  const double rh = robustify_row(kind[o], a[o], rv, j13);
+  r[e] = rv;
+  if (row == 0) rho[o] = rh;
+  double *out = J + e * 15;
+  out[0] = j13[0];
+  out[1] = 0.0;
+  out[2] = 0.0;
+  for (int j = 0; j < 12; ++j) out[3 + j] = j13[1 + j];
+}
+
 // AngleAxisRotatePoint of n (w, p) pairs with the branch each one took
 // (1: theta^2 > DBL_EPSILON, Rodrigues; 0: x + w x p) -- parity of the
 // small-angle branch, ar_slam_util.cpp:145,155.
@@ -1629,9 +1707,13 @@ void launch_linearize(const DevProblem &P, const double *x, double *g, double *c
                       double *obs_tg, double *parts, hipStream_t s) {
   if (P.nc == 0) return;
   const size_t lds = lds_rows(kObsChunk) + sizeof(double) * (kObsChunk + 16);
-  hipLaunchKernelGGL(k_linearize<false>, dim3(P.nc), dim3(kWave), lds, s, P, x, g, colnorm, obs_tg, parts);
+  // (the instance per loaded problem: kLoss iff it has robust losses)
+  const bool loss = P.obs_loss_kind != nullptr;
+  hipLaunchKernelGGL((loss ? k_linearize<false, true> : k_linearize<false, false>), dim3(P.nc), dim3(kWave), lds, s, P,
+                     x, g, colnorm, obs_tg, parts);
   if (P.n_chunk_caps)
-    hipLaunchKernelGGL(k_linearize<true>, dim3(P.n_chunk_caps), dim3(kWave), lds, s, P, x, g, colnorm, obs_tg, parts);
+    hipLaunchKernelGGL((loss ? k_linearize<true, true> : k_linearize<true, false>), dim3(P.n_chunk_caps), dim3(kWave),
+                       lds, s, P, x, g, colnorm, obs_tg, parts);
 }
 
 void launch_lin_reduce(const DevProblem &P, const double *obs_tg, double *g, double *colnorm,
@@ -1723,11 +1805,12 @@ void launch_backsub(const DevProblem &P, const double *x, const double *scale, c
                     bool reuse_ui, bool with_cost) {
   if (P.nc == 0) return;
   const size_t lds = lds_rows(kObsChunk) + sizeof(double) * (8L * kObsChunk + 36 + 36 + 16);
-  hipLaunchKernelGGL(k_backsub<false>, dim3(P.nc), dim3(kWave), lds, s, P, x, scale, diag, radius, yF, xc, parts,
-                     reuse_ui ? 1 : 0, with_cost ? 1 : 0);
+  const bool loss = P.obs_loss_kind != nullptr;
+  hipLaunchKernelGGL((loss ? k_backsub<false, true> : k_backsub<false, false>), dim3(P.nc), dim3(kWave), lds, s, P, x,
+                     scale, diag, radius, yF, xc, parts, reuse_ui ? 1 : 0, with_cost ? 1 : 0);
   if (P.n_chunk_caps)
-    hipLaunchKernelGGL(k_backsub<true>, dim3(P.n_chunk_caps), dim3(kWave), lds, s, P, x, scale, diag, radius, yF, xc,
-                       parts, reuse_ui ? 1 : 0, with_cost ? 1 : 0);
+    hipLaunchKernelGGL((loss ? k_backsub<true, true> : k_backsub<true, false>), dim3(P.n_chunk_caps), dim3(kWave), lds, s,
+                       P, x, scale, diag, radius, yF, xc, parts, reuse_ui ? 1 : 0, with_cost ? 1 : 0);
 }
 
 void launch_update_f(const DevProblem &P, const double *x, const double *scale, const double *yF,
@@ -1739,8 +1822,11 @@ void launch_update_f(const DevProblem &P, const double *x, const double *scale, 
 
 void launch_cost(const DevProblem &P, const double *x, double *parts, hipStream_t s) {
   if (P.nc == 0) return;
-  hipLaunchKernelGGL(k_cost<false>, dim3(P.nc), dim3(kWave), 0, s, P, x, parts);
-  if (P.n_chunk_caps) hipLaunchKernelGGL(k_cost<true>, dim3(P.n_chunk_caps), dim3(kWave), 0, s, P, x, parts);
+  const bool loss = P.obs_loss_kind != nullptr;
+  hipLaunchKernelGGL((loss ? k_cost<false, true> : k_cost<false, false>), dim3(P.nc), dim3(kWave), 0, s, P, x, parts);
+  if (P.n_chunk_caps)
+    hipLaunchKernelGGL((loss ? k_cost<true, true> : k_cost<true, false>), dim3(P.n_chunk_caps), dim3(kWave), 0, s, P, x,
+                       parts);
 }
 
 // The parameter download on one rank: a kernel stores x straight into the
@@ -1806,6 +1892,14 @@ void debug_residual_jacobian(int n, const double *cam, const double *cap, const 
   const long m = 8L * n;
   hipLaunchKernelGGL(k_debug_rj, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, n, cam, cap, tag,
                      corners, r, J);
+}
+
+void debug_residual_jacobian_loss(int n, const double *cam, const double *cap, const double *tag,
+                                  const double *corners, const unsigned char *kind, const double *a, double *r,
+                                  double *J, double *rho, hipStream_t s) {
+  const long m = 8L * n;
+  hipLaunchKernelGGL(k_debug_rj_loss, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, n, cam, cap, tag, corners,
+                     kind, a, r, J, rho);
 }
 
 void debug_set_reduced_diag(const DevProblem &P, double *S, long row, double v, hipStream_t s) {

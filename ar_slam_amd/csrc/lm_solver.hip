@@ -8,6 +8,7 @@
 // problem, the parameters and the reduced system stay resident in HBM.
 #include "host_threads.h"
 #include "lm_internal.h"
+#include "loss.h"
 #include "arslam_lm.h"
 #include "arslam_lm_debug.h"
 
@@ -238,6 +239,24 @@ struct arslam_lm {
   std::vector<double *> cap_ptrs, tag_ptrs;
   std::vector<int> pk_obs_cap, pk_obs_tag;
   std::vector<double> pk_corners;
+  // each residual block's loss (arslam_lm_add_residual_block_loss; the default
+  // loss for arslam_lm_add_residual_block).  Blocks are only ever appended, or
+  // all dropped by arslam_lm_reset (a full load follows), so a resident
+  // problem's losses never go stale under the values-only path, and the
+  // append path uploads the grown arrays with the grown problem.
+  std::vector<unsigned char> pk_loss_kind;
+  std::vector<double> pk_loss_a;
+  int def_loss_kind = ARSLAM_LOSS_NONE;   // arslam_lm_set_loss
+  double def_loss_a = 0.0;
+  std::vector<unsigned char> soa_loss_kind;   // arslam_lm_load_soa's default loss, per observation
+  std::vector<double> soa_loss_a;
+  // the default loss for each of n_obs observations (null arrays: NONE)
+  arslam::ObsLoss default_obs_loss(int n_obs) {
+    if (def_loss_kind == ARSLAM_LOSS_NONE || n_obs <= 0) return arslam::ObsLoss{};
+    soa_loss_kind.assign(n_obs, (unsigned char)def_loss_kind);
+    soa_loss_a.assign(n_obs, def_loss_a);
+    return arslam::ObsLoss{soa_loss_kind.data(), soa_loss_a.data()};
+  }
   std::unordered_set<double *> constant;
   // The pointer-keyed structure (blocks, residuals, constants) changed since
   // the last load: arslam_lm_solve reloads; otherwise it reuses the resident
@@ -275,6 +294,8 @@ struct arslam_lm {
   int *u_chunk_caps = nullptr;
   unsigned char *u_obs_active = nullptr, *u_slot_free = nullptr;
   double *u_corners = nullptr, *u_x0 = nullptr;
+  unsigned char *u_loss_kind = nullptr;   // DevProblem::obs_loss_kind, obs_loss_a (a problem with losses)
+  double *u_loss_a = nullptr;
   long *u_cap_off = nullptr;
   int2 *u_dest_row = nullptr;
   int4 *u_gather_items = nullptr, *u_gather_splits = nullptr;
@@ -457,14 +478,17 @@ struct arslam_lm {
     ready_opt_device = opt.device;
   }
 
-  void load(const arslam_soa_problem *p);
+  // (in_loss, here and in try_extend*: the losses of p's observations, in p's
+  // order, null arrays for none; they go beside the corners into every
+  // host_problem call of the load)
+  void load(const arslam_soa_problem *p, const arslam::ObsLoss &in_loss);
   // (extend_from >= 0: captures [extend_from, nc) were appended to the loaded
   // problem, the others unchanged: the gather plan is extended, not rebuilt)
   void upload_problem(const arslam::HostProblem &h, const arslam::ReducedLayout &L, int extend_from = -1);
   arslam::SchurGather sg;   // the loaded problem's Schur gather plan
   bool sg_ready = false;    // load(): sg was built beside the tile plan (upload_problem keeps it)
-  bool try_extend(const arslam_soa_problem *p);
-  bool try_extend_mixed(const arslam_soa_problem *p);
+  bool try_extend(const arslam_soa_problem *p, const arslam::ObsLoss &in_loss);
+  bool try_extend_mixed(const arslam_soa_problem *p, const arslam::ObsLoss &in_loss);
   arslam::ReducedLayout lay;      // the loaded layout (one rank), kept for try_extend
   bool pk_appended_only = false;  // since the last load only residual blocks of known tags were added
   int setup_kind = ARSLAM_SETUP_LOAD;
@@ -481,6 +505,8 @@ struct arslam_lm {
   std::vector<double> loc_cap, loc_corners;
   std::vector<int> loc_obs_cap, loc_obs_tag;
   std::vector<unsigned char> loc_cap_const;
+  std::vector<unsigned char> loc_loss_kind;   // this rank's observations' losses
+  std::vector<double> loc_loss_a;
   double split_top_work = 0.0, split_max_rank_work = 0.0, split_total_work = 0.0;
   int split_active = 1;   // ranks owning subtrees (RankSplit::n_active)
   // co-visibility of the free tags (a bit matrix, directed edge count as
@@ -626,7 +652,7 @@ long round_up(long v, long m) { return (v + m - 1) / m * m; }
 
 }  // namespace
 
-void arslam_lm::load(const arslam_soa_problem *p_in) {
+void arslam_lm::load(const arslam_soa_problem *p_in, const arslam::ObsLoss &in_loss) {
   const double t_load = now_s();
   loaded = false;
   // (the process's first HIP call starts the runtime, 0.02-0.2 s: the first
@@ -732,13 +758,20 @@ void arslam_lm::load(const arslam_soa_problem *p_in) {
       if (p->cap_const) loc_cap_const[c] = p->cap_const[own_caps[c]];
     }
     loc_obs_cap.clear(); loc_obs_tag.clear(); loc_corners.clear();
+    loc_loss_kind.clear(); loc_loss_a.clear();
+    const bool with_loss = in_loss.kind && in_loss.a;   // (the loss goes with its capture's observations)
     for (int b = 0; b < p->n_obs; ++b) {
       const int lc = loc_of[p->obs_cap[b]];
       if (lc < 0) continue;
       loc_obs_cap.push_back(lc);
       loc_obs_tag.push_back(p->obs_tag[b]);
       loc_corners.insert(loc_corners.end(), p->corners + 8L * b, p->corners + 8L * b + 8);
+      if (with_loss) {
+        loc_loss_kind.push_back(in_loss.kind[b]);
+        loc_loss_a.push_back(in_loss.a[b]);
+      }
     }
+    const arslam::ObsLoss loc_loss{with_loss ? loc_loss_kind.data() : nullptr, with_loss ? loc_loss_a.data() : nullptr};
     arslam_soa_problem pl = *p;
     pl.n_cap = (int)own_caps.size();
     pl.n_obs = (int)loc_obs_cap.size();
@@ -753,14 +786,15 @@ void arslam_lm::load(const arslam_soa_problem *p_in) {
       for (int b = 0; b < p->n_obs; ++b) deg[p->obs_tag[b]] += 1.0;
       deg[p->n_tag] = p->n_obs;
     };
-    h = arslam::host_problem(&pl, global_deg);
+    h = arslam::host_problem(&pl, global_deg, &loc_loss);
     // the layout's tag slots are the whole problem's (3 + 6 nc_full + 6 t + a):
     // renumber them for this rank's parameter vector (3 + 6 nc_own + 6 t + a)
     const long shift = 6L * (p->n_cap - (long)own_caps.size());
     for (int &sl : L.row_slot)
       if (sl >= 3) sl -= (int)shift;
   } else {
-    h = arslam::host_problem(p, nullptr);   // validates p
+    // (the role-swapped and the mixed problem keep p_in's observation order: its losses apply as they are)
+    h = arslam::host_problem(p, nullptr, &in_loss);   // validates p
     if (side == ARSLAM_ELIM_MIXED) arslam::mixed_patch(h, mx, *p_in);
     t_host = now_s();
     // (a grown pointer-keyed problem: a fresh order takes the faster separator search)
@@ -887,6 +921,11 @@ void arslam_lm::upload_problem(const arslam::HostProblem &h, const arslam::Reduc
   upload.add(&u_obs_active, h.obs_active.data(), nb);
   upload.add(&u_slot_free, h.slot_free.data(), n);
   upload.add(&u_corners, h.corners.data(), 8L * nb);
+  const bool has_loss = !h.loss_kind.empty();   // (permuted with the corners by host_problem)
+  if (has_loss) {
+    upload.add(&u_loss_kind, h.loss_kind.data(), nb);
+    upload.add(&u_loss_a, h.loss_a.data(), nb);
+  }
   upload.add(&u_x0, x0.data(), n);
   upload.add(&u_tag_row, L.tag_row.data(), L.tag_row.size());
   upload.add(&u_row_slot, row_slot.data(), row_slot.size());
@@ -1006,6 +1045,8 @@ void arslam_lm::upload_problem(const arslam::HostProblem &h, const arslam::Reduc
   P.cap_blk_start = u_cap_blk_start; P.blk_tag = u_blk_tag;
   P.obs_active = u_obs_active; P.slot_free = u_slot_free;
   P.tag_start = u_tag_start; P.obs_tpos = u_obs_tpos; P.corners = u_corners;
+  P.obs_loss_kind = has_loss ? u_loss_kind : nullptr;
+  P.obs_loss_a = has_loss ? u_loss_a : nullptr;
   P.tag_row = u_tag_row; P.row_slot = u_row_slot;
   P.tile_id = plan.tile_id; P.T = plan.T;
   P.tile_class = multi() && has_f ? plan.tile_class : nullptr;
@@ -1032,7 +1073,7 @@ void arslam_lm::upload_problem(const arslam::HostProblem &h, const arslam::Reduc
 // side, the gather plan and the values are rebuilt and uploaded.  false:
 // load() instead.  (summary.factor_scalar_flops keeps the loaded problem's
 // count: a new coupling inside a fill tile changes the scalar structure.)
-bool arslam_lm::try_extend(const arslam_soa_problem *p) {
+bool arslam_lm::try_extend(const arslam_soa_problem *p, const arslam::ObsLoss &in_loss) {
   // (ARSLAM_ELIM_MIXED whose set was every capture: new captures join it, as in try_extend_mixed)
   if (!loaded || multi() || elim_used != ARSLAM_ELIM_CAPTURES || !has_f ||
       (opt.elimination != ARSLAM_ELIM_AUTO && opt.elimination != ARSLAM_ELIM_CAPTURES &&
@@ -1048,7 +1089,7 @@ bool arslam_lm::try_extend(const arslam_soa_problem *p) {
   }
   if (p->n_tag != nt) return false;
   const double t1 = now_s();
-  arslam::HostProblem h = arslam::host_problem(p, nullptr);
+  arslam::HostProblem h = arslam::host_problem(p, nullptr, &in_loss);
   const double t2 = now_s();
   // the same free tags and camera (the same reduced rows)
   if ((lay.cam_row >= 0) != (h.slot_free[0] != 0)) return false;
@@ -1096,6 +1137,7 @@ bool arslam_lm::try_extend(const arslam_soa_problem *p) {
   for (int &sl : lay.row_slot)
     if (sl >= 3) sl += 6 * (h.nc - nc);
   nc = h.nc;
+  nc_full = h.nc;   // (as try_extend_mixed: reload_values checks the next unchanged solve against it)
   nc_user = p->n_cap;
   nb = h.nb;
   n = h.n;
@@ -1128,7 +1170,7 @@ bool arslam_lm::try_extend(const arslam_soa_problem *p) {
 // problem's Ceres set plus the new captures: an independent set (a new
 // capture is adjacent only to its tags, all reduced), not necessarily the
 // one Ceres would pick on the grown graph; the step is the same exact solve.
-bool arslam_lm::try_extend_mixed(const arslam_soa_problem *p) {
+bool arslam_lm::try_extend_mixed(const arslam_soa_problem *p, const arslam::ObsLoss &in_loss) {
   if (!loaded || multi() || elim_used != ARSLAM_ELIM_MIXED || !has_f || opt.elimination != ARSLAM_ELIM_MIXED)
     return false;
   const double t0 = now_s();
@@ -1175,7 +1217,7 @@ bool arslam_lm::try_extend_mixed(const arslam_soa_problem *p) {
   std::memcpy(m.cap.data(), xv.data() + 3, 6L * ng * sizeof(double));
   if (nf) std::memcpy(m.tag.data(), xv.data() + 3 + 6L * ng, 6L * nf * sizeof(double));
   const double t1 = now_s();
-  arslam::HostProblem h = arslam::host_problem(&m.soa, nullptr);
+  arslam::HostProblem h = arslam::host_problem(&m.soa, nullptr, &in_loss);   // (m.soa: p's observation order)
   arslam::mixed_patch(h, m, *p);
   const double t2 = now_s();
   // the same free f-blocks and camera (the same reduced rows)
@@ -2015,10 +2057,39 @@ int arslam_lm_get_options(const arslam_lm *h, arslam_lm_options *opt) {
   return ARSLAM_OK;
 }
 
+int arslam_lm_set_loss(arslam_lm *h, int kind, double a) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    fail_if(!arslam::loss_valid(kind, a), ARSLAM_E_INVALID_ARG,
+            "loss: kind must be ARSLAM_LOSS_NONE, _HUBER, _SOFT_L_ONE or _CAUCHY, its scale finite and > 0");
+    h->def_loss_kind = kind;
+    h->def_loss_a = kind == ARSLAM_LOSS_NONE ? 0.0 : a;
+    // (the pointer-keyed blocks keep the losses they were added with; the
+    // resident problem is dropped all the same: one rule for both paths)
+    h->loaded = false;
+    h->pk_dirty = true;
+  });
+}
+
+int arslam_lm_get_loss(const arslam_lm *h, int *kind, double *a) {
+  if (!h || !kind || !a) return ARSLAM_E_INVALID_ARG;
+  *kind = h->def_loss_kind;
+  *a = h->def_loss_a;
+  return ARSLAM_OK;
+}
+
 int arslam_lm_add_residual_block(arslam_lm *h, const double corners[8], double *camera,
                                  double *capture, double *tag) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return arslam_lm_add_residual_block_loss(h, corners, camera, capture, tag, h->def_loss_kind, h->def_loss_a);
+}
+
+int arslam_lm_add_residual_block_loss(arslam_lm *h, const double corners[8], double *camera,
+                                      double *capture, double *tag, int kind, double a) {
   if (!h || !corners || !camera || !capture || !tag) return ARSLAM_E_INVALID_ARG;
   return guarded([&] {
+    fail_if(!arslam::loss_valid(kind, a), ARSLAM_E_INVALID_ARG,
+            "loss: kind must be ARSLAM_LOSS_NONE, _HUBER, _SOFT_L_ONE or _CAUCHY, its scale finite and > 0");
     fail_if(h->camera_ptr && h->camera_ptr != camera, ARSLAM_E_UNSUPPORTED,
             "one shared camera block per problem (ArSlamSolver::camera_)");
     fail_if(capture == camera || tag == camera || capture == tag, ARSLAM_E_INVALID_ARG,
@@ -2049,6 +2120,8 @@ int arslam_lm_add_residual_block(arslam_lm *h, const double corners[8], double *
     h->pk_obs_cap.push_back(c);
     h->pk_obs_tag.push_back(t);
     h->pk_corners.insert(h->pk_corners.end(), corners, corners + 8);
+    h->pk_loss_kind.push_back((unsigned char)kind);
+    h->pk_loss_a.push_back(kind == ARSLAM_LOSS_NONE ? 0.0 : a);
   });
 }
 
@@ -2097,6 +2170,7 @@ int arslam_lm_solve(arslam_lm *h, arslam_lm_summary *summary) {
     p.camera = cam.data(); p.cap = cap.data(); p.tag = tag.data();
     p.obs_cap = h->pk_obs_cap.data(); p.obs_tag = h->pk_obs_tag.data();
     p.corners = h->pk_corners.data();
+    const arslam::ObsLoss pk_loss{h->pk_loss_kind.data(), h->pk_loss_a.data()};   // (one per block, beside pk_corners)
     p.camera_const = h->constant.count(h->camera_ptr) ? 1 : 0;
     p.cap_const = cc.data(); p.tag_const = tc.data();
     struct StageGuard {   // (the staging arrays go out of scope; the device problem stays)
@@ -2105,11 +2179,11 @@ int arslam_lm_solve(arslam_lm *h, arslam_lm_summary *summary) {
     } stage_guard{h};
     if (h->loaded && h->pk_loaded && !h->pk_dirty) {
       h->reload_values(&p);   // same problem, new values: no host rebuild, no re-upload of observations
-    } else if (h->loaded && h->pk_loaded && h->pk_appended_only && (h->try_extend(&p) || h->try_extend_mixed(&p))) {
+    } else if (h->loaded && h->pk_loaded && h->pk_appended_only && (h->try_extend(&p, pk_loss) || h->try_extend_mixed(&p, pk_loss))) {
       h->pk_dirty = false;    // appended residual blocks within the loaded tile pattern: layout and plan kept
     } else {
       h->reuse_order = h->pk_loaded;   // a grown pointer-keyed problem (not the first load)
-      h->load(&p);
+      h->load(&p, pk_loss);
       h->reuse_order = false;
       h->pk_loaded = true;
       h->pk_dirty = false;
@@ -2130,6 +2204,7 @@ int arslam_lm_reset(arslam_lm *h) {
     h->cap_of.clear(); h->tag_of.clear();
     h->cap_ptrs.clear(); h->tag_ptrs.clear();
     h->pk_obs_cap.clear(); h->pk_obs_tag.clear(); h->pk_corners.clear();
+    h->pk_loss_kind.clear(); h->pk_loss_a.clear();   // (the default loss stays: it is the handle's, not the problem's)
     h->constant.clear();
     h->loaded = false;
     h->pk_dirty = true;
@@ -2141,13 +2216,24 @@ int arslam_lm_reset(arslam_lm *h) {
 }
 
 int arslam_lm_load_soa(arslam_lm *h, const arslam_soa_problem *p) {
-  if (!h || !p) return ARSLAM_E_INVALID_ARG;
+  return arslam_lm_load_soa_loss(h, p, nullptr, nullptr);
+}
+
+int arslam_lm_load_soa_loss(arslam_lm *h, const arslam_soa_problem *p, const unsigned char *obs_loss_kind,
+                            const double *obs_loss_a) {
+  if (!h || !p || (obs_loss_kind == nullptr) != (obs_loss_a == nullptr)) return ARSLAM_E_INVALID_ARG;
   return guarded([&] {
+    fail_if(p->n_obs < 0, ARSLAM_E_INVALID_ARG, "negative sizes");   // (before n_obs sizes anything here)
+    if (obs_loss_kind)
+      for (int b = 0; b < p->n_obs; ++b)
+        fail_if(!arslam::loss_valid(obs_loss_kind[b], obs_loss_a[b]), ARSLAM_E_INVALID_ARG,
+                "obs_loss: kind must be ARSLAM_LOSS_NONE, _HUBER, _SOFT_L_ONE or _CAUCHY, its scale finite and > 0");
     h->pk_loaded = false;
     h->pk_dirty = true;
     h->reuse_order = false;   // a bulk load never reuses a pointer-keyed problem's order
     h->prev_tag_row.clear();
-    h->load(p);
+    // (the caller's arrays are read during the load only)
+    h->load(p, obs_loss_kind ? arslam::ObsLoss{obs_loss_kind, obs_loss_a} : h->default_obs_loss(p->n_obs));
   });
 }
 
@@ -2166,7 +2252,7 @@ int arslam_lm_solve_soa(arslam_soa_problem *p, const arslam_lm_options *opt,
   int rc = arslam_lm_create(&h, opt);
   if (rc) return rc;
   rc = guarded([&] {
-    h->load(p);
+    h->load(p, arslam::ObsLoss{});   // (a handle of its own: no default loss to apply)
     h->solve(summary);
   });
   arslam_lm_destroy(h);

@@ -479,6 +479,8 @@ void ArSlamSolver::optimize(const Capture &capture) {   // :1001-1018
   solve_log_.push_back(std::move(rec));
 }
 
+int ArSlamSolver::setLoss(int kind, double a) { return arslam_lm_set_loss(problem_, kind, a); }
+
 void ArSlamSolver::resetProblem() { check(arslam_lm_reset(problem_)); }   // :1021-1025
 
 std::vector<Transform> ArSlamSolver::getTransforms() const {   // :1028-1075

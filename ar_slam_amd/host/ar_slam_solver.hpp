@@ -166,6 +166,12 @@ class ArSlamSolver {
   const std::deque<SolveRecord> &solveLog() const { return solve_log_; }
   const std::unordered_set<CaptureHandle, CaptureHandleHash> &unsolvedCaptures() const { return unsolved_captures_; }
   void setVerbose(bool v) { verbose_ = v; }
+  // The ceres::LossFunction of the residual blocks added from now on (the
+  // reference passes nullptr, ar_slam_util.cpp:720-727): arslam_lm_set_loss on
+  // the problem, so it holds for solve, solveIncremental and solveCapture.
+  // localizeMany's batched kernel stays without a loss.  Returns ARSLAM_OK or
+  // ARSLAM_E_INVALID_ARG (the loss is then unchanged).
+  int setLoss(int kind, double a);
 
   // data-store builders (protected in the reference; public here so a host
   // or test can assemble a problem without ROS messages)

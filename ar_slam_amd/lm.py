@@ -44,6 +44,8 @@ EXPORTS = ["arslam_lm_options_init", "arslam_lm_create", "arslam_lm_destroy",
            "arslam_lm_solve_soa", "arslam_comm_unique_id", "arslam_lm_set_comm", "arslam_lm_set_comm_callback",
            "arslam_device_count", "arslam_lm_last_error", "arslam_lm_version",
            "arslam_lm_set_iteration_callback", "arslam_lm_owned_captures",
+           "arslam_lm_set_loss", "arslam_lm_get_loss", "arslam_lm_add_residual_block_loss",
+           "arslam_lm_load_soa_loss", "arslam_debug_residual_jacobian_loss", "arslam_slam_set_loss",
            "arslam_debug_residual_jacobian", "arslam_debug_dense_llt", "arslam_debug_dense_llt_ex",
            "arslam_debug_angle_axis_rotate", "arslam_lm_debug_force_indefinite",
            "arslam_lm_debug_force_multirank", "arslam_lm_debug_break_dependency", "arslam_lm_debug_tag_pair_tile",
@@ -68,6 +70,8 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
 SOLVER_CONTINUE, SOLVER_ABORT, SOLVER_TERMINATE_SUCCESSFULLY = 0, 1, 2
 ELIM_AUTO, ELIM_CAPTURES, ELIM_TAGS, ELIM_MIXED = 0, 1, 2, 3   # arslam_lm_options.elimination
 SETUP_LOAD, SETUP_VALUES, SETUP_APPEND = 0, 1, 2   # arslam_lm_summary.setup_kind
+# ceres::LossFunction of a residual block (arslam_lm.h ARSLAM_LOSS_*); a loss is (kind, a)
+LOSS_NONE, LOSS_HUBER, LOSS_SOFT_L_ONE, LOSS_CAUCHY = 0, 1, 2, 3
 _ip = C.POINTER(C.c_int)
 _up = C.POINTER(C.c_ubyte)
 
@@ -208,6 +212,13 @@ def lib():
     L.arslam_lm_destroy.argtypes = [C.c_void_p]
     L.arslam_lm_destroy.restype = None
     L.arslam_lm_add_residual_block.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp]
+    if hasattr(L, "arslam_lm_set_loss"):   # (absent from older variant builds under A/B)
+        L.arslam_lm_add_residual_block_loss.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, C.c_int, C.c_double]
+        L.arslam_lm_set_loss.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        L.arslam_lm_get_loss.argtypes = [C.c_void_p, _ip, _dp]
+        L.arslam_lm_load_soa_loss.argtypes = [C.c_void_p, C.POINTER(SoaProblem), _up, _dp]
+        L.arslam_debug_residual_jacobian_loss.argtypes = [C.c_int, _dp, _dp, _dp, _dp, _up, _dp, _dp, _dp, _dp]
+        L.arslam_slam_set_loss.argtypes = [C.c_void_p, C.c_int, C.c_double]
     L.arslam_lm_set_parameter_block_constant.argtypes = [C.c_void_p, _dp]
     L.arslam_lm_set_parameter_block_variable.argtypes = [C.c_void_p, _dp]
     L.arslam_lm_solve.argtypes = [C.c_void_p, C.POINTER(Summary)]
@@ -284,8 +295,18 @@ class _Soa:
 
 
 def solve_soa(camera, cap, tag, obs_cap, obs_tag, corners, camera_const=False, cap_const=None,
-              tag_const=None, **opts):
-    """One-shot bulk solve.  Returns (camera, cap, tag, summary dict)."""
+              tag_const=None, loss=None, obs_loss=None, **opts):
+    """One-shot bulk solve.  Returns (camera, cap, tag, summary dict).
+    loss = (kind, a): every observation's robust loss; obs_loss = (kinds[n_obs], a[n_obs]): one per
+    observation (see ResidentProblem)."""
+    if loss is not None or obs_loss is not None:
+        R = ResidentProblem(camera, cap, tag, obs_cap, obs_tag, corners, camera_const, cap_const, tag_const,
+                            loss=loss, obs_loss=obs_loss, **opts)
+        try:
+            s = R.solve()
+            return R.camera, R.cap, R.tag, s
+        finally:
+            R.close()
     A = _Soa(camera, cap, tag, obs_cap, obs_tag, corners, camera_const, cap_const, tag_const)
     s = Summary()
     _check(lib().arslam_lm_solve_soa(C.byref(A.s), C.byref(make_options(**opts)), C.byref(s)))
@@ -304,8 +325,8 @@ def warm_up(device=0):
     return time.perf_counter() - t
 
 
-def solve_graph(g, **opts):
-    return solve_soa(g.camera, g.cap, g.tag, g.obs_cap, g.obs_tag, g.corners, **opts)
+def solve_graph(g, loss=None, obs_loss=None, **opts):
+    return solve_soa(g.camera, g.cap, g.tag, g.obs_cap, g.obs_tag, g.corners, loss=loss, obs_loss=obs_loss, **opts)
 
 
 class _Handle:
@@ -331,6 +352,17 @@ class _Handle:
         o = Options()
         _check(lib().arslam_lm_get_options(self._h, C.byref(o)))
         return o
+
+    def set_loss(self, kind, a=0.0):
+        """The handle's default loss (LOSS_*, scale a): what add_residual_block gives the blocks
+        added afterwards and a bulk load gives every observation.  Drops a loaded SoA problem."""
+        _check(lib().arslam_lm_set_loss(self._h, int(kind), float(a)))
+
+    def get_loss(self):
+        """(kind, a) of the default loss."""
+        k, a = C.c_int(0), C.c_double(0.0)
+        _check(lib().arslam_lm_get_loss(self._h, C.byref(k), C.byref(a)))
+        return k.value, a.value
 
     def set_iteration_callback(self, fn):
         """ceres::IterationCallback: fn(iteration dict) -> SOLVER_CONTINUE / SOLVER_ABORT /
@@ -391,14 +423,27 @@ class ResidentProblem(_Handle):
     """SoA problem uploaded once to HBM; ``solve()`` restarts from the loaded state."""
 
     def __init__(self, camera, cap, tag, obs_cap, obs_tag, corners, camera_const=False,
-                 cap_const=None, tag_const=None, comm=None, force_multirank=False, **opts):
+                 cap_const=None, tag_const=None, comm=None, force_multirank=False, loss=None, obs_loss=None,
+                 **opts):
+        """loss = (kind, a): the robust loss of every observation (the handle's default loss);
+        obs_loss = (kinds[n_obs], a[n_obs]): one loss per observation, in observation order."""
         super().__init__(**opts)
         if force_multirank:
             self.debug_force_multirank(True)
         if comm is not None:
             self.set_comm(*comm)
+        if loss is not None:
+            self.set_loss(*loss)
         self.A = _Soa(camera, cap, tag, obs_cap, obs_tag, corners, camera_const, cap_const, tag_const)
-        _check(lib().arslam_lm_load_soa(self._h, C.byref(self.A.s)))
+        if obs_loss is None:
+            _check(lib().arslam_lm_load_soa(self._h, C.byref(self.A.s)))
+        else:
+            kinds = np.ascontiguousarray(obs_loss[0], np.uint8).reshape(-1)
+            scales = _f64(obs_loss[1]).reshape(-1)
+            if kinds.shape[0] != self.A.s.n_obs or scales.shape[0] != self.A.s.n_obs:
+                raise ValueError("obs_loss: one kind and one scale per observation")
+            _check(lib().arslam_lm_load_soa_loss(self._h, C.byref(self.A.s), kinds.ctypes.data_as(_up),
+                                                 scales.ctypes.data_as(_dp)))
 
     def solve(self):
         s = Summary()
@@ -446,9 +491,15 @@ class Problem(_Handle):
             raise TypeError(f"parameter block must be a C-contiguous float64 array of size {n}")
         return a.ctypes.data_as(_dp)
 
-    def add_residual_block(self, corners, camera, capture, tag):
+    def add_residual_block(self, corners, camera, capture, tag, loss=None):
+        """loss = (kind, a): this block's own robust loss; None: the handle's default (set_loss)."""
         c = _f64(corners).reshape(8)
         self._keep += [camera, capture, tag]
+        if loss is not None:
+            _check(lib().arslam_lm_add_residual_block_loss(self._h, c.ctypes.data_as(_dp),
+                                                           self._block(camera, 3), self._block(capture, 6),
+                                                           self._block(tag, 6), int(loss[0]), float(loss[1])))
+            return
         _check(lib().arslam_lm_add_residual_block(self._h, c.ctypes.data_as(_dp),
                                                   self._block(camera, 3), self._block(capture, 6),
                                                   self._block(tag, 6)))
@@ -495,6 +546,27 @@ def debug_residual_jacobian(cam, cap, tag, corners):
                                                 tag.ctypes.data_as(_dp), corners.ctypes.data_as(_dp),
                                                 r.ctypes.data_as(_dp), J.ctypes.data_as(_dp)))
     return r, J
+
+
+def debug_residual_jacobian_loss(cam, cap, tag, corners, kinds, a):
+    """Device residuals (n,8) and Jacobians (n,8,15) of n independent observations after each one's
+    robust loss (kinds[n] LOSS_*, a[n]): the rows times sqrt(rho'(s)); and rho(s) (n,)."""
+    cap = _f64(cap, (-1, 6))
+    n = cap.shape[0]
+    cam = _f64(np.broadcast_to(np.asarray(cam, np.float64), (n, 3)))
+    tag = _f64(tag, (-1, 6))
+    corners = _f64(corners, (-1, 8))
+    kinds = np.ascontiguousarray(np.broadcast_to(np.asarray(kinds), (n,)), np.uint8)
+    a = _f64(np.broadcast_to(np.asarray(a, np.float64), (n,)))
+    r = np.zeros((n, 8))
+    J = np.zeros((n, 8, 15))
+    rho = np.zeros(n)
+    _check(lib().arslam_debug_residual_jacobian_loss(n, cam.ctypes.data_as(_dp), cap.ctypes.data_as(_dp),
+                                                     tag.ctypes.data_as(_dp), corners.ctypes.data_as(_dp),
+                                                     kinds.ctypes.data_as(_up), a.ctypes.data_as(_dp),
+                                                     r.ctypes.data_as(_dp), J.ctypes.data_as(_dp),
+                                                     rho.ctypes.data_as(_dp)))
+    return r, J, rho
 
 
 def debug_angle_axis_rotate(w, p):
@@ -768,6 +840,11 @@ class SlamSolver:
             self.close()
         except Exception:
             pass
+
+    def set_loss(self, kind, a=0.0):
+        """The robust loss (LOSS_*, scale a) of every residual block added from now on: solve,
+        solve_incremental and the solveCapture calls inside them.  localize_many has none."""
+        _check(lib().arslam_slam_set_loss(self._h, int(kind), C.c_double(float(a))))
 
     def load_yaml(self, path):
         _check(lib().arslam_slam_load_yaml(self._h, str(path).encode()))

@@ -79,6 +79,22 @@ enum {
   ARSLAM_RULE_INVALID_STEPS = 6, ARSLAM_RULE_EVAL_FAILED = 7, ARSLAM_RULE_USER_CALLBACK = 8
 };
 
+/* ceres::LossFunction of a residual block (Ceres 2.0 loss_function.cc), with
+ * s = |r|^2 over the block's 8 residuals, scale a and b = a^2; the cost is
+ * 1/2 sum rho(s):
+ *   NONE        rho = s                          (the nullptr of AddResidualBlock)
+ *   HUBER       rho = s (s <= b), 2 a sqrt(s) - b   ceres::HuberLoss(a)
+ *   SOFT_L_ONE  rho = 2 b (sqrt(1 + s/b) - 1)       ceres::SoftLOneLoss(a)
+ *   CAUCHY      rho = b log(1 + s/b)                ceres::CauchyLoss(a)
+ * As in Ceres (corrector.cc; all three have rho'' <= 0) the linearization
+ * uses sqrt(rho') r and sqrt(rho') J per block and the cost rho itself: the
+ * gradient, Jacobi scaling, Schur complement, model cost change and step
+ * quality all work on the corrected rows.  Later kinds (Tolerant, Tukey,
+ * Arctan, Scaled, Composed) would append to the enum; any other value is
+ * ARSLAM_E_INVALID_ARG today, and so is a scale that is not finite or not
+ * > 0 for every kind but NONE (which ignores it). */
+enum { ARSLAM_LOSS_NONE = 0, ARSLAM_LOSS_HUBER = 1, ARSLAM_LOSS_SOFT_L_ONE = 2, ARSLAM_LOSS_CAUCHY = 3 };
+
 /* ceres::Solver::Options subset used by ArSlamSolver::optimize
  * (ar_slam_util.cpp:1003-1012); defaults from arslam_lm_options_init are
  * the reference's values (max_num_iterations = 50, DENSE_SCHUR) plus Ceres
@@ -127,7 +143,8 @@ typedef struct {
   int num_successful_steps, num_unsuccessful_steps;
   int num_linear_solves;        /* trust-region step computations = LM iterations of the metric */
   double initial_cost, final_cost, fixed_cost;
-  double final_rms_px;          /* sqrt(2 final_cost / (4 n_obs)) */
+  double final_rms_px;          /* sqrt(2 final_cost / (4 n_obs)); with a loss set final_cost is the
+                                   robustified cost 1/2 sum rho(s), so this is the robustified figure */
   int n_obs, n_reduced;         /* residual blocks; size of the reduced (tag+camera) system */
   double setup_time_s;          /* host assembly + upload */
   int setup_kind;               /* ARSLAM_SETUP_*: how the problem reached the device for this solve */
@@ -208,6 +225,20 @@ int arslam_lm_get_options(const arslam_lm *h, arslam_lm_options *opt);
 int arslam_lm_add_residual_block(arslam_lm *h, const double corners[8], double *camera,
                                  double *capture, double *tag);
 
+/* The handle's default loss: what arslam_lm_add_residual_block gives the
+ * blocks added afterwards (Ceres binds a loss at AddResidualBlock; a caller
+ * that passed `new ceres::HuberLoss(a)` there calls set_loss(ARSLAM_LOSS_HUBER,
+ * a) once) and what arslam_lm_load_soa gives every observation.  It drops a
+ * problem loaded by arslam_lm_load_soa (load again), as arslam_lm_set_comm
+ * does; arslam_lm_reset keeps it.  A rejected call leaves the handle as it was. */
+int arslam_lm_set_loss(arslam_lm *h, int kind, double a);
+int arslam_lm_get_loss(const arslam_lm *h, int *kind, double *a);
+
+/* arslam_lm_add_residual_block with this block's own loss
+ * (AddResidualBlock(cost, new ceres::CauchyLoss(a), camera, capture, tag)). */
+int arslam_lm_add_residual_block_loss(arslam_lm *h, const double corners[8], double *camera,
+                                      double *capture, double *tag, int kind, double a);
+
 /* problem_.SetParameterBlockConstant(block) -- ar_slam_util.cpp:965, 972 */
 int arslam_lm_set_parameter_block_constant(arslam_lm *h, double *block);
 int arslam_lm_set_parameter_block_variable(arslam_lm *h, double *block);
@@ -225,8 +256,15 @@ int arslam_lm_num_residual_blocks(const arslam_lm *h);
  * written to the SoA arrays given at load time. */
 int arslam_lm_load_soa(arslam_lm *h, const arslam_soa_problem *p);
 int arslam_lm_solve_loaded(arslam_lm *h, arslam_lm_summary *summary);
+/* arslam_lm_load_soa with one loss per observation, in p's observation order
+ * (obs_loss_kind[n_obs] ARSLAM_LOSS_*, obs_loss_a[n_obs]); NULL for both: the
+ * handle's default loss for every observation.  Several ranks: every rank
+ * passes the whole problem's arrays, as it does the problem. */
+int arslam_lm_load_soa_loss(arslam_lm *h, const arslam_soa_problem *p,
+                            const unsigned char *obs_loss_kind, const double *obs_loss_a);
 
-/* One-shot bulk solve. */
+/* One-shot bulk solve (a handle of its own, so no loss: with one, create a
+ * handle, arslam_lm_set_loss or arslam_lm_load_soa_loss, arslam_lm_solve_loaded). */
 int arslam_lm_solve_soa(arslam_soa_problem *p, const arslam_lm_options *opt,
                         arslam_lm_summary *summary);
 

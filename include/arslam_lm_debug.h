@@ -19,6 +19,15 @@ extern "C" {
 int arslam_debug_residual_jacobian(int n, const double *cam, const double *cap, const double *tag,
                                    const double *corners, double *r, double *J);
 
+/* The same rows after each observation's robust loss (arslam_lm.h
+ * ARSLAM_LOSS_*; kind [n], a [n]), through the device functions k_linearize
+ * uses: r [n*8] and J [n*8*15] times sqrt(rho'(s)), s = |r|^2 over the
+ * observation's 8 residuals, and rho [n] = rho(s) (the observation's cost is
+ * rho / 2). */
+int arslam_debug_residual_jacobian_loss(int n, const double *cam, const double *cap, const double *tag,
+                                        const double *corners, const unsigned char *kind, const double *a,
+                                        double *r, double *J, double *rho);
+
 /* ceres::AngleAxisRotatePoint (rotation.h; called at ar_slam_util.cpp:145,155)
  * of n points p[n*3] by angle-axis w[n*3] on the device -> out[n*3], and the
  * branch each took: branch[i] = 1 if theta^2 > DBL_EPSILON (Rodrigues), 0 for

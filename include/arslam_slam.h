@@ -34,6 +34,14 @@ typedef struct {
 int arslam_slam_create(arslam_slam **out, const arslam_lm_options *opt);
 void arslam_slam_destroy(arslam_slam *h);
 int arslam_slam_set_verbose(arslam_slam *h, int verbose);
+/* The robust loss (arslam_lm.h ARSLAM_LOSS_*, scale a) of every residual block
+ * the solver adds from now on -- the reference passes nullptr to
+ * AddResidualBlock (ar_slam_util.cpp:720-727); this is the mirror of passing
+ * `new ceres::HuberLoss(a)` there.  It applies to solve, solveIncremental and
+ * the solveCapture calls inside them.  localizeMany (the batched device
+ * localizer, arslam_localize.h) stays without a loss.  An invalid kind or
+ * scale returns ARSLAM_E_INVALID_ARG and leaves the loss unchanged. */
+int arslam_slam_set_loss(arslam_slam *h, int kind, double a);
 
 int arslam_slam_load_yaml(arslam_slam *h, const char *path);
 int arslam_slam_load_yaml_string(arslam_slam *h, const char *text);
