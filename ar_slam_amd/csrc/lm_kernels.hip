@@ -74,16 +74,6 @@ __device__ __forceinline__ double lm_d2(const double *diag, long slot, double ra
   return d * d;
 }
 
-// The sum of v over an observation's 8 residual rows, which sit in 8
-// consecutive lanes (lane = 8 q + row): wave_reduce's first three steps, so
-// the 8 lanes end with the same bits.  The 8 lanes are active together.
-__device__ __forceinline__ double obs_sum8(double v) {
-  v += dpp_f64<0xB1>(v);    // lane ^ 1
-  v += dpp_f64<0x4E>(v);    // lane ^ 2
-  v += dpp_f64<0x141>(v);   // row_half_mirror: the other quad of the 8
-  return v;
-}
-
 // Ceres' corrector (corrector.cc, alpha = 0: every loss of loss.h has
 // rho'' <= 0) on one row of an observation whose 8 rows sit in 8 consecutive
 // lanes: r and its 13 Jacobian entries times sqrt(rho'(s)), s = |r|^2 over

@@ -13,6 +13,7 @@
 // round trip until every query has terminated.  The control flow restates
 // the oracle's or_solve (oracle/arslam_oracle.c) for a single free block.
 #include "lm_internal.h"
+#include "loss.h"
 #include "projection.h"
 #include "arslam_localize.h"
 
@@ -43,6 +44,10 @@ struct LocParams {
   int init_from_map, max_k;
   int max_iters, max_invalid, jacobi;
   double ftol, gtol, ptol, r0, rmax, rmin, min_rel, dmin, dmax;
+  // per-observation robust loss (ARSLAM_LOSS_*, scale), read by the kLoss
+  // instances only; null when no observation of the batch has one
+  const unsigned char *lk;     // [nb]
+  const double *la;            // [nb]
 };
 
 // ---- initialisers (ar_slam_util.cpp:41-128; Ceres 2.0 rotation.h) ----
@@ -242,9 +247,32 @@ __device__ __forceinline__ void query_sums28(double *red, int lane, double c, co
 template <int LPQ>
 constexpr int sums_off() { return 28 * (LPQ + 2); }
 
-template <int NCH, int LPQ>
-__device__ bool evaluate_jacobian(const LocParams &p, const double *rc, int nrow, const double *x, int lane,
-                                  double &cost, double *red,
+// An observation's loss as staged in LDS beside rc: {kind, scale}.
+typedef double LossKA __attribute__((ext_vector_type(2)));
+
+// Ceres' corrector (corrector.cc, alpha = 0: every loss of loss.h has
+// rho'' <= 0) on row R of a query.  Row R = 8 obs + 2 corner + comp sits in
+// lane R % LPQ of chunk R / LPQ, so an observation is 8 consecutive lanes of
+// one chunk (LPQ = 32 and 64 alike) and nrow = 8 k puts the 8 lanes inside or
+// outside R < nrow together: obs_sum8 runs under that test and reads its own
+// group only -- never a group past nrow, never the other half-wave's query
+// (whose LM loop may have diverged: EXEC is then partial, in whole groups).
+// Returns rho(s) and leaves sqrt(rho'(s)) in w; the same bits in the 8 lanes.
+__device__ __forceinline__ double robust_weight(const LossKA *lka, int R, double r, double &w) {
+  const double s = obs_sum8(r * r);
+  const LossKA ka = lka[R >> 3];
+  double rho, rho1;
+  loss_eval((int)ka.x, ka.y, s, &rho, &rho1);
+  w = sqrt(rho1);
+  return rho;
+}
+
+// kLoss: the rows are the corrected ones, sqrt(rho') (J | r) per observation,
+// and the cost is sum rho / 2; lka = the query's staged losses.  kLoss = false
+// is the code without a loss (lka unused).
+template <int NCH, int LPQ, bool kLoss>
+__device__ bool evaluate_jacobian(const LocParams &p, const double *rc, const LossKA *lka, int nrow,
+                                  const double *x, int lane, double &cost, double *red,
                                   const AngleAxis *ac_pre = nullptr) {
   double c = 0.0, gl[6] = {0, 0, 0, 0, 0, 0}, hl[21];
 #pragma unroll
@@ -264,9 +292,18 @@ __device__ bool evaluate_jacobian(const LocParams &p, const double *rc, int nrow
     if (R < nrow) {
       const double *rr = rc + 4 * R;   // (the row's corner world point and observation, LDS)
       double j6[6];
-      const double r = loc_row(F, x, rr, p.cam[0], R & 1, rr[3], j6);
-      bad = bad || !isfinite(r);
-      c += r * r;
+      double r = loc_row(F, x, rr, p.cam[0], R & 1, rr[3], j6);
+      bad = bad || !isfinite(r);   // (the uncorrected residual)
+      if (kLoss) {
+        double w;
+        const double rho = robust_weight(lka, R, r, w);
+        c += (R & 7) == 0 ? rho : 0.0;   // each observation's rho once
+        r *= w;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) j6[j] *= w;
+      } else {
+        c += r * r;
+      }
 #pragma unroll
       for (int j = 0; j < 6; ++j) {
         gl[j] += j6[j] * r;
@@ -283,9 +320,9 @@ __device__ bool evaluate_jacobian(const LocParams &p, const double *rc, int nrow
   return wave_max<LPQ>(bad ? 1.0 : 0.0) == 0.0;
 }
 
-template <int NCH, int LPQ>
-__device__ double evaluate_cost(const LocParams &p, const double *rc, int nrow, const double *x, int lane, bool &finite,
-                              CapFrame &F) {
+template <int NCH, int LPQ, bool kLoss>
+__device__ double evaluate_cost(const LocParams &p, const double *rc, const LossKA *lka, int nrow, const double *x,
+                                int lane, bool &finite, CapFrame &F) {
   cap_frame(x, F, false);
   double c = 0.0;
   bool bad = false;
@@ -296,7 +333,13 @@ __device__ double evaluate_cost(const LocParams &p, const double *rc, int nrow, 
       const double *rr = rc + 4 * R;
       const double r = loc_row(F, x, rr, p.cam[0], R & 1, rr[3], nullptr);
       bad = bad || !isfinite(r);
-      c += r * r;
+      if (kLoss) {
+        double w;
+        const double rho = robust_weight(lka, R, r, w);
+        c += (R & 7) == 0 ? rho : 0.0;
+      } else {
+        c += r * r;
+      }
     }
   }
   finite = wave_max<LPQ>(bad ? 1.0 : 0.0) == 0.0;
@@ -308,7 +351,9 @@ __device__ double evaluate_cost(const LocParams &p, const double *rc, int nrow, 
 // capture's rotation then cost half the instructions per query), NCH =
 // LPQ-row chunks per query (k <= NCH LPQ / 8 observations).  One wavefront
 // per workgroup, so a finished wave's slot is reused at once.
-template <int NCH, int LPQ>
+// kLoss = true: some observation of the batch has a robust loss (p.lk, p.la);
+// a batch without one runs the kLoss = false instances, the code without a loss.
+template <int NCH, int LPQ, bool kLoss>
 __global__ __launch_bounds__(64, 2) void k_localize(LocParams p) {
   const int lane = threadIdx.x & (LPQ - 1);
   const int q = blockIdx.x * (64 / LPQ) + threadIdx.x / LPQ;
@@ -320,6 +365,12 @@ __global__ __launch_bounds__(64, 2) void k_localize(LocParams p) {
   // that every cost and Jacobian evaluation repeated)
   __shared__ __attribute__((aligned(16))) double rc_all[(64 / LPQ) * NCH * LPQ * 4];
   double *rc = rc_all + (threadIdx.x / LPQ) * NCH * LPQ * 4;
+  // kLoss: each observation's {kind, scale}, staged once per query like rc
+  // (every cost and Jacobian evaluation reads them; the 8 lanes of an
+  // observation read one address, a broadcast)
+  constexpr int kObsPerQuery = NCH * LPQ / 8;
+  __shared__ LossKA lka_all[kLoss ? (64 / LPQ) * kObsPerQuery : 1];
+  LossKA *lka = lka_all + (kLoss ? (threadIdx.x / LPQ) * kObsPerQuery : 0);
   if (q >= p.nq) return;
   const int o0 = p.qs[q], k = p.qs[q + 1] - o0;
   arslam_localize_result res;
@@ -355,6 +406,8 @@ __global__ __launch_bounds__(64, 2) void k_localize(LocParams p) {
       typedef double d2 __attribute__((ext_vector_type(2)));
       reinterpret_cast<d2 *>(rc + 4 * R)[0] = d2{a[0], a[1]};
       reinterpret_cast<d2 *>(rc + 4 * R)[1] = d2{a[2], p.corners[8L * o + row]};
+      if (kLoss && row == 0)
+        lka[R >> 3] = LossKA{(double)p.lk[o], p.la[o]};
     }
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -366,7 +419,7 @@ __global__ __launch_bounds__(64, 2) void k_localize(LocParams p) {
   // J'r and J'J of the last linearization, in LDS (column norms squared = diag(H): HD(j))
   const double *g = red + sums_off<LPQ>() + 1, *H = red + sums_off<LPQ>() + 7;
   double x_norm = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3] + x[4] * x[4] + x[5] * x[5]);
-  bool finite = evaluate_jacobian<NCH, LPQ>(p, rc, nrow, x, lane, cost, red);
+  bool finite = evaluate_jacobian<NCH, LPQ, kLoss>(p, rc, lka, nrow, x, lane, cost, red);
   res.initial_cost = cost;
   if (!finite) {
     res.status = ARSLAM_FAILURE;
@@ -504,7 +557,7 @@ __global__ __launch_bounds__(64, 2) void k_localize(LocParams p) {
       }
       bool cfin = true;
       CapFrame Fc;
-      double cand = evaluate_cost<NCH, LPQ>(p, rc, nrow, xc, lane, cfin, Fc);
+      double cand = evaluate_cost<NCH, LPQ, kLoss>(p, rc, lka, nrow, xc, lane, cfin, Fc);
       if (!cfin) cand = DBL_MAX;
       // ParameterToleranceReached / FunctionToleranceReached
       if (sqrt(sq) <= p.ptol * (x_norm + p.ptol)) { res.status = ARSLAM_CONVERGENCE; res.rule = ARSLAM_RULE_PARAMETER; break; }
@@ -515,7 +568,7 @@ __global__ __launch_bounds__(64, 2) void k_localize(LocParams p) {
 #pragma unroll
         for (int j = 0; j < 6; ++j) x[j] = xc[j];
         x_norm = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3] + x[4] * x[4] + x[5] * x[5]);
-        (void)evaluate_jacobian<NCH, LPQ>(p, rc, nrow, x, lane, cost, red, &Fc.ac);
+        (void)evaluate_jacobian<NCH, LPQ, kLoss>(p, rc, lka, nrow, x, lane, cost, red, &Fc.ac);
         gmax = 0.0;
 #pragma unroll
         for (int j = 0; j < 6; ++j) gmax = fmax(gmax, fabs(g[j]));
@@ -537,6 +590,45 @@ __global__ __launch_bounds__(64, 2) void k_localize(LocParams p) {
 #pragma unroll
     for (int j = 0; j < 6; ++j) p.pose_out[6L * q + j] = x[j];
   }
+}
+
+// What the loss did to each observation at the returned pose: the plain
+// s = |r|^2 over the observation's 8 residuals and the weight w = rho'(s)
+// its rows carry (1 without a loss: lk == null); -1 for both on the
+// observations of a skipped query.  One 64-thread block per query, thread j
+// its observation j (k <= ARSLAM_LOC_MAX_OBS = 64).  Runs only on request.
+__global__ __launch_bounds__(64) void k_localize_terms(int nq, const double *__restrict__ cam,
+                                                       const int *__restrict__ qs, const int *__restrict__ ot,
+                                                       const double *__restrict__ corners,
+                                                       const double *__restrict__ aw,
+                                                       const double *__restrict__ pose,
+                                                       const arslam_localize_result *__restrict__ res,
+                                                       const unsigned char *__restrict__ lk,
+                                                       const double *__restrict__ la, double *__restrict__ sq_out,
+                                                       double *__restrict__ w_out) {
+  const int q = blockIdx.x;
+  if (q >= nq) return;
+  const int o0 = qs[q], k = qs[q + 1] - o0;
+  if ((int)threadIdx.x >= k) return;
+  const int o = o0 + (int)threadIdx.x;
+  double s = -1.0, w = -1.0;
+  if (res[q].status != ARSLAM_LOC_SKIPPED) {
+    double x[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) x[j] = pose[6L * q + j];
+    CapFrame F;
+    cap_frame(x, F, false);
+    s = 0.0;
+    for (int row = 0; row < 8; ++row) {
+      const double r = loc_row(F, x, aw + 4L * (4 * ot[o] + (row >> 1)), cam[0], row & 1, corners[8L * o + row],
+                               nullptr);
+      s += r * r;
+    }
+    double rho;
+    loss_eval(lk ? lk[o] : ARSLAM_LOSS_NONE, lk ? la[o] : 0.0, s, &rho, &w);
+  }
+  sq_out[o] = s;
+  w_out[o] = w;
 }
 
 }  // namespace
@@ -590,6 +682,17 @@ struct arslam_localizer {
   DBuf<int> qs, ot;
   DBuf<unsigned char> tim;
   DBuf<arslam_localize_result> res;
+  // Robust losses.  The default (set_loss) holds for every observation of a
+  // batch loaded without arrays; a batch's own arrays (load_loss) override it.
+  // The device copy is made by the next solve (loss_dirty), so set_loss needs
+  // no reload; lk / la then stay what the last solve used (observation_terms).
+  int loss_kind = ARSLAM_LOSS_NONE;
+  double loss_a = 0.0;
+  std::vector<unsigned char> obs_kind;   // the loaded batch's arrays, empty = the default
+  std::vector<double> obs_a;
+  bool has_obs_loss = false, loss_dirty = true, any_loss = false, solved = false;
+  DBuf<unsigned char> lk;
+  DBuf<double> la, terms;
 
   ~arslam_localizer() {
     if (ev0) (void)hipEventDestroy(ev0);
@@ -612,10 +715,22 @@ struct arslam_localizer {
     }
   }
 
-  void load(const arslam_localize_batch *b) {
+  // (before any device call: a host without a GPU answers INVALID_ARG, and a
+  // rejected loss leaves the handle as it was)
+  static void check_loss(int kind, double a) {
+    arslam::api_check(arslam::loss_valid(kind, a), ARSLAM_E_INVALID_ARG,
+                      "loss: unknown kind, or a scale that is not finite and > 0");
+  }
+
+  // kinds / scales [n_obs]: the batch's own losses, both null = the handle's default
+  void load(const arslam_localize_batch *b, const unsigned char *kinds = nullptr, const double *scales = nullptr) {
     using arslam::api_check;
     api_check(b != nullptr, ARSLAM_E_INVALID_ARG, "null batch");
     api_check(b->n_query >= 0 && b->n_tag >= 0 && b->n_obs >= 0, ARSLAM_E_INVALID_ARG, "negative sizes");
+    api_check((kinds == nullptr) == (scales == nullptr), ARSLAM_E_INVALID_ARG,
+              "obs_loss_kind and obs_loss_a: both or neither");
+    if (kinds)
+      for (int o = 0; o < b->n_obs; ++o) check_loss(kinds[o], scales[o]);
     api_check(b->camera && b->pose && (!b->n_tag || b->tag) && b->query_start, ARSLAM_E_INVALID_ARG,
               "null arrays");
     api_check(!b->n_obs || (b->obs_tag && b->corners), ARSLAM_E_INVALID_ARG, "null observation arrays");
@@ -629,7 +744,11 @@ struct arslam_localizer {
     for (int o = 0; o < b->n_obs; ++o)
       api_check(b->obs_tag[o] >= 0 && b->obs_tag[o] < b->n_tag, ARSLAM_E_INVALID_ARG, "obs_tag out of range");
     ensure_stream();
-    loaded = false;
+    loaded = solved = false;
+    has_obs_loss = kinds != nullptr;
+    obs_kind.assign(kinds, kinds + (kinds ? b->n_obs : 0));
+    obs_a.assign(scales, scales + (kinds ? b->n_obs : 0));
+    loss_dirty = true;
     nq = b->n_query; nt = b->n_tag; nb = b->n_obs; init_from_map = b->init_from_map != 0;
     max_k = 0;
     for (int q = 0; q < nq; ++q) max_k = std::max(max_k, b->query_start[q + 1] - b->query_start[q]);
@@ -653,9 +772,55 @@ struct arslam_localizer {
     loaded = true;
   }
 
+  // The device's per-observation losses for the next solve: the batch's own or
+  // the default for all; none uploaded (any_loss = false) when every kind is NONE.
+  void refresh_loss() {
+    if (!loss_dirty) return;
+    const std::vector<unsigned char> k =
+        has_obs_loss ? obs_kind : std::vector<unsigned char>((size_t)nb, (unsigned char)loss_kind);
+    any_loss = std::any_of(k.begin(), k.end(), [](unsigned char v) { return v != ARSLAM_LOSS_NONE; });
+    if (any_loss) {
+      const std::vector<double> a = has_obs_loss ? obs_a : std::vector<double>((size_t)nb, loss_a);
+      lk.alloc(nb);
+      la.alloc(nb);
+      hip_check(hipMemcpyAsync(lk.p, k.data(), (size_t)nb, hipMemcpyHostToDevice, stream), "upload");
+      hip_check(hipMemcpyAsync(la.p, a.data(), (size_t)nb * sizeof(double), hipMemcpyHostToDevice, stream), "upload");
+      hip_check(hipStreamSynchronize(stream), "loss upload sync");   // (k, a are locals)
+    }
+    loss_dirty = false;
+  }
+
+  void set_loss(int kind, double a) {
+    check_loss(kind, a);
+    loss_kind = kind;
+    loss_a = a;
+    loss_dirty = true;
+  }
+
+  // s = |r|^2 and w = rho'(s) of every observation at the last solve's poses
+  void observation_terms(double *sq_host, double *w_host) {
+    arslam::api_check(loaded && solved, ARSLAM_E_STATE, "observation_terms needs a completed solve");
+    if (!nb || (!sq_host && !w_host)) return;
+    terms.alloc(2L * nb);
+    hipLaunchKernelGGL(arslam::k_localize_terms, dim3((unsigned)nq), dim3(64), 0, stream, nq, cam.p, qs.p, ot.p,
+                       corners.p, aw.p, pose_out.p, res.p, any_loss ? lk.p : nullptr, any_loss ? la.p : nullptr,
+                       terms.p, terms.p + nb);
+    hip_check(hipGetLastError(), "k_localize_terms launch");
+    if (sq_host)
+      hip_check(hipMemcpyAsync(sq_host, terms.p, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, stream),
+                "download");
+    if (w_host)
+      hip_check(hipMemcpyAsync(w_host, terms.p + nb, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, stream),
+                "download");
+    hip_check(hipStreamSynchronize(stream), "terms sync");
+  }
+
   void solve(double *pose_host, arslam_localize_result *res_host, double *kernel_ms) {
     arslam::api_check(loaded, ARSLAM_E_STATE, "no batch loaded");
+    refresh_loss();
     arslam::LocParams p{};
+    p.lk = any_loss ? lk.p : nullptr;
+    p.la = any_loss ? la.p : nullptr;
     p.nq = nq; p.cam = cam.p; p.tag = tag.p; p.tim = has_tim ? tim.p : nullptr;
     p.qs = qs.p; p.ot = ot.p; p.corners = corners.p; p.pose_in = pose_in.p; p.pose_out = pose_out.p;
     p.res = res.p; p.init_from_map = init_from_map; p.max_k = max_k;
@@ -677,6 +842,7 @@ struct arslam_localizer {
       hip_check(hipMemcpyAsync(res_host, res.p, (size_t)nq * sizeof(arslam_localize_result),
                                hipMemcpyDeviceToHost, stream), "download");
     hip_check(hipStreamSynchronize(stream), "solve sync");
+    solved = true;
     if (kernel_ms) {
       float ms = 0.0f;
       hip_check(hipEventElapsedTime(&ms, ev0, ev1), "elapsed");
@@ -692,10 +858,16 @@ void launch_localize(const LocParams &p, hipStream_t s) {
     hipLaunchKernelGGL(k_tag_corners, dim3((unsigned)((4 * p.nt + 255) / 256)), dim3(256), 0, s, p.nt, p.tag,
                        const_cast<double *>(p.aw));
   const dim3 block(64);
-  if (p.max_k <= 8)   // (cfg5: k = 8) two queries per wave
-    hipLaunchKernelGGL((k_localize<2, 32>), dim3((unsigned)((p.nq + 1) / 2)), block, 0, s, p);
-  else if (p.max_k <= 16) hipLaunchKernelGGL((k_localize<2, 64>), dim3((unsigned)p.nq), block, 0, s, p);
-  else hipLaunchKernelGGL((k_localize<kMaxChunks, 64>), dim3((unsigned)p.nq), block, 0, s, p);
+  if (!p.lk) {   // no observation has a robust loss: the code without one
+    if (p.max_k <= 8)   // (cfg5: k = 8) two queries per wave
+      hipLaunchKernelGGL((k_localize<2, 32, false>), dim3((unsigned)((p.nq + 1) / 2)), block, 0, s, p);
+    else if (p.max_k <= 16) hipLaunchKernelGGL((k_localize<2, 64, false>), dim3((unsigned)p.nq), block, 0, s, p);
+    else hipLaunchKernelGGL((k_localize<kMaxChunks, 64, false>), dim3((unsigned)p.nq), block, 0, s, p);
+    return;
+  }
+  if (p.max_k <= 8) hipLaunchKernelGGL((k_localize<2, 32, true>), dim3((unsigned)((p.nq + 1) / 2)), block, 0, s, p);
+  else if (p.max_k <= 16) hipLaunchKernelGGL((k_localize<2, 64, true>), dim3((unsigned)p.nq), block, 0, s, p);
+  else hipLaunchKernelGGL((k_localize<kMaxChunks, 64, true>), dim3((unsigned)p.nq), block, 0, s, p);
 }
 }  // namespace arslam
 
@@ -743,16 +915,45 @@ int arslam_localizer_solve(arslam_localizer *h, double *pose_out, arslam_localiz
   return loc_guarded([&] { h->solve(pose_out, res, kernel_ms); });
 }
 
-int arslam_localize_many(const arslam_localize_batch *b, const arslam_lm_options *opt,
-                         arslam_localize_result *res) {
+int arslam_localizer_set_loss(arslam_localizer *h, int kind, double a) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return loc_guarded([&] { h->set_loss(kind, a); });
+}
+
+int arslam_localizer_get_loss(const arslam_localizer *h, int *kind, double *a) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  if (kind) *kind = h->loss_kind;
+  if (a) *a = h->loss_a;
+  return ARSLAM_OK;
+}
+
+int arslam_localizer_load_loss(arslam_localizer *h, const arslam_localize_batch *b,
+                               const unsigned char *obs_loss_kind, const double *obs_loss_a) {
+  if (!h || !b) return ARSLAM_E_INVALID_ARG;
+  return loc_guarded([&] { h->load(b, obs_loss_kind, obs_loss_a); });
+}
+
+int arslam_localizer_observation_terms(arslam_localizer *h, double *sq_residual, double *weight) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return loc_guarded([&] { h->observation_terms(sq_residual, weight); });
+}
+
+int arslam_localize_many_loss(const arslam_localize_batch *b, const arslam_lm_options *opt, int kind, double a,
+                              arslam_localize_result *res) {
   if (!b) return ARSLAM_E_INVALID_ARG;
   arslam_localizer *h = nullptr;
   int rc = arslam_localizer_create(&h, opt);
   if (rc) return rc;
-  rc = arslam_localizer_load(h, b);
+  rc = arslam_localizer_set_loss(h, kind, a);
+  if (!rc) rc = arslam_localizer_load(h, b);
   if (!rc) rc = arslam_localizer_solve(h, b->pose, res, nullptr);
   arslam_localizer_destroy(h);
   return rc;
+}
+
+int arslam_localize_many(const arslam_localize_batch *b, const arslam_lm_options *opt,
+                         arslam_localize_result *res) {
+  return arslam_localize_many_loss(b, opt, ARSLAM_LOSS_NONE, 0.0, res);
 }
 
 }  // extern "C"

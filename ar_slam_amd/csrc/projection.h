@@ -232,6 +232,16 @@ __device__ __forceinline__ double wave_reduce(double v, Op op) {
             __longlong_as_double((long long)(((unsigned long long)d[1] << 32) | c[1])));   // halves
 }
 
+// The sum of v over an observation's 8 residual rows, which sit in 8
+// consecutive lanes (lane = 8 q + row): wave_reduce's first three steps, so
+// the 8 lanes end with the same bits.  The 8 lanes are active together.
+__device__ __forceinline__ double obs_sum8(double v) {
+  v += dpp_f64<0xB1>(v);    // lane ^ 1
+  v += dpp_f64<0x4E>(v);    // lane ^ 2
+  v += dpp_f64<0x141>(v);   // row_half_mirror: the other quad of the 8
+  return v;
+}
+
 template <int W = 64>
 __device__ __forceinline__ double wave_sum(double v) {
   return wave_reduce<W>(v, [](double x, double y) { return x + y; });

@@ -3,6 +3,7 @@
 #include "ar_slam_solver.hpp"
 
 #include "yaml_lite.hpp"
+#include "loss.h"
 
 #include <algorithm>
 #include <cmath>
@@ -449,7 +450,7 @@ void ArSlamSolver::localizeMany(unsigned first_loc_cap_idx) {   // :888-901, eac
   b.pose = pose.data();
   b.init_from_map = 1;
   std::vector<arslam_localize_result> res(std::max<size_t>(qcap.size(), 1));
-  check(arslam_localize_many(&b, &options_, res.data()));
+  check(arslam_localize_many_loss(&b, &options_, localize_loss_kind_, localize_loss_a_, res.data()));
   for (size_t q = 0; q < qcap.size(); ++q) {
     Capture &capture = captures_[qcap[q]];
     if (res[q].status == ARSLAM_LOC_SKIPPED) {
@@ -480,6 +481,13 @@ void ArSlamSolver::optimize(const Capture &capture) {   // :1001-1018
 }
 
 int ArSlamSolver::setLoss(int kind, double a) { return arslam_lm_set_loss(problem_, kind, a); }
+
+int ArSlamSolver::setLocalizeLoss(int kind, double a) {
+  if (!loss_valid(kind, a)) return ARSLAM_E_INVALID_ARG;
+  localize_loss_kind_ = kind;
+  localize_loss_a_ = a;
+  return ARSLAM_OK;
+}
 
 void ArSlamSolver::resetProblem() { check(arslam_lm_reset(problem_)); }   // :1021-1025
 

@@ -169,9 +169,13 @@ class ArSlamSolver {
   // The ceres::LossFunction of the residual blocks added from now on (the
   // reference passes nullptr, ar_slam_util.cpp:720-727): arslam_lm_set_loss on
   // the problem, so it holds for solve, solveIncremental and solveCapture.
-  // localizeMany's batched kernel stays without a loss.  Returns ARSLAM_OK or
-  // ARSLAM_E_INVALID_ARG (the loss is then unchanged).
+  // localizeMany's batched kernel takes its own loss, setLocalizeLoss.  Returns
+  // ARSLAM_OK or ARSLAM_E_INVALID_ARG (the loss is then unchanged).
   int setLoss(int kind, double a);
+  // The ceres::LossFunction of every residual block localizeMany adds (the
+  // reference passes nullptr, ar_slam_util.cpp:956-963): localizeMany then
+  // runs through arslam_localize_many_loss.  Same return values as setLoss.
+  int setLocalizeLoss(int kind, double a);
 
   // data-store builders (protected in the reference; public here so a host
   // or test can assemble a problem without ROS messages)
@@ -201,6 +205,8 @@ class ArSlamSolver {
   std::unordered_set<CaptureHandle, CaptureHandleHash> unsolved_captures_;
   std::deque<SolveRecord> solve_log_;   // (records are ~90 KB: no reallocation copies)
   bool verbose_ = false;
+  int localize_loss_kind_ = ARSLAM_LOSS_NONE;   // setLocalizeLoss
+  double localize_loss_a_ = 0.0;
 };
 
 // initialisers (ar_slam_util.cpp:41-128)

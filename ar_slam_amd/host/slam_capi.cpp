@@ -67,6 +67,11 @@ int arslam_slam_set_loss(arslam_slam *h, int kind, double a) {
   return h->s.setLoss(kind, a);
 }
 
+int arslam_slam_set_localize_loss(arslam_slam *h, int kind, double a) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return h->s.setLocalizeLoss(kind, a);
+}
+
 int arslam_slam_load_yaml(arslam_slam *h, const char *path) {
   if (!h || !path) return ARSLAM_E_INVALID_ARG;
   return slam_guarded([&] { h->s.loadYaml(path); });

@@ -56,6 +56,8 @@ EXPORTS = ["arslam_lm_options_init", "arslam_lm_create", "arslam_lm_destroy",
            "arslam_debug_rank_split", "arslam_debug_gather_extend", "arslam_debug_schur_store_table",
            "arslam_localize_many", "arslam_localizer_create", "arslam_localizer_destroy",
            "arslam_localizer_load", "arslam_localizer_solve",
+           "arslam_localizer_set_loss", "arslam_localizer_get_loss", "arslam_localizer_load_loss",
+           "arslam_localizer_observation_terms", "arslam_localize_many_loss", "arslam_slam_set_localize_loss",
            "arslam_slam_create", "arslam_slam_destroy", "arslam_slam_set_verbose", "arslam_slam_load_yaml",
            "arslam_slam_load_yaml_string", "arslam_slam_save_yaml", "arslam_slam_add_detections",
            "arslam_slam_solve", "arslam_slam_solve_incremental", "arslam_slam_localize_many",
@@ -219,6 +221,14 @@ def lib():
         L.arslam_lm_load_soa_loss.argtypes = [C.c_void_p, C.POINTER(SoaProblem), _up, _dp]
         L.arslam_debug_residual_jacobian_loss.argtypes = [C.c_int, _dp, _dp, _dp, _dp, _up, _dp, _dp, _dp, _dp]
         L.arslam_slam_set_loss.argtypes = [C.c_void_p, C.c_int, C.c_double]
+    if hasattr(L, "arslam_localizer_set_loss"):   # (likewise)
+        L.arslam_localizer_set_loss.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        L.arslam_localizer_get_loss.argtypes = [C.c_void_p, _ip, _dp]
+        L.arslam_localizer_load_loss.argtypes = [C.c_void_p, C.POINTER(LocalizeBatchC), _up, _dp]
+        L.arslam_localizer_observation_terms.argtypes = [C.c_void_p, _dp, _dp]
+        L.arslam_localize_many_loss.argtypes = [C.POINTER(LocalizeBatchC), C.POINTER(Options), C.c_int, C.c_double,
+                                                C.POINTER(LocalizeResult)]
+        L.arslam_slam_set_localize_loss.argtypes = [C.c_void_p, C.c_int, C.c_double]
     L.arslam_lm_set_parameter_block_constant.argtypes = [C.c_void_p, _dp]
     L.arslam_lm_set_parameter_block_variable.argtypes = [C.c_void_p, _dp]
     L.arslam_lm_solve.argtypes = [C.c_void_p, C.POINTER(Summary)]
@@ -775,24 +785,63 @@ class _LocArrays:
                                 int(bool(init_from_map)))
 
 
-def localize_many(batch, init_from_map=True, pose=None, **opts):
+def localize_many(batch, init_from_map=True, pose=None, loss=None, **opts):
     """localizeMany on the device (one-shot).  ``batch`` has camera, tag, q_start, obs_tag,
-    corners, tag_in_map (synth.LocalizeBatch).  Returns (pose (Nq,6), results dict of arrays)."""
+    corners, tag_in_map (synth.LocalizeBatch).  loss = (kind, a): every observation's robust loss
+    (LOSS_*, scale); the results' costs are then the robust cost.  Returns (pose (Nq,6), results
+    dict of arrays)."""
     A = _LocArrays(batch, init_from_map, pose)
     res = (LocalizeResult * max(A.s.n_query, 1))()
-    _check(lib().arslam_localize_many(C.byref(A.s), C.byref(make_options(**opts)), res))
+    if loss is None:
+        _check(lib().arslam_localize_many(C.byref(A.s), C.byref(make_options(**opts)), res))
+    else:
+        _check(lib().arslam_localize_many_loss(C.byref(A.s), C.byref(make_options(**opts)), int(loss[0]),
+                                               float(loss[1]), res))
     return A.pose, _loc_results(res[:A.s.n_query])
 
 
 class Localizer:
     """Resident batched localizer: load a batch once, solve it many times."""
 
-    def __init__(self, batch, init_from_map=True, pose=None, **opts):
+    def __init__(self, batch, init_from_map=True, pose=None, loss=None, obs_loss=None, **opts):
+        """loss = (kind, a): the robust loss of every observation (the handle's default loss);
+        obs_loss = (kinds[n_obs], a[n_obs]): one loss per observation of this batch, in observation
+        order, overriding the default."""
         self._h = C.c_void_p()
         _check(lib().arslam_localizer_create(C.byref(self._h), C.byref(make_options(**opts))))
         self.A = _LocArrays(batch, init_from_map, pose)
-        _check(lib().arslam_localizer_load(self._h, C.byref(self.A.s)))
         self.n_query = self.A.s.n_query
+        self.n_obs = self.A.s.n_obs
+        if loss is not None:
+            self.set_loss(*loss)
+        if obs_loss is None:
+            _check(lib().arslam_localizer_load(self._h, C.byref(self.A.s)))
+        else:
+            kinds = np.ascontiguousarray(obs_loss[0], np.uint8).reshape(-1)
+            scales = _f64(obs_loss[1]).reshape(-1)
+            if kinds.shape[0] != self.n_obs or scales.shape[0] != self.n_obs:
+                raise ValueError("obs_loss: one kind and one scale per observation")
+            _check(lib().arslam_localizer_load_loss(self._h, C.byref(self.A.s), kinds.ctypes.data_as(_up),
+                                                    scales.ctypes.data_as(_dp)))
+
+    def set_loss(self, kind, a=0.0):
+        """The default loss (LOSS_*, scale a) of every observation, from the next solve() on; the
+        loaded batch stays loaded.  A batch loaded with obs_loss keeps its own losses."""
+        _check(lib().arslam_localizer_set_loss(self._h, int(kind), float(a)))
+
+    def get_loss(self):
+        """(kind, a) of the default loss."""
+        k, a = C.c_int(0), C.c_double(0.0)
+        _check(lib().arslam_localizer_get_loss(self._h, C.byref(k), C.byref(a)))
+        return k.value, a.value
+
+    def observation_terms(self):
+        """(s, w), each (n_obs,): per observation the plain squared residual s = |r|^2 and the
+        weight w = rho'(s) at the poses the last solve() returned (w = 1 without a loss, near 0 for
+        a rejected detection); -1 for the observations of skipped queries."""
+        s, w = np.zeros(max(self.n_obs, 1)), np.zeros(max(self.n_obs, 1))
+        _check(lib().arslam_localizer_observation_terms(self._h, s.ctypes.data_as(_dp), w.ctypes.data_as(_dp)))
+        return s[:self.n_obs], w[:self.n_obs]
 
     def solve(self, download=True):
         """Returns (pose or None, results or None, kernel_ms)."""
@@ -843,8 +892,13 @@ class SlamSolver:
 
     def set_loss(self, kind, a=0.0):
         """The robust loss (LOSS_*, scale a) of every residual block added from now on: solve,
-        solve_incremental and the solveCapture calls inside them.  localize_many has none."""
+        solve_incremental and the solveCapture calls inside them.  localize_many has its own:
+        set_localize_loss."""
         _check(lib().arslam_slam_set_loss(self._h, int(kind), C.c_double(float(a))))
+
+    def set_localize_loss(self, kind, a=0.0):
+        """The robust loss (LOSS_*, scale a) of every residual block localize_many adds."""
+        _check(lib().arslam_slam_set_localize_loss(self._h, int(kind), C.c_double(float(a))))
 
     def load_yaml(self, path):
         _check(lib().arslam_slam_load_yaml(self._h, str(path).encode()))

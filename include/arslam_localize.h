@@ -72,6 +72,41 @@ int arslam_localizer_load(arslam_localizer *h, const arslam_localize_batch *b);
 int arslam_localizer_solve(arslam_localizer *h, double *pose_out, arslam_localize_result *res,
                            double *kernel_ms);
 
+/* ---- robust losses (arslam_lm.h ARSLAM_LOSS_*: Huber, SoftLOne, Cauchy) ----
+ * One loss per observation (residual block), with the LM solver's and Ceres'
+ * semantics (loss_function.cc, corrector.cc) -- what passing
+ * `new ceres::CauchyLoss(a)` to AddResidualBlock at ar_slam_util.cpp:956-963
+ * would do: s = |r|^2 over the block's 8 residuals, rows and Jacobian rows
+ * times sqrt(rho'(s)), cost 1/2 sum rho(s); the Jacobi scaling, the LM
+ * diagonal, the model cost change, the step quality and every termination
+ * test work on the corrected quantities, and initial_cost / final_cost of
+ * arslam_localize_result are the robust cost.  A batch whose observations
+ * are all ARSLAM_LOSS_NONE runs the code without a loss (the same bits).
+ *
+ * An invalid kind, or a scale that is not finite and > 0 for a kind other
+ * than NONE, returns ARSLAM_E_INVALID_ARG before any device call and leaves
+ * the handle as it was. */
+
+/* The default loss of every observation (initially NONE).  Takes effect at
+ * the next solve; the loaded batch stays loaded. */
+int arslam_localizer_set_loss(arslam_localizer *h, int kind, double a);
+int arslam_localizer_get_loss(const arslam_localizer *h, int *kind, double *a);
+/* arslam_localizer_load with the batch's own losses, obs_loss_kind and
+ * obs_loss_a [n_obs] in observation order: they override the default for this
+ * batch.  Both NULL = the default (arslam_localizer_load); exactly one NULL
+ * is rejected. */
+int arslam_localizer_load_loss(arslam_localizer *h, const arslam_localize_batch *b,
+                               const unsigned char *obs_loss_kind, const double *obs_loss_a);
+/* What the loss did, per observation, at the poses the last solve returned:
+ * sq_residual = the plain s = |r|^2, weight = rho'(s) (1 without a loss; a
+ * rejected detection shows a weight near 0).  Both -1 for the observations of
+ * a skipped query.  [n_obs] each, either nullable.  ARSLAM_E_STATE before a
+ * completed solve of the loaded batch. */
+int arslam_localizer_observation_terms(arslam_localizer *h, double *sq_residual, double *weight);
+/* arslam_localize_many with one loss for every observation. */
+int arslam_localize_many_loss(const arslam_localize_batch *b, const arslam_lm_options *opt,
+                              int kind, double a, arslam_localize_result *res);
+
 #ifdef __cplusplus
 }
 #endif

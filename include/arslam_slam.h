@@ -39,9 +39,16 @@ int arslam_slam_set_verbose(arslam_slam *h, int verbose);
  * AddResidualBlock (ar_slam_util.cpp:720-727); this is the mirror of passing
  * `new ceres::HuberLoss(a)` there.  It applies to solve, solveIncremental and
  * the solveCapture calls inside them.  localizeMany (the batched device
- * localizer, arslam_localize.h) stays without a loss.  An invalid kind or
- * scale returns ARSLAM_E_INVALID_ARG and leaves the loss unchanged. */
+ * localizer, arslam_localize.h) takes its own loss,
+ * arslam_slam_set_localize_loss.  An invalid kind or scale returns
+ * ARSLAM_E_INVALID_ARG and leaves the loss unchanged. */
 int arslam_slam_set_loss(arslam_slam *h, int kind, double a);
+/* The robust loss of every residual block localizeMany adds from now on --
+ * the mirror of passing `new ceres::CauchyLoss(a)` to AddResidualBlock at
+ * ar_slam_util.cpp:956-963; localizeMany then runs through
+ * arslam_localize_many_loss.  Initially NONE.  An invalid kind or scale
+ * returns ARSLAM_E_INVALID_ARG and leaves the loss unchanged. */
+int arslam_slam_set_localize_loss(arslam_slam *h, int kind, double a);
 
 int arslam_slam_load_yaml(arslam_slam *h, const char *path);
 int arslam_slam_load_yaml_string(arslam_slam *h, const char *text);
