@@ -631,9 +631,175 @@ __global__ __launch_bounds__(64) void k_localize_terms(int nq, const double *__r
   w_out[o] = w;
 }
 
+// ---- per-query pose covariance (arslam_localizer_covariance) ----
+// k_localize's arguments (the batch, the last solve's poses, results, losses
+// and aw) and the three outputs.
+struct LocCovParams {
+  LocParams p;
+  double *cov;       // [nq*36]
+  int *cov_status;   // [nq]
+  double *min_pivot; // [nq]
+};
+
+constexpr double kCovMinPivot = 1e-14;   // a squared pivot of the equilibrated Cholesky below this: rank deficient
+
+// Ceres' Covariance with apply_loss_function = true for the one free block of
+// a query: C = (J~'J~)^-1 at the pose the last solve returned, J~ the rows as
+// the solve corrects them (no LM diagonal, no Jacobi scaling).  The launch
+// geometry, the staging of rc / lka and evaluate_jacobian are k_localize's, so
+// the sums are the solve's own code; then, from J~'J~ in LDS, every lane
+// equilibrates (c_j = H_jj^-1/2, Hs = c H c with a unit diagonal) and factors
+// Hs = L L' redundantly (the same 6x6 Cholesky k_localize runs per iteration;
+// the pivots are the same bits on every lane, so the status is uniform), lane
+// j < 6 of the query solves column j of Hs^-1 by the two substitutions and
+// leaves its lower part (rows i >= j) scaled by c_i c_j in LDS, and lane
+// t < 36 stores C[t / 6][t % 6] from entry (max, min): one triangle, mirrored
+// (C[i][j] and C[j][i] the same bits), the query's 36 values one contiguous
+// 288-byte run.  A skipped or unavailable query leaves its half of the wave
+// before the evaluation, as in k_localize.  The staging loop is k_localize's,
+// repeated: moved into a function shared by both kernels it changed
+// k_localize's instruction schedule, and the solve's ISA is held fixed here.
+template <int NCH, int LPQ, bool kLoss>
+__global__ __launch_bounds__(64, 2) void k_localize_cov(LocCovParams cp) {
+  const LocParams &p = cp.p;
+  const int lane = threadIdx.x & (LPQ - 1);
+  const int q = blockIdx.x * (64 / LPQ) + threadIdx.x / LPQ;
+  __shared__ __attribute__((aligned(16))) double red_all[(64 / LPQ) * (28 * (LPQ + 2) + 28)];
+  double *red = red_all + (threadIdx.x / LPQ) * (28 * (LPQ + 2) + 28);
+  __shared__ __attribute__((aligned(16))) double rc_all[(64 / LPQ) * NCH * LPQ * 4];
+  double *rc = rc_all + (threadIdx.x / LPQ) * NCH * LPQ * 4;
+  constexpr int kObsPerQuery = NCH * LPQ / 8;
+  __shared__ LossKA lka_all[kLoss ? (64 / LPQ) * kObsPerQuery : 1];
+  LossKA *lka = lka_all + (kLoss ? (threadIdx.x / LPQ) * kObsPerQuery : 0);
+  if (q >= p.nq) return;
+  const int o0 = p.qs[q], k = p.qs[q + 1] - o0;
+  const int status = p.res[q].status, rule = p.res[q].rule;
+  int cst = ARSLAM_COV_OK;
+  double mp = -1.0;
+  bool have = !(k == 0 || status == ARSLAM_LOC_SKIPPED ||
+                (status == ARSLAM_FAILURE && rule == ARSLAM_RULE_EVAL_FAILED));
+  if (have) {
+    const int nrow = 8 * k;
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+      const int R = lane + LPQ * ch;
+      if (R < nrow) {
+        const int o = o0 + (R >> 3), row = R & 7;
+        const double *a = p.aw + 4L * (4 * p.ot[o] + (row >> 1));
+        typedef double d2 __attribute__((ext_vector_type(2)));
+        reinterpret_cast<d2 *>(rc + 4 * R)[0] = d2{a[0], a[1]};
+        reinterpret_cast<d2 *>(rc + 4 * R)[1] = d2{a[2], p.corners[8L * o + row]};
+        if (kLoss && row == 0)
+          lka[R >> 3] = LossKA{(double)p.lk[o], p.la[o]};
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    double x[6], cost;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) x[j] = p.pose_out[6L * q + j];
+    have = evaluate_jacobian<NCH, LPQ, kLoss>(p, rc, lka, nrow, x, lane, cost, red) && isfinite(cost);
+  }
+  if (!have) {
+    cst = ARSLAM_COV_UNAVAILABLE;
+  } else {
+    const double *H = red + sums_off<LPQ>() + 7;
+    // equilibrate: c_j = 1 / sqrt(H_jj), Hs = c H c with its diagonal exactly 1
+    double c[6], A[21];
+    bool diag_ok = true;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const double h = H[HD(j)];
+      diag_ok = diag_ok && isfinite(h) && h > 0.0;
+      c[j] = 1.0 / sqrt(h);
+    }
+    {
+      int e = 0;
+#pragma unroll
+      for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = a; b < 6; ++b) {
+          A[e] = a == b ? 1.0 : c[a] * H[e] * c[b];
+          ++e;
+        }
+    }
+#define UP(a, b) ((a) * 6 - ((a) * ((a) - 1)) / 2 + ((b) - (a)))
+#define L_(i, j) A[UP(j, i)]
+    // Hs = L L' in place (L[i][j], i > j, overwrites A[UP(j, i)]); the first
+    // squared pivot that is not >= kCovMinPivot (a negative or NaN one
+    // included) ends the query as rank deficient
+    double il[6];
+    bool piv_ok = true;
+    mp = 1.0;
+    double bad_pivot = -1.0;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      double s = L_(j, j);
+#pragma unroll
+      for (int m = 0; m < j; ++m) s -= L_(j, m) * L_(j, m);
+      if (piv_ok && !(s >= kCovMinPivot)) { piv_ok = false; bad_pivot = s; }
+      mp = fmin(mp, s);
+      il[j] = 1.0 / sqrt(s);
+#pragma unroll
+      for (int i = j + 1; i < 6; ++i) {
+        double t = L_(i, j);
+#pragma unroll
+        for (int m = 0; m < j; ++m) t -= L_(i, m) * L_(j, m);
+        L_(i, j) = t * il[j];
+      }
+    }
+    if (!diag_ok) { cst = ARSLAM_COV_RANK_DEFICIENT; mp = -1.0; }
+    else if (!piv_ok) { cst = ARSLAM_COV_RANK_DEFICIENT; mp = bad_pivot; }
+    else {
+      // lane j < 6: column j of Hs^-1, L z = e_j then L' y = z; rows i >= j go
+      // to stage[6 i + j] (= the lower triangle of C), scaled by c_i c_j.
+      // stage = the partials of query_sums28, dead since its sums were formed.
+      double *stage = red;
+      if (lane < 6) {
+        double z[6], y[6], cj = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+          double t = i == lane ? 1.0 : 0.0;
+          cj = i == lane ? c[i] : cj;
+#pragma unroll
+          for (int m = 0; m < i; ++m) t -= L_(i, m) * z[m];
+          z[i] = t * il[i];
+        }
+#pragma unroll
+        for (int i = 5; i >= 0; --i) {
+          double t = z[i];
+#pragma unroll
+          for (int m = i + 1; m < 6; ++m) t -= L_(m, i) * y[m];
+          y[i] = t * il[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+          if (i >= lane) stage[6 * i + lane] = c[i] * y[i] * cj;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      for (int t = lane; t < 36; t += LPQ) {
+        const int i = t / 6, j = t - 6 * i;
+        cp.cov[36L * q + t] = stage[6 * (i > j ? i : j) + (i > j ? j : i)];
+      }
+    }
+#undef L_
+#undef UP
+  }
+  if (cst != ARSLAM_COV_OK)
+    for (int t = lane; t < 36; t += LPQ) cp.cov[36L * q + t] = -1.0;
+  if (lane == 0) {
+    cp.cov_status[q] = cst;
+    cp.min_pivot[q] = mp;
+  }
+}
+
 }  // namespace
 
 void launch_localize(const LocParams &p, hipStream_t s);
+void launch_localize_cov(const LocCovParams &cp, hipStream_t s);
 
 }  // namespace arslam
 
@@ -693,6 +859,8 @@ struct arslam_localizer {
   bool has_obs_loss = false, loss_dirty = true, any_loss = false, solved = false;
   DBuf<unsigned char> lk;
   DBuf<double> la, terms;
+  DBuf<double> cov, cov_piv;   // covariance(): allocated by its first call
+  DBuf<int> cov_st;
 
   ~arslam_localizer() {
     if (ev0) (void)hipEventDestroy(ev0);
@@ -815,9 +983,8 @@ struct arslam_localizer {
     hip_check(hipStreamSynchronize(stream), "terms sync");
   }
 
-  void solve(double *pose_host, arslam_localize_result *res_host, double *kernel_ms) {
-    arslam::api_check(loaded, ARSLAM_E_STATE, "no batch loaded");
-    refresh_loss();
+  // k_localize's arguments: the loaded batch, the options and the resident losses
+  arslam::LocParams params() const {
     arslam::LocParams p{};
     p.lk = any_loss ? lk.p : nullptr;
     p.la = any_loss ? la.p : nullptr;
@@ -831,6 +998,47 @@ struct arslam_localizer {
     p.r0 = opt.initial_trust_region_radius; p.rmax = opt.max_trust_region_radius;
     p.rmin = opt.min_trust_region_radius; p.min_rel = opt.min_relative_decrease;
     p.dmin = opt.min_lm_diagonal; p.dmax = opt.max_lm_diagonal;
+    return p;
+  }
+
+  // cov (J~'J~)^-1 [nq*36], its status and min_pivot [nq] at the last solve's
+  // poses, under the losses that solve used (lk / la as they are resident);
+  // *kernel_ms (nullable): the device time of the covariance kernel
+  void covariance(double *cov_host, int *status_host, double *pivot_host, double *kernel_ms = nullptr) {
+    arslam::api_check(loaded && solved, ARSLAM_E_STATE, "covariance needs a completed solve");
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (!nq || (!cov_host && !status_host && !pivot_host)) return;
+    if (cov.n < 36 * (size_t)nq) {   // sized on first use
+      cov.alloc(36 * (size_t)nq);
+      cov_piv.alloc(nq);
+      cov_st.alloc(nq);
+    }
+    arslam::LocCovParams cp{params(), cov.p, cov_st.p, cov_piv.p};
+    hip_check(hipEventRecord(ev0, stream), "event");
+    arslam::launch_localize_cov(cp, stream);
+    hip_check(hipGetLastError(), "k_localize_cov launch");
+    hip_check(hipEventRecord(ev1, stream), "event");
+    if (cov_host)
+      hip_check(hipMemcpyAsync(cov_host, cov.p, 36 * (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, stream),
+                "download");
+    if (status_host)
+      hip_check(hipMemcpyAsync(status_host, cov_st.p, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost, stream),
+                "download");
+    if (pivot_host)
+      hip_check(hipMemcpyAsync(pivot_host, cov_piv.p, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, stream),
+                "download");
+    hip_check(hipStreamSynchronize(stream), "covariance sync");
+    if (kernel_ms) {
+      float ms = 0.0f;
+      hip_check(hipEventElapsedTime(&ms, ev0, ev1), "elapsed");
+      *kernel_ms = ms;
+    }
+  }
+
+  void solve(double *pose_host, arslam_localize_result *res_host, double *kernel_ms) {
+    arslam::api_check(loaded, ARSLAM_E_STATE, "no batch loaded");
+    refresh_loss();
+    const arslam::LocParams p = params();
     hip_check(hipEventRecord(ev0, stream), "event");
     arslam::launch_localize(p, stream);
     hip_check(hipGetLastError(), "k_localize launch");
@@ -868,6 +1076,25 @@ void launch_localize(const LocParams &p, hipStream_t s) {
   if (p.max_k <= 8) hipLaunchKernelGGL((k_localize<2, 32, true>), dim3((unsigned)((p.nq + 1) / 2)), block, 0, s, p);
   else if (p.max_k <= 16) hipLaunchKernelGGL((k_localize<2, 64, true>), dim3((unsigned)p.nq), block, 0, s, p);
   else hipLaunchKernelGGL((k_localize<kMaxChunks, 64, true>), dim3((unsigned)p.nq), block, 0, s, p);
+}
+
+// k_localize's geometry and instance choice (by max_k and by "any loss"), on
+// the poses, results, losses and aw the last solve left on the device
+void launch_localize_cov(const LocCovParams &cp, hipStream_t s) {
+  const LocParams &p = cp.p;
+  if (p.nq == 0) return;
+  const dim3 block(64);
+  if (!p.lk) {
+    if (p.max_k <= 8)
+      hipLaunchKernelGGL((k_localize_cov<2, 32, false>), dim3((unsigned)((p.nq + 1) / 2)), block, 0, s, cp);
+    else if (p.max_k <= 16) hipLaunchKernelGGL((k_localize_cov<2, 64, false>), dim3((unsigned)p.nq), block, 0, s, cp);
+    else hipLaunchKernelGGL((k_localize_cov<kMaxChunks, 64, false>), dim3((unsigned)p.nq), block, 0, s, cp);
+    return;
+  }
+  if (p.max_k <= 8)
+    hipLaunchKernelGGL((k_localize_cov<2, 32, true>), dim3((unsigned)((p.nq + 1) / 2)), block, 0, s, cp);
+  else if (p.max_k <= 16) hipLaunchKernelGGL((k_localize_cov<2, 64, true>), dim3((unsigned)p.nq), block, 0, s, cp);
+  else hipLaunchKernelGGL((k_localize_cov<kMaxChunks, 64, true>), dim3((unsigned)p.nq), block, 0, s, cp);
 }
 }  // namespace arslam
 
@@ -938,8 +1165,19 @@ int arslam_localizer_observation_terms(arslam_localizer *h, double *sq_residual,
   return loc_guarded([&] { h->observation_terms(sq_residual, weight); });
 }
 
-int arslam_localize_many_loss(const arslam_localize_batch *b, const arslam_lm_options *opt, int kind, double a,
-                              arslam_localize_result *res) {
+int arslam_localizer_covariance(arslam_localizer *h, double *cov, int *cov_status, double *min_pivot) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return loc_guarded([&] { h->covariance(cov, cov_status, min_pivot); });
+}
+
+int arslam_localizer_covariance_timed(arslam_localizer *h, double *cov, int *cov_status, double *min_pivot,
+                                      double *kernel_ms) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return loc_guarded([&] { h->covariance(cov, cov_status, min_pivot, kernel_ms); });
+}
+
+int arslam_localize_many_cov(const arslam_localize_batch *b, const arslam_lm_options *opt, int kind, double a,
+                             arslam_localize_result *res, double *cov, int *cov_status) {
   if (!b) return ARSLAM_E_INVALID_ARG;
   arslam_localizer *h = nullptr;
   int rc = arslam_localizer_create(&h, opt);
@@ -947,8 +1185,14 @@ int arslam_localize_many_loss(const arslam_localize_batch *b, const arslam_lm_op
   rc = arslam_localizer_set_loss(h, kind, a);
   if (!rc) rc = arslam_localizer_load(h, b);
   if (!rc) rc = arslam_localizer_solve(h, b->pose, res, nullptr);
+  if (!rc && (cov || cov_status)) rc = arslam_localizer_covariance(h, cov, cov_status, nullptr);
   arslam_localizer_destroy(h);
   return rc;
+}
+
+int arslam_localize_many_loss(const arslam_localize_batch *b, const arslam_lm_options *opt, int kind, double a,
+                              arslam_localize_result *res) {
+  return arslam_localize_many_cov(b, opt, kind, a, res, nullptr, nullptr);
 }
 
 int arslam_localize_many(const arslam_localize_batch *b, const arslam_lm_options *opt,

@@ -145,7 +145,10 @@ ArSlamSolver::ArSlamSolver(const arslam_lm_options *opt) {
   check(arslam_lm_create(&problem_, &options_));
 }
 
-ArSlamSolver::~ArSlamSolver() { arslam_lm_destroy(problem_); }
+ArSlamSolver::~ArSlamSolver() {
+  arslam_localizer_destroy(localizer_);
+  arslam_lm_destroy(problem_);
+}
 
 Capture &ArSlamSolver::addCapture(const std::string &cap_uid, const std::string &fn) {   // :419-428
   const unsigned idx = (unsigned)captures_.size();
@@ -415,6 +418,7 @@ void ArSlamSolver::localizeMany(unsigned first_loc_cap_idx) {   // :888-901, eac
   // Every localizeOne resets the problem and holds the tags and the camera
   // constant, so the queries are independent: they run as one device batch.
   const unsigned n = (unsigned)captures_.size();
+  dropLocalizer();
   if (first_loc_cap_idx >= n) return;
   std::vector<unsigned char> in_map(arucos_.size(), 0);
   for (const Aruco &a : arucos_)
@@ -450,7 +454,15 @@ void ArSlamSolver::localizeMany(unsigned first_loc_cap_idx) {   // :888-901, eac
   b.pose = pose.data();
   b.init_from_map = 1;
   std::vector<arslam_localize_result> res(std::max<size_t>(qcap.size(), 1));
-  check(arslam_localize_many_loss(&b, &options_, localize_loss_kind_, localize_loss_a_, res.data()));
+  // arslam_localize_many_loss's own sequence, with the handle kept: the batch,
+  // its poses and its losses stay on the device, so localizeCovariance can
+  // evaluate there on the first request (nothing more runs when nobody asks)
+  check(arslam_localizer_create(&localizer_, &options_));
+  check(arslam_localizer_set_loss(localizer_, localize_loss_kind_, localize_loss_a_));
+  check(arslam_localizer_load(localizer_, &b));
+  check(arslam_localizer_solve(localizer_, pose.data(), res.data(), nullptr));
+  loc_first_ = first_loc_cap_idx;
+  loc_count_ = (unsigned)qcap.size();
   for (size_t q = 0; q < qcap.size(); ++q) {
     Capture &capture = captures_[qcap[q]];
     if (res[q].status == ARSLAM_LOC_SKIPPED) {
@@ -460,6 +472,30 @@ void ArSlamSolver::localizeMany(unsigned first_loc_cap_idx) {   // :888-901, eac
     for (BlockHandle bh : capture.blocks) at(bh).added = true;
     std::copy(pose.begin() + 6 * q, pose.begin() + 6 * q + 6, capture.inv_pose.params.begin());
   }
+}
+
+void ArSlamSolver::dropLocalizer() {
+  arslam_localizer_destroy(localizer_);
+  localizer_ = nullptr;
+  loc_count_ = 0;
+  loc_cov_.clear();
+  loc_cov_status_.clear();
+}
+
+int ArSlamSolver::localizeCovariance(unsigned cap_idx, double cov[36], int *cov_status) {
+  if (!localizer_ || cap_idx < loc_first_ || cap_idx - loc_first_ >= loc_count_) return ARSLAM_E_STATE;
+  if (loc_cov_status_.empty()) {   // the first request since that localizeMany
+    std::vector<double> c(36 * (size_t)loc_count_);
+    std::vector<int> st(loc_count_);
+    const int rc = arslam_localizer_covariance(localizer_, c.data(), st.data(), nullptr);
+    if (rc < 0) return rc;
+    loc_cov_.swap(c);
+    loc_cov_status_.swap(st);
+  }
+  const size_t q = cap_idx - loc_first_;
+  if (cov) std::copy(loc_cov_.begin() + 36 * q, loc_cov_.begin() + 36 * q + 36, cov);
+  if (cov_status) *cov_status = loc_cov_status_[q];
+  return ARSLAM_OK;
 }
 
 void ArSlamSolver::optimize(const Capture &capture) {   // :1001-1018

@@ -176,6 +176,14 @@ class ArSlamSolver {
   // reference passes nullptr, ar_slam_util.cpp:956-963): localizeMany then
   // runs through arslam_localize_many_loss.  Same return values as setLoss.
   int setLocalizeLoss(int kind, double a);
+  // The 6x6 covariance (arslam_localizer_covariance: row-major, [t_c, w_c],
+  // unit-variance residuals) and its ARSLAM_COV_* status of a capture the last
+  // localizeMany localized, at the pose it was given -- ceres::Covariance on
+  // the capture block after localizeOne's Solve.  localizeMany keeps its
+  // batch on the device; the covariances of all its captures are computed by
+  // the first request after it.  Returns ARSLAM_OK, or ARSLAM_E_STATE for a
+  // capture the last localizeMany did not cover.  cov and cov_status nullable.
+  int localizeCovariance(unsigned cap_idx, double cov[36], int *cov_status);
 
   // data-store builders (protected in the reference; public here so a host
   // or test can assemble a problem without ROS messages)
@@ -207,6 +215,13 @@ class ArSlamSolver {
   bool verbose_ = false;
   int localize_loss_kind_ = ARSLAM_LOSS_NONE;   // setLocalizeLoss
   double localize_loss_a_ = 0.0;
+  // the last localizeMany: its resident batch, the captures it covered
+  // (loc_first_ + q is query q) and their covariances once asked for
+  void dropLocalizer();
+  arslam_localizer *localizer_ = nullptr;
+  unsigned loc_first_ = 0, loc_count_ = 0;
+  std::vector<double> loc_cov_;
+  std::vector<int> loc_cov_status_;
 };
 
 // initialisers (ar_slam_util.cpp:41-128)

@@ -128,6 +128,15 @@ int arslam_slam_localize_many(arslam_slam *h, int first) {
   return slam_guarded([&] { h->s.localizeMany((unsigned)first); });
 }
 
+int arslam_slam_localize_covariance(arslam_slam *h, int cap_idx, double cov[36], int *cov_status) {
+  if (!h || cap_idx < 0) return ARSLAM_E_INVALID_ARG;
+  int rc = ARSLAM_OK;
+  const int g = slam_guarded([&] { rc = h->s.localizeCovariance((unsigned)cap_idx, cov, cov_status); });
+  if (!g && rc == ARSLAM_E_STATE)
+    arslam::set_last_error("localize_covariance: the last localize_many did not cover this capture");
+  return g ? g : rc;
+}
+
 int arslam_slam_num_captures(const arslam_slam *h) { return h ? (int)h->s.numCaptures() : 0; }
 int arslam_slam_num_arucos(const arslam_slam *h) { return h ? (int)h->s.numArucos() : 0; }
 int arslam_slam_num_blocks(const arslam_slam *h) { return h ? (int)h->s.numBlocks() : 0; }

@@ -58,6 +58,8 @@ EXPORTS = ["arslam_lm_options_init", "arslam_lm_create", "arslam_lm_destroy",
            "arslam_localizer_load", "arslam_localizer_solve",
            "arslam_localizer_set_loss", "arslam_localizer_get_loss", "arslam_localizer_load_loss",
            "arslam_localizer_observation_terms", "arslam_localize_many_loss", "arslam_slam_set_localize_loss",
+           "arslam_localizer_covariance", "arslam_localizer_covariance_timed", "arslam_localize_many_cov",
+           "arslam_slam_localize_covariance",
            "arslam_slam_create", "arslam_slam_destroy", "arslam_slam_set_verbose", "arslam_slam_load_yaml",
            "arslam_slam_load_yaml_string", "arslam_slam_save_yaml", "arslam_slam_add_detections",
            "arslam_slam_solve", "arslam_slam_solve_incremental", "arslam_slam_localize_many",
@@ -229,6 +231,12 @@ def lib():
         L.arslam_localize_many_loss.argtypes = [C.POINTER(LocalizeBatchC), C.POINTER(Options), C.c_int, C.c_double,
                                                 C.POINTER(LocalizeResult)]
         L.arslam_slam_set_localize_loss.argtypes = [C.c_void_p, C.c_int, C.c_double]
+    if hasattr(L, "arslam_localizer_covariance"):   # (likewise)
+        L.arslam_localizer_covariance.argtypes = [C.c_void_p, _dp, _ip, _dp]
+        L.arslam_localizer_covariance_timed.argtypes = [C.c_void_p, _dp, _ip, _dp, _dp]
+        L.arslam_localize_many_cov.argtypes = [C.POINTER(LocalizeBatchC), C.POINTER(Options), C.c_int, C.c_double,
+                                               C.POINTER(LocalizeResult), _dp, _ip]
+        L.arslam_slam_localize_covariance.argtypes = [C.c_void_p, C.c_int, _dp, _ip]
     L.arslam_lm_set_parameter_block_constant.argtypes = [C.c_void_p, _dp]
     L.arslam_lm_set_parameter_block_variable.argtypes = [C.c_void_p, _dp]
     L.arslam_lm_solve.argtypes = [C.c_void_p, C.POINTER(Summary)]
@@ -745,6 +753,7 @@ def debug_mixed_groups(camera, cap, tag, obs_cap, obs_tag, corners=None, camera_
 
 # ---- batched localize (include/arslam_localize.h) ----
 LOC_SKIPPED = -1
+COV_OK, COV_UNAVAILABLE, COV_RANK_DEFICIENT = 0, 1, 2   # arslam_localize.h ARSLAM_COV_*
 
 
 class LocalizeBatchC(C.Structure):
@@ -785,13 +794,21 @@ class _LocArrays:
                                 int(bool(init_from_map)))
 
 
-def localize_many(batch, init_from_map=True, pose=None, loss=None, **opts):
+def localize_many(batch, init_from_map=True, pose=None, loss=None, covariance=False, **opts):
     """localizeMany on the device (one-shot).  ``batch`` has camera, tag, q_start, obs_tag,
     corners, tag_in_map (synth.LocalizeBatch).  loss = (kind, a): every observation's robust loss
     (LOSS_*, scale); the results' costs are then the robust cost.  Returns (pose (Nq,6), results
-    dict of arrays)."""
+    dict of arrays); with covariance=True also cov (Nq, 6, 6) and its status (Nq,), COV_*
+    (Localizer.covariance)."""
     A = _LocArrays(batch, init_from_map, pose)
     res = (LocalizeResult * max(A.s.n_query, 1))()
+    if covariance:
+        nq = A.s.n_query
+        cov, st = np.zeros((max(nq, 1), 6, 6)), np.zeros(max(nq, 1), np.int32)
+        kind, a = (LOSS_NONE, 0.0) if loss is None else loss
+        _check(lib().arslam_localize_many_cov(C.byref(A.s), C.byref(make_options(**opts)), int(kind), float(a), res,
+                                              cov.ctypes.data_as(_dp), st.ctypes.data_as(_ip)))
+        return A.pose, _loc_results(res[:nq]), cov[:nq], st[:nq]
     if loss is None:
         _check(lib().arslam_localize_many(C.byref(A.s), C.byref(make_options(**opts)), res))
     else:
@@ -842,6 +859,24 @@ class Localizer:
         s, w = np.zeros(max(self.n_obs, 1)), np.zeros(max(self.n_obs, 1))
         _check(lib().arslam_localizer_observation_terms(self._h, s.ctypes.data_as(_dp), w.ctypes.data_as(_dp)))
         return s[:self.n_obs], w[:self.n_obs]
+
+    def covariance(self, timed=False):
+        """(cov (n_query, 6, 6), status (n_query,), min_pivot (n_query,)): per query the inverse
+        of J~'J~ at the pose the last solve() returned, rows corrected by the loss as in the solve
+        (ceres::Covariance with apply_loss_function), parameters [t_c, w_c], for unit-variance
+        residuals (multiply by the pixel noise's sigma^2); status COV_OK, COV_UNAVAILABLE (skipped
+        or failed evaluation) or COV_RANK_DEFICIENT, the last two with cov = -1; min_pivot the
+        smallest squared pivot of the equilibrated Cholesky.  timed=True appends the kernel's
+        device time in ms."""
+        nq = self.n_query
+        cov, st, mp = np.zeros((max(nq, 1), 6, 6)), np.zeros(max(nq, 1), np.int32), np.zeros(max(nq, 1))
+        ms = C.c_double(0.0)
+        args = (self._h, cov.ctypes.data_as(_dp), st.ctypes.data_as(_ip), mp.ctypes.data_as(_dp))
+        if timed:
+            _check(lib().arslam_localizer_covariance_timed(*args, C.byref(ms)))
+            return cov[:nq], st[:nq], mp[:nq], ms.value
+        _check(lib().arslam_localizer_covariance(*args))
+        return cov[:nq], st[:nq], mp[:nq]
 
     def solve(self, download=True):
         """Returns (pose or None, results or None, kernel_ms)."""
@@ -930,6 +965,13 @@ class SlamSolver:
 
     def localize_many(self, first_loc_cap_idx):
         _check(lib().arslam_slam_localize_many(self._h, C.c_int(first_loc_cap_idx)))
+
+    def localize_covariance(self, cap_idx):
+        """(cov (6, 6), status COV_*) of a capture the last localize_many localized
+        (Localizer.covariance); LMError -7 (STATE) for any other capture."""
+        cov, st = np.zeros((6, 6)), C.c_int(-1)
+        _check(lib().arslam_slam_localize_covariance(self._h, int(cap_idx), cov.ctypes.data_as(_dp), C.byref(st)))
+        return cov, st.value
 
     @property
     def num_captures(self):

@@ -107,6 +107,52 @@ int arslam_localizer_observation_terms(arslam_localizer *h, double *sq_residual,
 int arslam_localize_many_loss(const arslam_localize_batch *b, const arslam_lm_options *opt,
                               int kind, double a, arslam_localize_result *res);
 
+/* ---- per-query pose covariance ----
+ * What ceres::Covariance::Compute on the capture block after Solve would give
+ * (Covariance::Options::apply_loss_function = true), for every query of the
+ * batch at once.  At the pose the last solve returned, H = J~'J~ over the
+ * query's 8k rows and its 6 parameters [t_c, w_c], the Jacobian rows corrected
+ * by sqrt(rho'(s)) exactly as the solve corrects them (no LM diagonal, no
+ * Jacobi scaling).  cov = H^-1, row-major 6x6 in the parameter order of
+ * `pose`.  A query has no gauge freedom (tags and camera are constant), so
+ * the inverse is well defined.
+ *   - It assumes unit-variance residuals: with pixel noise sigma, multiply by
+ *     sigma^2.
+ *   - The camera centre in the world is -t_c, so the top-left 3x3 block is
+ *     the covariance of its position.
+ *   - The inverse is computed from the equilibrated matrix: c_j = 1/sqrt(H_jj),
+ *     Hs = c H c (unit diagonal), Cholesky Hs = L L', C = c (L^-T L^-1) c.
+ *     min_pivot = min_j L_jj^2, a scale-free number in (0, 1].
+ *   - A query is rank deficient when some H_jj is not finite and > 0 or some
+ *     squared pivot is not >= 1e-14 (a negative or NaN pivot included).  This
+ *     stands where Ceres tests singular values against
+ *     min_reciprocal_condition_number = 1e-14; it is NOT the same number (a
+ *     pivot of the equilibrated Cholesky, not a ratio of singular values).
+ *   - C[i][j] and C[j][i] are the same bits.
+ *   - NO_CONVERGENCE and MIN_RADIUS queries get a covariance like any other:
+ *     the linearization at the returned pose. */
+#define ARSLAM_COV_OK 0
+#define ARSLAM_COV_UNAVAILABLE 1     /* the query was skipped, or its status is FAILURE with rule
+                                        EVAL_FAILED, or the evaluation at the returned pose is not finite */
+#define ARSLAM_COV_RANK_DEFICIENT 2
+/* cov [n_query*36], cov_status [n_query] (ARSLAM_COV_*), min_pivot [n_query];
+ * each nullable (all null: the call checks the state only).  For a status
+ * other than OK all 36 values are -1; min_pivot is -1 for UNAVAILABLE and, for
+ * RANK_DEFICIENT, the first offending pivot, or -1 when a diagonal entry
+ * failed.  ARSLAM_E_STATE before a completed solve of the loaded batch
+ * (checked before any device call).  Uses the losses the last solve used: a
+ * set_loss after it changes nothing until the next solve.  Changes nothing
+ * arslam_localizer_solve returns; repeated calls give the same bits. */
+int arslam_localizer_covariance(arslam_localizer *h, double *cov, int *cov_status, double *min_pivot);
+/* The same; *kernel_ms (nullable) receives the device time of the covariance
+ * kernel, as arslam_localizer_solve's does for the solve (0 when nothing ran). */
+int arslam_localizer_covariance_timed(arslam_localizer *h, double *cov, int *cov_status, double *min_pivot,
+                                      double *kernel_ms);
+/* arslam_localize_many_loss plus the covariances: cov [n_query*36] and
+ * cov_status [n_query], either nullable. */
+int arslam_localize_many_cov(const arslam_localize_batch *b, const arslam_lm_options *opt, int kind, double a,
+                             arslam_localize_result *res, double *cov, int *cov_status);
+
 #ifdef __cplusplus
 }
 #endif

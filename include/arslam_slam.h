@@ -64,6 +64,18 @@ int arslam_slam_add_detections(arslam_slam *h, const char *capture_uid, int imag
 int arslam_slam_solve(arslam_slam *h);
 int arslam_slam_solve_incremental(arslam_slam *h);
 int arslam_slam_localize_many(arslam_slam *h, int first_loc_cap_idx);
+/* The 6x6 covariance of a capture the last arslam_slam_localize_many
+ * localized, at the pose it was given: arslam_localizer_covariance's
+ * (arslam_localize.h: row-major, parameters [t_c, w_c], unit-variance
+ * residuals, under the localize loss that call ran with) -- the mirror of
+ * ceres::Covariance::Compute on the capture block after localizeOne's Solve.
+ * *cov_status is ARSLAM_COV_*; cov holds -1 when it is not ARSLAM_COV_OK (a
+ * capture that was skipped, for one).  Both nullable.  localize_many keeps its
+ * batch on the device and computes nothing more; the covariances of all its
+ * captures are computed by the first call here after it.  ARSLAM_E_STATE for
+ * a capture the last localize_many did not cover (a mapping capture, or no
+ * localize_many yet). */
+int arslam_slam_localize_covariance(arslam_slam *h, int cap_idx, double cov[36], int *cov_status);
 
 int arslam_slam_num_captures(const arslam_slam *h);
 int arslam_slam_num_arucos(const arslam_slam *h);
