@@ -216,6 +216,71 @@ extern "C" int arslam_debug_dense_llt_ex(long n, double *A, const double *b, dou
   return ARSLAM_OK;
 }
 
+extern "C" int arslam_debug_selinv(long n, const double *A, const unsigned char *tile_pattern, double *Z_out,
+                                   unsigned char *pattern_out, int *info) {
+  if (n <= 0 || !A || !Z_out || !info) return ARSLAM_E_INVALID_ARG;
+  const long N = (n + 1 + arslam::kTile - 1) / arslam::kTile * arslam::kTile;
+  const int T = (int)(N / arslam::kTile);
+  std::vector<uint8_t> pattern((size_t)T * T, 0);
+  for (int i = 0; i < T; ++i)
+    for (int j = 0; j <= i; ++j) pattern[(size_t)i * T + j] = i == j || !tile_pattern || tile_pattern[(size_t)i * T + j];
+  const std::vector<uint8_t> given = pattern;
+  arslam::LltPlan plan;
+  arslam::SelinvPlan sp;
+  try {
+    arslam::llt_plan_build(plan, T, N, pattern, 0);   // (pattern: filled in place)
+    arslam::selinv_plan_build(plan, sp, 0);
+  } catch (...) {
+    arslam::llt_plan_free(plan);
+    return ARSLAM_E_HIP;
+  }
+  if (pattern_out) std::memcpy(pattern_out, pattern.data(), pattern.size());
+  // the matrix on the given tiles, a zero rhs as row n (pivot 1e300) and identity padding
+  std::vector<double> tiles((size_t)plan.n_tiles * 4096, 0.0);
+  for (int ti = 0; ti < T; ++ti)
+    for (int tj = 0; tj <= ti; ++tj) {
+      if (!given[(size_t)ti * T + tj]) continue;
+      double *t = tiles.data() + (size_t)plan.h_tile_id[(size_t)ti * T + tj] * 4096;
+      for (int r = 0; r < 64; ++r)
+        for (int c = 0; c < 64; ++c) {
+          const long i = ti * 64L + r, j = tj * 64L + c;
+          t[r * 64 + c] = j > i ? 0.0 : i < n ? A[i * n + j] : i == j ? (i == n ? 1e300 : 1.0) : 0.0;
+        }
+    }
+  double *d_S = nullptr, *d_Z = nullptr;
+  int *d_flag = nullptr;
+  const size_t bytes = tiles.size() * sizeof(double);
+  hipError_t e = hipMalloc(&d_S, bytes);
+  if (e == hipSuccess) e = hipMalloc(&d_Z, bytes);
+  if (e == hipSuccess) e = hipMalloc(&d_flag, sizeof(int));
+  if (e == hipSuccess) e = hipMemcpy(d_S, tiles.data(), bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d_Z, 0, bytes);
+  if (e == hipSuccess) e = hipMemset(d_flag, 0, sizeof(int));
+  if (e == hipSuccess) {
+    arslam::launch_dense_llt(plan, d_S, d_flag, 0);
+    arslam::launch_selinv(plan, sp, d_S, n, d_Z, d_flag, 0);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(tiles.data(), d_Z, bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(info, d_flag, sizeof(int), hipMemcpyDeviceToHost);
+  if (e == hipSuccess)
+    for (long i = 0; i < n; ++i)
+      for (long j = 0; j < n; ++j) {
+        // tile (ti, tj), ti >= tj, holds Z's rows of ti; the upper triangle is its mirror
+        const long ti = std::max(i, j) / 64, tj = std::min(i, j) / 64;
+        const int id = plan.h_tile_id[(size_t)ti * T + tj];
+        const long r = ti == tj ? i % 64 : std::max(i, j) % 64, c = ti == tj ? j % 64 : std::min(i, j) % 64;
+        Z_out[i * n + j] = id < 0 ? 0.0 : tiles[(size_t)id * 4096 + r * 64 + c];
+      }
+  arslam::selinv_plan_free(sp);
+  arslam::llt_plan_free(plan);
+  (void)hipFree(d_S);
+  (void)hipFree(d_Z);
+  (void)hipFree(d_flag);
+  return hip_fail(e);
+}
+
 namespace {
 // The protocol simulation over grids and policies (arslam::dag_simulate):
 // 1 if deadlock-free in every run, else -(grid * 16 + policy) of the first

@@ -386,6 +386,10 @@ void set_schur_big_lds_attribute();
 void launch_schur(const DevProblem &P, const double *x, const double *scale, const double *diag,
                   double radius, double *S, hipStream_t s, bool prep = false, long zero_tiles = 0,
                   const ExecReset *er = nullptr);
+// launch_schur's second half alone (one rank, prep mode): the gather of the
+// local systems already in P.slab into a cleared S, with the diagonal's D^2
+// and the padding / rhs rows (the covariance fills the slab itself)
+void launch_schur_gather(const DevProblem &P, const double *diag, double radius, double *S, hipStream_t s);
 // (which: -1 every row; 0 / 1 only the rows of tile columns of that class)
 void launch_prep_reduced(const DevProblem &P, const double *diag, double radius, double *S,
                          hipStream_t s, int which = -1);
@@ -558,5 +562,41 @@ void launch_dense_back_solve_dag(const LltPlan &P, const double *S, long nR, dou
 void launch_zero_tiles(const LltPlan &P, double *S, hipStream_t s);
 // copy the diagonal factors L_kk into S (tests only: S then holds the whole factor)
 void launch_scatter_diag(const LltPlan &P, double *S, hipStream_t s);
+
+// ---- selinv.hip ----
+// Selected inverse of the factored reduced system on the factor's tile
+// pattern (one-rank plans).  gcol[g]: the position in bs_cols of gather g's
+// column; n_products: its 64x64x64 tile products.
+struct SelinvPlan {
+  int *gcol = nullptr;
+  long n_products = 0;
+};
+void selinv_plan_build(const LltPlan &P, SelinvPlan &sp, hipStream_t s);
+void selinv_plan_free(SelinvPlan &sp);
+// After a factorization of S (launch_dense_llt or launch_dense_llt_dag): Z =
+// the real rows' (< nR) inverse on the plan's tiles (P.n_tiles x 4096, tile_id
+// addressing; diagonal tiles full and exactly symmetric, off-diagonal tiles
+// (i, k), i > k).  Overwrites the off-diagonal tiles of S.  Level launches on s.
+void launch_selinv(const LltPlan &P, const SelinvPlan &sp, double *S, long nR, double *Z, const int *flag,
+                   hipStream_t s);
+// The marginal 6x6 blocks of the covariance at the linearization in P.jrows,
+// in the device problem's block order, unscaled by the Jacobi scale:
+//   cov_f [36 nt], var_f [1]: the reduced-side blocks and the focal from Z (-1
+//     where the block has no reduced row);
+//   cov_e [36 nc], status_e [nc]: the eliminated blocks, R^{-1} (I + G Z G^T)
+//     R^{-T} from launch_cov_schur's G and R (one wavefront each; status 0
+//     computed, 1 constant or unused, 2 its R is singular; -1 in the block
+//     unless 0).
+// Z may be null when there is no reduced system.  *flag != 0: -1 everywhere.
+void launch_cov_blocks(const DevProblem &P, const double *Z, const double *scale, const double *Gb, const double *Rb,
+                       double *cov_e, int *status_e, double *cov_f, double *var_f, const int *flag, hipStream_t s);
+// The covariance's elimination of every e-block from P.jrows by an orthogonal
+// factorization E = Q R of its scaled columns (one wavefront each): G = Q'F
+// and R are kept for launch_cov_blocks, and with write_slab the local reduced
+// systems F'F - G'G go to P.slab in k_schur's layout (launch_schur_gather
+// then assembles S).  Scratch: Qb 48 nb doubles, Gb 6 (nc + 6 sum of the
+// e-blocks' distinct f-blocks), Rb 36 nc.
+void launch_cov_schur(const DevProblem &P, const double *scale, double *Qb, double *Gb, double *Rb, bool write_slab,
+                      hipStream_t s);
 
 }  // namespace arslam

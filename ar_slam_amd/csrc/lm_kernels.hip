@@ -1774,6 +1774,13 @@ void launch_schur(const DevProblem &P, const double *x, const double *scale, con
                        radius);
 }
 
+void launch_schur_gather(const DevProblem &P, const double *diag, double radius, double *S, hipStream_t s) {
+  const unsigned gb = (unsigned)((P.n_items + 3) / 4) + (unsigned)((P.N + 255) / 256);
+  hipLaunchKernelGGL(k_schur_gather, dim3(gb), dim3(256), 0, s, P, S, diag, radius);
+  if (P.n_splits)
+    hipLaunchKernelGGL(k_schur_combine, dim3((unsigned)((P.n_splits + 3) / 4)), dim3(256), 0, s, P, S, diag, radius);
+}
+
 void launch_prep_reduced(const DevProblem &P, const double *diag, double radius, double *S,
                          hipStream_t s, int which) {
   hipLaunchKernelGGL(k_prep_reduced, dim3((unsigned)((P.N + 255) / 256)), dim3(256), 0, s, P, diag,

@@ -375,6 +375,9 @@ struct arslam_lm {
     for (auto &t : timers) t.destroy();
     for (auto e : upd_events) (void)hipEventDestroy(e);
     if (ev_sync) (void)hipEventDestroy(ev_sync);
+    for (auto e : cov_ev)
+      if (e) (void)hipEventDestroy(e);
+    arslam::selinv_plan_free(cov_sp);
     arslam::llt_plan_free(plan);
     if (comm) (void)ncclCommDestroy(comm);
     if (stream) (void)hipStreamDestroy(stream);
@@ -644,6 +647,27 @@ struct arslam_lm {
   bool any_iter_cb = false;
   DevBuf<double> d_cb;
   int agree_callback(int r);
+
+  // ---- marginal covariances (arslam_lm_covariance) ----
+  // the last solve of the loaded problem: 0 none completed, 1 completed, 2 ended with EVAL_FAILED
+  int solve_state = 0;
+  // everything below is allocated at the first covariance call
+  arslam::SelinvPlan cov_sp;
+  bool cov_sp_ready = false;   // cov_sp is the loaded plan's
+  DevBuf<double> d_cov_Z, d_cov_Q, d_cov_Y, d_cov_R, d_cov_out, d_cov_diag;   // d_cov_out: e-blocks 36 nc | f-blocks 36 nt | var(f)
+  DevBuf<int> d_cov_status;
+  hipEvent_t cov_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  // the kept result, in the caller's block order (arslam_lm_covariance_block serves it)
+  bool cov_valid = false;
+  std::vector<double> cov_cap, cov_tag;
+  std::vector<int> cov_cap_status, cov_tag_status;
+  double cov_var_f = -1.0;
+  arslam_lm_cov_info cov_info{};
+  void covariance();
+  void cov_invalidate() {
+    solve_state = 0;
+    cov_valid = false;
+  }
 };
 
 namespace {
@@ -655,6 +679,8 @@ long round_up(long v, long m) { return (v + m - 1) / m * m; }
 void arslam_lm::load(const arslam_soa_problem *p_in, const arslam::ObsLoss &in_loss) {
   const double t_load = now_s();
   loaded = false;
+  cov_invalidate();
+  cov_sp_ready = false;
   // (the process's first HIP call starts the runtime, 0.02-0.2 s: the first
   // load of a process pays it here, in summary.setup_phase_s[0] -- round 4's
   // "1.2 ms per full load" was that one start averaged over 179 loads)
@@ -892,6 +918,7 @@ void arslam_lm::load(const arslam_soa_problem *p_in, const arslam::ObsLoss &in_l
 // sized for the problem.  Ends with the load's one stream sync.
 void arslam_lm::upload_problem(const arslam::HostProblem &h, const arslam::ReducedLayout &L, int extend_from) {
   const int maxk = h.maxk;
+  cov_invalidate();   // (an appended problem too: its last solve was another problem's)
   const std::vector<int> &row_slot = L.row_slot;
   // f-side slot -> reduced row (camera slots 0..2, then the tag slots)
   std::vector<int> fslot_row(3 + 6L * nt, -1);
@@ -1511,6 +1538,7 @@ void print_row(const arslam_lm_iteration &it) {
 
 void arslam_lm::solve(arslam_lm_summary *s) {
   fail_if(!loaded, ARSLAM_E_STATE, "no problem loaded");
+  cov_invalidate();
   const arslam_lm_options &o = opt;
   const double t_start = now_s();
   std::memset(s, 0, sizeof(*s));
@@ -1565,6 +1593,7 @@ void arslam_lm::solve(arslam_lm_summary *s) {
     s->termination = ARSLAM_FAILURE;
     s->rule = ARSLAM_RULE_EVAL_FAILED;
     s->total_time_s = now_s() - t_start;
+    solve_state = 2;
     return;
   }
   {
@@ -1950,6 +1979,181 @@ void arslam_lm::solve(arslam_lm_summary *s) {
   s->split_total_work = split_total_work;
   s->n_active_ranks = multi() ? split_active : 1;
   s->order_reused = last_order_reused ? 1 : 0;
+  solve_state = 1;
+}
+
+// Marginal covariances at the point the last solve returned (arslam_lm.h): the
+// structural gauge check on the host, then one linearization, the reduced
+// system without the LM diagonal (its own elimination kernel, the LM step's
+// gather) and its factorization as in an LM step, the selected inverse over
+// the factor's tiles and the two block kernels (selinv.hip).  Everything it writes on the device is scratch the next
+// solve rebuilds from the loaded state; the result is kept on the host in the
+// caller's block order.
+void arslam_lm::covariance() {
+  fail_if(!loaded || solve_state == 0, ARSLAM_E_STATE, "covariance: no completed solve of the loaded problem");
+  fail_if(solve_state == 2, ARSLAM_E_STATE, "covariance: the last solve ended with rule EVAL_FAILED");
+  fail_if(multi(), ARSLAM_E_UNSUPPORTED, "covariance: single-rank only");
+  fail_if(elim_used == ARSLAM_ELIM_MIXED, ARSLAM_E_UNSUPPORTED,
+          "covariance: the mixed e-block set is not supported (ARSLAM_ELIM_CAPTURES or _TAGS)");
+  cov_valid = false;
+  ensure_stream();
+  // the device problem's structure (its host copy is not kept after a load)
+  std::vector<int> h_cs(nc + 1, 0), h_ot(std::max(nb, 1));
+  std::vector<unsigned char> h_act(std::max(nb, 1));
+  int n_blk = 0;
+  HIP_CHECK(hipMemcpyAsync(h_cs.data(), u_cap_start, (nc + 1) * sizeof(int), hipMemcpyDeviceToHost, stream));
+  if (nb) HIP_CHECK(hipMemcpyAsync(h_ot.data(), u_obs_tag, nb * sizeof(int), hipMemcpyDeviceToHost, stream));
+  if (nb) HIP_CHECK(hipMemcpyAsync(h_act.data(), u_obs_active, nb, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipMemcpyAsync(&n_blk, u_cap_blk_start + nc, sizeof(int), hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  // Gauge: every connected component of the e-block / f-block graph over the
+  // active observations that holds a free block must hold a constant one
+  const auto e_free = [&](int c) { return slot_free[3 + 6L * c] != 0; };
+  const auto f_free = [&](int t) { return slot_free[3 + 6L * nc + 6L * t] != 0; };
+  bool deficient = false;
+  {
+    std::vector<int> par(nc + nt);
+    for (int i = 0; i < nc + nt; ++i) par[i] = i;
+    const auto find = [&](int a) {
+      while (par[a] != a) a = par[a] = par[par[a]];
+      return a;
+    };
+    std::vector<unsigned char> used(nc + nt, 0);
+    for (int c = 0; c < nc; ++c)
+      for (int q = h_cs[c]; q < h_cs[c + 1]; ++q) {
+        if (!h_act[q]) continue;
+        used[c] = used[nc + h_ot[q]] = 1;
+        const int a = find(c), b = find(nc + h_ot[q]);
+        if (a != b) par[a] = b;
+      }
+    std::vector<unsigned char> anchored(nc + nt, 0), needs(nc + nt, 0);
+    for (int i = 0; i < nc + nt; ++i) {
+      const bool fr = i < nc ? e_free(i) : f_free(i - nc);
+      if (fr) needs[find(i)] = 1;
+      else if (used[i]) anchored[find(i)] = 1;
+    }
+    for (int i = 0; i < nc + nt; ++i) deficient = deficient || (needs[i] && !anchored[i]);
+  }
+  std::vector<double> out(36L * nc + 36L * nt + 1, -1.0);
+  std::vector<int> st_e(std::max(nc, 1), 0);
+  arslam_lm_cov_info info{};
+  info.status = ARSLAM_COV_OK;
+  info.min_pivot = -1.0;
+  info.n_reduced = has_f ? nR : 0;
+  info.n_factor_tiles = has_f ? plan.n_tiles : 0;
+  if (!deficient) {
+    for (auto &e : cov_ev)
+      if (!e) HIP_CHECK(hipEventCreate(&e));
+    // 1. the linearization at the returned point (jrows; the handle's Jacobi scale stays)
+    x = xbest;
+    HIP_CHECK(hipEventRecord(cov_ev[0], stream));
+    double c0, c1, c2, c3, c4;
+    linearize(&c0, &c1, &c2, &c3, &c4);
+    HIP_CHECK(hipEventRecord(cov_ev[1], stream));
+    // 2. the reduced system with no LM diagonal, eliminated by an orthogonal
+    // factorization of each e-block's columns (k_cov_schur: the normal
+    // equations' F'F - W'U^-1 W loses cond(U) digits, too many for a
+    // covariance), gathered as an LM step's is, then factored.  The gather's
+    // diagonal is 0 on the free slots; the camera's l1 / l2 rows, which hold
+    // nothing else, get the pivot 1
+    std::vector<double> dg(n);
+    for (long i = 0; i < n; ++i) dg[i] = slot_free[i] ? 0.0 : 1.0;
+    dg[1] = dg[2] = 1.0;
+    d_cov_diag.alloc(n);
+    HIP_CHECK(hipMemcpyAsync(d_cov_diag.p, dg.data(), n * sizeof(double), hipMemcpyHostToDevice, stream));
+    d_cov_Q.alloc(std::max(48L * nb, 1L));
+    d_cov_Y.alloc(std::max(6L * (nc + 6L * n_blk), 1L));
+    d_cov_R.alloc(std::max(36L * nc, 1L));
+    arslam::launch_cov_schur(P, d_scale.p, d_cov_Q.p, d_cov_Y.p, d_cov_R.p, has_f, stream);
+    if (has_f) {
+      const bool dag = opt.factor_executor == 1;
+      if (dag) {
+        const arslam::LmDiagArgs ld{0, d_scale.p, d_colnorm.p, 0.0, 0.0, d_diag.p, d_yF.p, nR};
+        arslam::launch_exec_reset(plan, d_flag.p, stream, &ld);
+      } else {
+        HIP_CHECK(hipMemsetAsync(d_flag.p, 0, sizeof(int), stream));
+      }
+      arslam::launch_zero_tiles(plan, Sp, stream);
+      arslam::launch_schur_gather(P, d_cov_diag.p, 1.0, Sp, stream);
+      if (dag)
+        arslam::launch_dense_llt_dag(plan, Sp, d_flag.p, stream, dag_workgroups, nullptr, nullptr, false, -1, LONG_MAX);
+      else
+        arslam::launch_dense_llt(plan, Sp, d_flag.p, stream, nullptr);
+    } else {
+      HIP_CHECK(hipMemsetAsync(d_flag.p, 0, sizeof(int), stream));
+    }
+    HIP_CHECK(hipEventRecord(cov_ev[2], stream));
+    // 3. the selected inverse on the factor's tiles
+    if (has_f) {
+      if (!cov_sp_ready) {
+        arslam::selinv_plan_build(plan, cov_sp, stream);
+        cov_sp_ready = true;
+      }
+      d_cov_Z.alloc((size_t)plan.n_tiles * 4096);
+      arslam::launch_selinv(plan, cov_sp, Sp, nR, d_cov_Z.p, d_flag.p, stream);
+      info.n_selinv_products = cov_sp.n_products;
+      info.n_factor_products = plan.total_upd_tiles + (long)plan.h_gather.size() + plan.T;
+    }
+    HIP_CHECK(hipEventRecord(cov_ev[3], stream));
+    // 4. the blocks
+    d_cov_out.alloc(out.size());
+    d_cov_status.alloc(std::max(nc, 1));
+    arslam::launch_cov_blocks(P, has_f ? d_cov_Z.p : nullptr, d_scale.p, d_cov_Y.p, d_cov_R.p, d_cov_out.p, d_cov_status.p,
+                              d_cov_out.p + 36L * nc, d_cov_out.p + 36L * nc + 36L * nt, d_flag.p, stream);
+    HIP_CHECK(hipEventRecord(cov_ev[4], stream));
+    int flag = 0;
+    std::vector<double> ld(has_f ? (size_t)plan.T * 4096 : 0);
+    HIP_CHECK(hipMemcpyAsync(out.data(), d_cov_out.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (nc) HIP_CHECK(hipMemcpyAsync(st_e.data(), d_cov_status.p, nc * sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(&flag, d_flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+    if (has_f) HIP_CHECK(hipMemcpyAsync(ld.data(), plan.ldiag, ld.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    if (flag < 0) throw Error(ARSLAM_E_DEVICE, executor_fault_message(flag, rank, -1, plan, stream));
+    float ms[4] = {0, 0, 0, 0};
+    for (int i = 0; i < 4; ++i) HIP_CHECK(hipEventElapsedTime(&ms[i], cov_ev[i], cov_ev[i + 1]));
+    info.t_linearize_ms = ms[0];
+    info.t_factor_ms = ms[1];
+    info.t_selinv_ms = ms[2];
+    info.t_blocks_ms = ms[3];
+    // the numeric test: no failed pivot, and the smallest squared pivot of the
+    // real rows (not l1 / l2, the padding or the rhs) at least 1e-14
+    if (flag > 0) {
+      deficient = true;
+    } else {
+      double mp = 1.0;
+      bool first = true;
+      for (long r = 0; r < (has_f ? nR : 0); ++r) {
+        const int sl = lay.row_slot[r];
+        if (sl < 0 || sl == 1 || sl == 2) continue;
+        const double l = ld[(size_t)(r >> 6) * 4096 + (r & 63) * 65];
+        const double p2 = l * l;
+        if (first || !(p2 >= mp)) mp = p2;   // (a NaN pivot stays)
+        first = false;
+      }
+      info.min_pivot = mp;
+      if (!(mp >= 1e-14)) deficient = true;
+    }
+  }
+  if (deficient) {
+    info.status = ARSLAM_COV_RANK_DEFICIENT;
+    std::fill(out.begin(), out.end(), -1.0);
+  }
+  // statuses in the device problem's order, then the caller's arrays (tag
+  // elimination: the e-blocks are the caller's tags)
+  std::vector<int> se(nc), sf(nt);
+  for (int c = 0; c < nc; ++c)
+    se[c] = !e_free(c) ? ARSLAM_COV_UNAVAILABLE : (deficient || st_e[c] == 2) ? ARSLAM_COV_RANK_DEFICIENT : ARSLAM_COV_OK;
+  for (int t = 0; t < nt; ++t)
+    sf[t] = !f_free(t) ? ARSLAM_COV_UNAVAILABLE : deficient ? ARSLAM_COV_RANK_DEFICIENT : ARSLAM_COV_OK;
+  const bool swapped = elim_used == ARSLAM_ELIM_TAGS;
+  std::vector<double> ce(out.begin(), out.begin() + 36L * nc), cf(out.begin() + 36L * nc, out.begin() + 36L * (nc + nt));
+  cov_cap = swapped ? cf : ce;
+  cov_tag = swapped ? ce : cf;
+  cov_cap_status = swapped ? sf : se;
+  cov_tag_status = swapped ? se : sf;
+  cov_var_f = out.back();
+  cov_info = info;
+  cov_valid = true;
 }
 
 // ===========================================================================
@@ -2257,6 +2461,68 @@ int arslam_lm_solve_soa(arslam_soa_problem *p, const arslam_lm_options *opt,
   });
   arslam_lm_destroy(h);
   return rc;
+}
+
+int arslam_lm_covariance(arslam_lm *h, double *cov_cap, double *cov_tag, double *var_f, int *cap_status,
+                         int *tag_status, arslam_lm_cov_info *info) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    h->covariance();
+    if (cov_cap && !h->cov_cap.empty()) std::memcpy(cov_cap, h->cov_cap.data(), h->cov_cap.size() * sizeof(double));
+    if (cov_tag && !h->cov_tag.empty()) std::memcpy(cov_tag, h->cov_tag.data(), h->cov_tag.size() * sizeof(double));
+    if (var_f) *var_f = h->cov_var_f;
+    if (cap_status && !h->cov_cap_status.empty())
+      std::memcpy(cap_status, h->cov_cap_status.data(), h->cov_cap_status.size() * sizeof(int));
+    if (tag_status && !h->cov_tag_status.empty())
+      std::memcpy(tag_status, h->cov_tag_status.data(), h->cov_tag_status.size() * sizeof(int));
+    if (info) *info = h->cov_info;
+  });
+}
+
+int arslam_lm_covariance_block(arslam_lm *h, const double *block, double *cov, int *status) {
+  if (!h || !block || !cov) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    double *key = const_cast<double *>(block);
+    const auto ci = h->cap_of.find(key);
+    const auto ti = h->tag_of.find(key);
+    fail_if(key != h->camera_ptr && ci == h->cap_of.end() && ti == h->tag_of.end(), ARSLAM_E_INVALID_ARG,
+            "parameter block is not part of the problem");
+    fail_if(!h->pk_loaded || h->pk_dirty, ARSLAM_E_STATE,
+            "covariance_block: no completed arslam_lm_solve of the problem as it stands");
+    if (!h->cov_valid) h->covariance();
+    if (key == h->camera_ptr) {
+      std::fill(cov, cov + 9, 0.0);
+      cov[0] = h->cov_var_f;
+      const bool ok = h->cov_var_f >= 0.0;
+      if (!ok) std::fill(cov, cov + 9, -1.0);
+      if (status)
+        *status = ok ? ARSLAM_COV_OK
+                     : h->cov_info.status == ARSLAM_COV_RANK_DEFICIENT && !h->constant.count(key) ? ARSLAM_COV_RANK_DEFICIENT
+                                                                                                   : ARSLAM_COV_UNAVAILABLE;
+      return;
+    }
+    const bool is_cap = ci != h->cap_of.end();
+    const int i = is_cap ? ci->second : ti->second;
+    const std::vector<double> &c = is_cap ? h->cov_cap : h->cov_tag;
+    const std::vector<int> &st = is_cap ? h->cov_cap_status : h->cov_tag_status;
+    fail_if((size_t)i >= st.size(), ARSLAM_E_STATE, "covariance_block: the block is not part of the solved problem");
+    std::memcpy(cov, c.data() + 36L * i, 36 * sizeof(double));
+    if (status) *status = st[i];
+  });
+}
+
+int arslam_lm_debug_reduced_rows(arslam_lm *h, int *cap_row, int *tag_row, int *cam_row) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    fail_if(!h->loaded || h->multi() || h->elim_used == ARSLAM_ELIM_MIXED, ARSLAM_E_STATE,
+            "reduced_rows: a one-rank problem loaded with capture or tag elimination");
+    const bool swapped = h->elim_used == ARSLAM_ELIM_TAGS;
+    // (the device problem's e-blocks nc, f-blocks nt; no reduced system: the layout has no rows)
+    int *e_row = swapped ? tag_row : cap_row, *f_row = swapped ? cap_row : tag_row;
+    for (int c = 0; c < h->nc && e_row; ++c) e_row[c] = -1;
+    for (int t = 0; t < h->nt && f_row; ++t) f_row[t] = (size_t)t < h->lay.tag_row.size() ? h->lay.tag_row[t] : -1;
+    if (cam_row) *cam_row = h->has_f ? h->P.cam_row : -1;
+  });
 }
 
 int arslam_comm_unique_id(unsigned char id[ARSLAM_COMM_ID_BYTES]) {

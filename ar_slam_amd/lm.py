@@ -47,7 +47,8 @@ EXPORTS = ["arslam_lm_options_init", "arslam_lm_create", "arslam_lm_destroy",
            "arslam_lm_set_loss", "arslam_lm_get_loss", "arslam_lm_add_residual_block_loss",
            "arslam_lm_load_soa_loss", "arslam_debug_residual_jacobian_loss", "arslam_slam_set_loss",
            "arslam_debug_residual_jacobian", "arslam_debug_dense_llt", "arslam_debug_dense_llt_ex",
-           "arslam_debug_angle_axis_rotate", "arslam_lm_debug_force_indefinite",
+           "arslam_debug_angle_axis_rotate", "arslam_debug_selinv", "arslam_lm_debug_force_indefinite",
+           "arslam_lm_covariance", "arslam_lm_covariance_block", "arslam_lm_debug_reduced_rows",
            "arslam_lm_debug_force_multirank", "arslam_lm_debug_break_dependency", "arslam_lm_debug_tag_pair_tile",
            "arslam_debug_reduced_plan", "arslam_debug_reduced_plan_side", "arslam_debug_schur_stamps", "arslam_debug_ceres_e_blocks",
            "arslam_debug_mixed_groups",
@@ -154,6 +155,20 @@ class Summary(C.Structure):
         return d
 
 
+COV_OK, COV_UNAVAILABLE, COV_RANK_DEFICIENT = 0, 1, 2   # arslam_lm.h ARSLAM_COV_*
+
+
+class CovInfo(C.Structure):
+    """arslam_lm_cov_info."""
+    _fields_ = [("status", C.c_int), ("min_pivot", C.c_double), ("n_reduced", C.c_long),
+                ("n_factor_tiles", C.c_long), ("n_factor_products", C.c_long), ("n_selinv_products", C.c_long),
+                ("t_linearize_ms", C.c_double), ("t_factor_ms", C.c_double), ("t_selinv_ms", C.c_double),
+                ("t_blocks_ms", C.c_double)]
+
+    def to_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class SoaProblem(C.Structure):
     _fields_ = [("n_cap", C.c_int), ("n_tag", C.c_int), ("n_obs", C.c_int),
                 ("camera", _dp), ("cap", _dp), ("tag", _dp),
@@ -253,6 +268,10 @@ def lib():
     L.arslam_debug_residual_jacobian.argtypes = [C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]
     L.arslam_debug_dense_llt.argtypes = [C.c_long, _dp, _dp, _dp, C.POINTER(C.c_int)]
     L.arslam_debug_angle_axis_rotate.argtypes = [C.c_int, _dp, _dp, _dp, _ip]
+    L.arslam_debug_selinv.argtypes = [C.c_long, _dp, _up, _dp, _up, _ip]
+    L.arslam_lm_covariance.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip, _ip, C.POINTER(CovInfo)]
+    L.arslam_lm_covariance_block.argtypes = [C.c_void_p, _dp, _dp, _ip]
+    L.arslam_lm_debug_reduced_rows.argtypes = [C.c_void_p, _ip, _ip, _ip]
     L.arslam_debug_ceres_e_blocks.argtypes = [C.POINTER(SoaProblem), _ip]
     L.arslam_debug_mixed_groups.argtypes = [C.POINTER(SoaProblem), _ip, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]
     L.arslam_lm_debug_force_indefinite.argtypes = [C.c_void_p, C.c_ulonglong]
@@ -468,6 +487,32 @@ class ResidentProblem(_Handle):
         _check(lib().arslam_lm_solve_loaded(self._h, C.byref(s)))
         return s.to_dict()
 
+    def covariance(self):
+        """Marginal covariances at the point the last ``solve()`` returned (arslam_lm_covariance):
+        ``cap`` (n_cap, 6, 6), ``tag`` (n_tag, 6, 6), ``var_f``, ``cap_status`` / ``tag_status``
+        (COV_*) and ``info`` (arslam_lm_cov_info as a dict).  Unit-variance residuals: times sigma^2."""
+        n_cap, n_tag = self.A.s.n_cap, self.A.s.n_tag
+        cap = np.zeros((n_cap, 6, 6))
+        tag = np.zeros((n_tag, 6, 6))
+        var_f = C.c_double(0.0)
+        cs = np.zeros(max(n_cap, 1), np.int32)
+        ts = np.zeros(max(n_tag, 1), np.int32)
+        info = CovInfo()
+        _check(lib().arslam_lm_covariance(self._h, cap.ctypes.data_as(_dp), tag.ctypes.data_as(_dp), C.byref(var_f),
+                                          cs.ctypes.data_as(_ip), ts.ctypes.data_as(_ip), C.byref(info)))
+        return {"cap": cap, "tag": tag, "var_f": var_f.value, "cap_status": cs[:n_cap], "tag_status": ts[:n_tag],
+                "info": info.to_dict()}
+
+    def debug_reduced_rows(self):
+        """(cap_row (n_cap,), tag_row (n_tag,), cam_row): the first reduced row of each block, -1 off
+        the reduced side (arslam_lm_debug_reduced_rows)."""
+        cr = np.zeros(max(self.A.s.n_cap, 1), np.int32)
+        tr = np.zeros(max(self.A.s.n_tag, 1), np.int32)
+        cam = C.c_int(-1)
+        _check(lib().arslam_lm_debug_reduced_rows(self._h, cr.ctypes.data_as(_ip), tr.ctypes.data_as(_ip),
+                                                  C.byref(cam)))
+        return cr[:self.A.s.n_cap], tr[:self.A.s.n_tag], cam.value
+
     def owned_captures(self):
         """Indices of the captures this rank owns (every capture on one rank)."""
         n = C.c_int(0)
@@ -535,6 +580,18 @@ class Problem(_Handle):
         s = Summary()
         _check(lib().arslam_lm_solve(self._h, C.byref(s)))
         return s.to_dict()
+
+    def covariance_block(self, block):
+        """Covariance::GetCovarianceBlock(block, block) after ``solve()``: (6, 6) for a pose block,
+        (3, 3) for the camera block (var(f) at [0, 0]); and its status (COV_*)."""
+        if not (isinstance(block, np.ndarray) and block.dtype == np.float64 and block.size in (3, 6)):
+            raise TypeError("parameter block must be a float64 array of size 3 or 6")
+        k = block.size
+        out = np.zeros((k, k))
+        st = C.c_int(0)
+        _check(lib().arslam_lm_covariance_block(self._h, block.ctypes.data_as(_dp), out.ctypes.data_as(_dp),
+                                                C.byref(st)))
+        return out, st.value
 
     def reset(self):
         _check(lib().arslam_lm_reset(self._h))
@@ -609,6 +666,26 @@ def debug_dense_llt(A, b, executor=0):
     _check(lib().arslam_debug_dense_llt_ex(C.c_long(n), A.ctypes.data_as(_dp), b.ctypes.data_as(_dp),
                                            y.ctypes.data_as(_dp), C.byref(info), C.c_int(executor)))
     return A, y, info.value
+
+
+def debug_selinv(A, tile_pattern=None):
+    """Device selected inverse of the SPD matrix A on the tiles of its factor (the step behind
+    ``covariance()``, alone).  tile_pattern: None for a dense matrix, else (T, T) with T =
+    (n + 1 + 63) // 64, non-zero where lower tile (i, j) of A is taken.  Returns (Z (n, n): the
+    inverse on the factor's tiles, 0 elsewhere; pattern (T, T): the factor's lower tile pattern; info)."""
+    A = _f64(A)
+    n = A.shape[0]
+    T = (n + 1 + 63) // 64
+    pat = None
+    if tile_pattern is not None:
+        pat = np.ascontiguousarray(tile_pattern, np.uint8).reshape(T, T)
+    Z = np.zeros((n, n))
+    out = np.zeros((T, T), np.uint8)
+    info = C.c_int(0)
+    _check(lib().arslam_debug_selinv(C.c_long(n), A.ctypes.data_as(_dp),
+                                     pat.ctypes.data_as(_up) if pat is not None else None,
+                                     Z.ctypes.data_as(_dp), out.ctypes.data_as(_up), C.byref(info)))
+    return Z, out, info.value
 
 
 class PlanInfo(C.Structure):

@@ -307,6 +307,83 @@ enum { ARSLAM_SOLVER_CONTINUE = 0, ARSLAM_SOLVER_ABORT = 1, ARSLAM_SOLVER_TERMIN
 typedef int (*arslam_iteration_callback)(void *ctx, const arslam_lm_iteration *it);
 int arslam_lm_set_iteration_callback(arslam_lm *h, arslam_iteration_callback fn, void *ctx);
 
+/* ---- marginal pose covariances (ceres::Covariance) ----
+ * What ceres::Covariance::Compute after Solve, then GetCovarianceBlock(p, p)
+ * for every pose block p and the camera, would give
+ * (Covariance::Options::apply_loss_function = true).  At the parameters the
+ * last solve returned, H = J~'J~ over every active residual block and every
+ * free parameter -- the focal f if the camera is free and used (never l1, l2:
+ * their Jacobian columns are zero), 6 per free capture, 6 per free tag -- the
+ * Jacobian rows corrected by sqrt(rho'(s)) exactly as the solve corrects them,
+ * no LM diagonal.  C = H^-1, for unit-variance residuals: with pixel noise
+ * sigma, multiply by sigma^2.  Only the marginals are returned: the 6x6
+ * diagonal block of C of every free capture ([t_c, w_c], row-major) and tag
+ * ([t_t, w_t]), and var(f).  C[i][j] and C[j][i] are the same bits.
+ *
+ * Gauge: the mapping problem has a 6-DoF gauge freedom unless a pose block is
+ * held constant (arslam_lm_set_parameter_block_constant / cap_const /
+ * tag_const).  As with Ceres' Cholesky-based covariance, a gauge-free problem
+ * has no covariance; the result is the covariance in the anchor's gauge.  The
+ * host checks this structurally before any device work (a union-find, no
+ * threshold): every connected component of the capture-tag graph over the
+ * active observations must contain a constant pose block, else the status is
+ * ARSLAM_COV_RANK_DEFICIENT.  Behind it a numeric test: the factorization of
+ * the reduced system (Jacobi-scaled, no LM diagonal) must raise no
+ * non-positive pivot, and the smallest squared pivot of its real rows
+ * (min_pivot; the rows of l1 / l2, the padding and the right-hand side
+ * excluded) must be >= 1e-14.  This threshold stands where Ceres tests
+ * singular values against min_reciprocal_condition_number = 1e-14; it is NOT
+ * the same number (a pivot of the scaled Cholesky, not a ratio of singular
+ * values).
+ *
+ * The device work: one linearization at the returned point, the reduced
+ * system (each eliminated block by an orthogonal factorization of its
+ * columns, not the LM step's normal equations, whose error would be
+ * multiplied by the block's condition number) and its tile Cholesky as in an
+ * LM step, a selected inverse over the factor's tiles (about two
+ * factorizations' worth of tile products), then one small kernel per side
+ * for the blocks.
+ *
+ * Valid after a completed arslam_lm_solve_loaded or arslam_lm_solve on the
+ * handle, NO_CONVERGENCE included (the linearization at the returned point).
+ * ARSLAM_E_STATE when no completed solve precedes the call or the last one
+ * ended with rule EVAL_FAILED (both checked before any device call).
+ * ARSLAM_E_UNSUPPORTED with several ranks (arslam_lm_debug_force_multirank
+ * included) and when the loaded problem's elimination_used is
+ * ARSLAM_ELIM_MIXED; ARSLAM_ELIM_CAPTURES, _TAGS, and _AUTO or _MIXED
+ * resolving to one whole side are supported.  The call changes nothing a
+ * later solve returns, repeated calls give the same bits, and nothing is
+ * allocated or launched for it before the first call. */
+#define ARSLAM_COV_OK 0
+#define ARSLAM_COV_UNAVAILABLE 1     /* no covariance for this block: it is constant or unused */
+#define ARSLAM_COV_RANK_DEFICIENT 2
+typedef struct {
+  int status;               /* ARSLAM_COV_OK or ARSLAM_COV_RANK_DEFICIENT for the whole problem */
+  double min_pivot;         /* smallest squared pivot of the reduced system's real rows (1 with no
+                               reduced system; -1 when the structural check or a pivot failed) */
+  long n_reduced;           /* rows of the reduced system */
+  long n_factor_tiles;      /* 64x64 tiles of its factor = tiles of the selected inverse */
+  long n_factor_products;   /* 64x64x64 tile products of one factorization (updates, solves, diagonal tiles) */
+  long n_selinv_products;   /* ... and of the selected inverse */
+  double t_linearize_ms, t_factor_ms, t_selinv_ms, t_blocks_ms;   /* device times (HIP events): linearization,
+                               reduced system + factorization, selected inverse, marginal blocks */
+} arslam_lm_cov_info;
+/* cov_cap [n_cap*36], cov_tag [n_tag*36], var_f [1], cap_status [n_cap],
+ * tag_status [n_tag] (ARSLAM_COV_*), info: each nullable.  A block that is
+ * constant or unused gets ARSLAM_COV_UNAVAILABLE and -1 in its 36 values (so
+ * does var_f for a constant or unused camera); with info->status
+ * RANK_DEFICIENT every value is -1 and every free block's status
+ * RANK_DEFICIENT. */
+int arslam_lm_covariance(arslam_lm *h, double *cov_cap, double *cov_tag, double *var_f, int *cap_status,
+                         int *tag_status, arslam_lm_cov_info *info);
+/* Covariance::GetCovarianceBlock(block, block, cov) for a block added through
+ * arslam_lm_add_residual_block: 36 values for a pose block; 9 for the camera
+ * block, var(f) at [0] and 0 elsewhere.  Computes on the first request after
+ * a solve and serves later requests from the kept result.  *status (nullable)
+ * = ARSLAM_COV_*; -1 in the values unless OK.  ARSLAM_E_INVALID_ARG for a
+ * pointer that is not a block of the problem. */
+int arslam_lm_covariance_block(arslam_lm *h, const double *block, double *cov, int *status);
+
 /* Diagnostics */
 int arslam_device_count(void);
 const char *arslam_lm_last_error(void);

@@ -42,6 +42,27 @@ int arslam_debug_dense_llt(long n, double *A, const double *b, double *y, int *i
  * info < 0 reports a task-graph wait that timed out */
 int arslam_debug_dense_llt_ex(long n, double *A, const double *b, double *y, int *info, int executor);
 
+/* The selected inverse behind arslam_lm_covariance, alone: factor the n x n
+ * row-major SPD matrix A as the reduced system is factored (64 x 64 tiles, a
+ * zero right-hand side as row n, identity padding after it; level launches)
+ * and compute Z = A^{-1} on the tiles of the factor (Takahashi recursion).
+ * tile_pattern: NULL for a dense matrix, else T*T bytes, T = (n + 1 + 63) / 64,
+ * non-zero where lower tile (i, j), j <= i, of A is taken (A's entries
+ * elsewhere are not read; diagonal tiles are always taken).  Z_out [n*n]: both
+ * triangles of Z on the factor's tiles, 0 on the others.  pattern_out (may be
+ * NULL) [T*T]: the factor's lower tile pattern, the given one after symbolic
+ * fill.  *info = 0 on success, k+1 if pivot k was not positive. */
+int arslam_debug_selinv(long n, const double *A, const unsigned char *tile_pattern, double *Z_out,
+                        unsigned char *pattern_out, int *info);
+
+/* The loaded problem's reduced rows, by the caller's blocks (one rank, capture
+ * or tag elimination): cap_row [n_cap], tag_row [n_tag] = the first of the
+ * block's 6 rows in the reduced system, -1 for a block that is eliminated,
+ * constant or unused; *cam_row = the focal's row (l1, l2 follow it), -1 if
+ * the camera is not free.  Each nullable.  The order in which a reference has
+ * to eliminate to reproduce arslam_lm_cov_info.min_pivot. */
+int arslam_lm_debug_reduced_rows(arslam_lm *h, int *cap_row, int *tag_row, int *cam_row);
+
 /* Host-only symbolic analysis of the reduced system (no device needed): the
  * row layout arslam_lm_load_soa would choose for problem p under the given
  * ordering (0 natural, 1 RCM, 2 nested dissection) and tile pattern

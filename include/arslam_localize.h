@@ -131,10 +131,9 @@ int arslam_localize_many_loss(const arslam_localize_batch *b, const arslam_lm_op
  *   - C[i][j] and C[j][i] are the same bits.
  *   - NO_CONVERGENCE and MIN_RADIUS queries get a covariance like any other:
  *     the linearization at the returned pose. */
-#define ARSLAM_COV_OK 0
-#define ARSLAM_COV_UNAVAILABLE 1     /* the query was skipped, or its status is FAILURE with rule
-                                        EVAL_FAILED, or the evaluation at the returned pose is not finite */
-#define ARSLAM_COV_RANK_DEFICIENT 2
+/* cov_status: ARSLAM_COV_OK, _UNAVAILABLE, _RANK_DEFICIENT (arslam_lm.h).  UNAVAILABLE here: the query
+ * was skipped, or its status is FAILURE with rule EVAL_FAILED, or the evaluation at the returned
+ * pose is not finite. */
 /* cov [n_query*36], cov_status [n_query] (ARSLAM_COV_*), min_pivot [n_query];
  * each nullable (all null: the call checks the state only).  For a status
  * other than OK all 36 values are -1; min_pivot is -1 for UNAVAILABLE and, for
