@@ -1,0 +1,521 @@
+// lm_capi.hip -- the C-ABI of include/arslam_lm.h over the LM handle
+// (lm_handle.h): argument checks, the pointer-keyed problem's staging, and
+// the translation of exceptions into error codes.
+#include "lm_handle.h"
+
+arslam_lm::~arslam_lm() {
+  for (auto &t : timers) t.destroy();
+  for (auto e : upd_events) (void)hipEventDestroy(e);
+  if (ev_sync) (void)hipEventDestroy(ev_sync);
+  for (auto e : cov_ev)
+    if (e) (void)hipEventDestroy(e);
+  arslam::selinv_plan_free(cov_sp);
+  arslam::llt_plan_free(plan);
+  if (comm) (void)ncclCommDestroy(comm);
+  if (stream) (void)hipStreamDestroy(stream);
+}
+
+// ===========================================================================
+// C-ABI
+// ===========================================================================
+
+namespace {
+thread_local std::string g_last_error;
+}  // namespace
+namespace arslam {
+void set_last_error(const std::string &msg) { g_last_error = msg; }
+}  // namespace arslam
+namespace {
+template <class F>
+int guarded(F &&f) {
+  try {
+    f();
+    return ARSLAM_OK;
+  } catch (const Error &e) {
+    g_last_error = e.what();
+    return e.code;
+  } catch (const std::bad_alloc &) {
+    g_last_error = "host out of memory";
+    return ARSLAM_E_OUT_OF_MEMORY;
+  } catch (const std::exception &e) {
+    g_last_error = e.what();
+    return ARSLAM_E_HIP;
+  } catch (...) {
+    g_last_error = "unknown error";
+    return ARSLAM_E_HIP;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int arslam_lm_options_init(arslam_lm_options *o) {
+  if (!o) return ARSLAM_E_INVALID_ARG;
+  std::memset(o, 0, sizeof(*o));
+  o->max_num_iterations = 50;              // ar_slam_util.cpp:1004
+  o->function_tolerance = 1e-6;            // Ceres 2.0 defaults below
+  o->gradient_tolerance = 1e-10;
+  o->parameter_tolerance = 1e-8;
+  o->initial_trust_region_radius = 1e4;
+  o->max_trust_region_radius = 1e16;
+  o->min_trust_region_radius = 1e-32;
+  o->min_relative_decrease = 1e-3;
+  o->min_lm_diagonal = 1e-6;
+  o->max_lm_diagonal = 1e32;
+  o->max_num_consecutive_invalid_steps = 5;
+  o->jacobi_scaling = 1;
+  o->elimination = ARSLAM_ELIM_AUTO;       // DENSE_SCHUR, ar_slam_util.cpp:1011
+  o->minimizer_progress_to_stdout = 0;
+  o->update_state_every_iteration = 0;
+  o->device = -1;
+  o->cholesky_skip_zero_tiles = 1;
+  o->reduced_ordering = 2;
+  o->kernel_timing = 0;
+  o->factor_executor = 1;
+  o->phase_timing = 0;
+  return ARSLAM_OK;
+}
+
+int arslam_lm_create(arslam_lm **out, const arslam_lm_options *opt) {
+  if (!out) return ARSLAM_E_INVALID_ARG;
+  *out = nullptr;
+  return guarded([&] {
+    auto *h = new arslam_lm();
+    if (opt) h->opt = *opt; else arslam_lm_options_init(&h->opt);
+    if (h->opt.elimination < ARSLAM_ELIM_AUTO || h->opt.elimination > ARSLAM_ELIM_MIXED) {
+      delete h;
+      throw Error(ARSLAM_E_INVALID_ARG, "elimination must be ARSLAM_ELIM_AUTO, _CAPTURES, _TAGS or _MIXED");
+    }
+    *out = h;
+  });
+}
+
+void arslam_lm_destroy(arslam_lm *h) { delete h; }
+
+int arslam_lm_set_options(arslam_lm *h, const arslam_lm_options *opt) {
+  if (!h || !opt) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    fail_if(opt->elimination < ARSLAM_ELIM_AUTO || opt->elimination > ARSLAM_ELIM_MIXED, ARSLAM_E_INVALID_ARG,
+            "elimination must be ARSLAM_ELIM_AUTO, _CAPTURES, _TAGS or _MIXED");
+    fail_if(opt->factor_executor != 0 && opt->factor_executor != 1, ARSLAM_E_INVALID_ARG,
+            "factor_executor must be 0 or 1");
+    fail_if(opt->max_num_iterations < 0 || opt->max_num_iterations > ARSLAM_LM_MAX_ITERS,
+            ARSLAM_E_INVALID_ARG, "max_num_iterations out of range");
+    // the stream and every device buffer live on the device of the first load
+    fail_if(h->stream && opt->device >= 0 && opt->device != h->device,
+            ARSLAM_E_INVALID_ARG, "a handle's device is fixed once it has loaded a problem: create a new handle");
+    if (opt->device != h->opt.device || opt->reduced_ordering != h->opt.reduced_ordering ||
+        opt->cholesky_skip_zero_tiles != h->opt.cholesky_skip_zero_tiles || opt->elimination != h->opt.elimination)
+      h->loaded = false, h->pk_dirty = true;
+    h->opt = *opt;
+  });
+}
+
+int arslam_lm_get_options(const arslam_lm *h, arslam_lm_options *opt) {
+  if (!h || !opt) return ARSLAM_E_INVALID_ARG;
+  *opt = h->opt;
+  return ARSLAM_OK;
+}
+
+int arslam_lm_set_loss(arslam_lm *h, int kind, double a) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    fail_if(!arslam::loss_valid(kind, a), ARSLAM_E_INVALID_ARG,
+            "loss: kind must be ARSLAM_LOSS_NONE, _HUBER, _SOFT_L_ONE or _CAUCHY, its scale finite and > 0");
+    h->def_loss_kind = kind;
+    h->def_loss_a = kind == ARSLAM_LOSS_NONE ? 0.0 : a;
+    // (the pointer-keyed blocks keep the losses they were added with; the
+    // resident problem is dropped all the same: one rule for both paths)
+    h->loaded = false;
+    h->pk_dirty = true;
+  });
+}
+
+int arslam_lm_get_loss(const arslam_lm *h, int *kind, double *a) {
+  if (!h || !kind || !a) return ARSLAM_E_INVALID_ARG;
+  *kind = h->def_loss_kind;
+  *a = h->def_loss_a;
+  return ARSLAM_OK;
+}
+
+int arslam_lm_add_residual_block(arslam_lm *h, const double corners[8], double *camera,
+                                 double *capture, double *tag) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return arslam_lm_add_residual_block_loss(h, corners, camera, capture, tag, h->def_loss_kind, h->def_loss_a);
+}
+
+int arslam_lm_add_residual_block_loss(arslam_lm *h, const double corners[8], double *camera,
+                                      double *capture, double *tag, int kind, double a) {
+  if (!h || !corners || !camera || !capture || !tag) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    fail_if(!arslam::loss_valid(kind, a), ARSLAM_E_INVALID_ARG,
+            "loss: kind must be ARSLAM_LOSS_NONE, _HUBER, _SOFT_L_ONE or _CAUCHY, its scale finite and > 0");
+    fail_if(h->camera_ptr && h->camera_ptr != camera, ARSLAM_E_UNSUPPORTED,
+            "one shared camera block per problem (ArSlamSolver::camera_)");
+    fail_if(capture == camera || tag == camera || capture == tag, ARSLAM_E_INVALID_ARG,
+            "parameter blocks must be distinct");
+    fail_if(h->tag_of.count(capture) || h->cap_of.count(tag), ARSLAM_E_INVALID_ARG,
+            "a block cannot be both a capture and a tag");
+    h->camera_ptr = camera;
+    auto ci = h->cap_of.find(capture);
+    int c;
+    if (ci == h->cap_of.end()) {
+      c = (int)h->cap_ptrs.size();
+      h->cap_of.emplace(capture, c);
+      h->cap_ptrs.push_back(capture);
+    } else {
+      c = ci->second;
+    }
+    auto ti = h->tag_of.find(tag);
+    int t;
+    if (ti == h->tag_of.end()) {
+      t = (int)h->tag_ptrs.size();
+      h->tag_of.emplace(tag, t);
+      h->tag_ptrs.push_back(tag);
+    } else {
+      t = ti->second;
+    }
+    if (ti == h->tag_of.end()) h->pk_appended_only = false;   // a new tag: new reduced rows
+    h->pk_dirty = true;
+    h->pk_obs_cap.push_back(c);
+    h->pk_obs_tag.push_back(t);
+    h->pk_corners.insert(h->pk_corners.end(), corners, corners + 8);
+    h->pk_loss_kind.push_back((unsigned char)kind);
+    h->pk_loss_a.push_back(kind == ARSLAM_LOSS_NONE ? 0.0 : a);
+  });
+}
+
+int arslam_lm_set_parameter_block_constant(arslam_lm *h, double *block) {
+  if (!h || !block) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    fail_if(block != h->camera_ptr && !h->cap_of.count(block) && !h->tag_of.count(block),
+            ARSLAM_E_INVALID_ARG, "parameter block is not part of the problem");
+    if (h->constant.insert(block).second) h->pk_dirty = true, h->pk_appended_only = false;
+  });
+}
+
+int arslam_lm_set_parameter_block_variable(arslam_lm *h, double *block) {
+  if (!h || !block) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    if (h->constant.erase(block)) h->pk_dirty = true, h->pk_appended_only = false;
+  });
+}
+
+int arslam_lm_num_residual_blocks(const arslam_lm *h) {
+  return h ? (int)h->pk_obs_cap.size() : 0;
+}
+
+int arslam_lm_solve(arslam_lm *h, arslam_lm_summary *summary) {
+  if (!h || !summary) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    std::memset(summary, 0, sizeof(*summary));
+    if (h->pk_obs_cap.empty()) {   // empty problem: nothing to do (Ceres returns immediately)
+      summary->termination = ARSLAM_CONVERGENCE;
+      return;
+    }
+    const double t_stage = now_s();
+    const int nc = (int)h->cap_ptrs.size(), nt = (int)h->tag_ptrs.size();
+    std::vector<double> cam(h->camera_ptr, h->camera_ptr + 3), cap(6L * nc), tag(6L * nt);
+    std::vector<unsigned char> cc(nc), tc(nt);
+    for (int c = 0; c < nc; ++c) {
+      std::memcpy(&cap[6L * c], h->cap_ptrs[c], 6 * sizeof(double));
+      cc[c] = h->constant.count(h->cap_ptrs[c]) ? 1 : 0;
+    }
+    for (int t = 0; t < nt; ++t) {
+      std::memcpy(&tag[6L * t], h->tag_ptrs[t], 6 * sizeof(double));
+      tc[t] = h->constant.count(h->tag_ptrs[t]) ? 1 : 0;
+    }
+    arslam_soa_problem p{};
+    p.n_cap = nc; p.n_tag = nt; p.n_obs = (int)h->pk_obs_cap.size();
+    p.camera = cam.data(); p.cap = cap.data(); p.tag = tag.data();
+    p.obs_cap = h->pk_obs_cap.data(); p.obs_tag = h->pk_obs_tag.data();
+    p.corners = h->pk_corners.data();
+    const arslam::ObsLoss pk_loss{h->pk_loss_kind.data(), h->pk_loss_a.data()};   // (one per block, beside pk_corners)
+    p.camera_const = h->constant.count(h->camera_ptr) ? 1 : 0;
+    p.cap_const = cc.data(); p.tag_const = tc.data();
+    struct StageGuard {   // (the staging arrays go out of scope; the device problem stays)
+      arslam_lm *h;
+      ~StageGuard() { h->pk_stage = nullptr; h->soa = arslam_soa_problem{}; h->reuse_order = false; }
+    } stage_guard{h};
+    if (h->loaded && h->pk_loaded && !h->pk_dirty) {
+      h->reload_values(&p);   // same problem, new values: no host rebuild, no re-upload of observations
+    } else if (h->loaded && h->pk_loaded && h->pk_appended_only && h->try_append(&p, pk_loss)) {
+      h->pk_dirty = false;    // appended residual blocks within the loaded tile pattern: layout and plan kept
+    } else {
+      h->reuse_order = h->pk_loaded;   // a grown pointer-keyed problem (not the first load)
+      h->load(&p, pk_loss);
+      h->reuse_order = false;
+      h->pk_loaded = true;
+      h->pk_dirty = false;
+    }
+    if (h->env.setup_profile) std::fprintf(stderr, "arslam stage+setup %.3f ms\n", 1e3 * (now_s() - t_stage));
+    h->pk_stage = &p;
+    // the final write_back also writes the caller's blocks (Ceres writes parameters back;
+    // every iteration under update_state_every_iteration)
+    h->solve(summary);
+  });
+}
+
+int arslam_lm_reset(arslam_lm *h) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    h->camera_ptr = nullptr;
+    h->cap_of.clear(); h->tag_of.clear();
+    h->cap_ptrs.clear(); h->tag_ptrs.clear();
+    h->pk_obs_cap.clear(); h->pk_obs_tag.clear(); h->pk_corners.clear();
+    h->pk_loss_kind.clear(); h->pk_loss_a.clear();   // (the default loss stays: it is the handle's, not the problem's)
+    h->constant.clear();
+    h->loaded = false;
+    h->pk_dirty = true;
+    h->pk_loaded = false;
+    h->prev_tag_row.clear();
+    h->prev_mx_tag_row.clear();
+    h->prev_mx_cap_row.clear();
+  });
+}
+
+int arslam_lm_load_soa(arslam_lm *h, const arslam_soa_problem *p) {
+  return arslam_lm_load_soa_loss(h, p, nullptr, nullptr);
+}
+
+int arslam_lm_load_soa_loss(arslam_lm *h, const arslam_soa_problem *p, const unsigned char *obs_loss_kind,
+                            const double *obs_loss_a) {
+  if (!h || !p || (obs_loss_kind == nullptr) != (obs_loss_a == nullptr)) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    fail_if(p->n_obs < 0, ARSLAM_E_INVALID_ARG, "negative sizes");   // (before n_obs sizes anything here)
+    if (obs_loss_kind)
+      for (int b = 0; b < p->n_obs; ++b)
+        fail_if(!arslam::loss_valid(obs_loss_kind[b], obs_loss_a[b]), ARSLAM_E_INVALID_ARG,
+                "obs_loss: kind must be ARSLAM_LOSS_NONE, _HUBER, _SOFT_L_ONE or _CAUCHY, its scale finite and > 0");
+    h->pk_loaded = false;
+    h->pk_dirty = true;
+    h->reuse_order = false;   // a bulk load never reuses a pointer-keyed problem's order
+    h->prev_tag_row.clear();
+    // (the caller's arrays are read during the load only)
+    h->load(p, obs_loss_kind ? arslam::ObsLoss{obs_loss_kind, obs_loss_a} : h->default_obs_loss(p->n_obs));
+  });
+}
+
+int arslam_lm_solve_loaded(arslam_lm *h, arslam_lm_summary *summary) {
+  if (!h || !summary) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    fail_if(h->pk_loaded, ARSLAM_E_STATE, "no problem loaded by arslam_lm_load_soa");
+    h->solve(summary);
+  });
+}
+
+int arslam_lm_solve_soa(arslam_soa_problem *p, const arslam_lm_options *opt,
+                        arslam_lm_summary *summary) {
+  if (!p || !summary) return ARSLAM_E_INVALID_ARG;
+  arslam_lm *h = nullptr;
+  int rc = arslam_lm_create(&h, opt);
+  if (rc) return rc;
+  rc = guarded([&] {
+    h->load(p, arslam::ObsLoss{});   // (a handle of its own: no default loss to apply)
+    h->solve(summary);
+  });
+  arslam_lm_destroy(h);
+  return rc;
+}
+
+int arslam_lm_covariance(arslam_lm *h, double *cov_cap, double *cov_tag, double *var_f, int *cap_status,
+                         int *tag_status, arslam_lm_cov_info *info) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    h->covariance();
+    if (cov_cap && !h->cov_cap.empty()) std::memcpy(cov_cap, h->cov_cap.data(), h->cov_cap.size() * sizeof(double));
+    if (cov_tag && !h->cov_tag.empty()) std::memcpy(cov_tag, h->cov_tag.data(), h->cov_tag.size() * sizeof(double));
+    if (var_f) *var_f = h->cov_var_f;
+    if (cap_status && !h->cov_cap_status.empty())
+      std::memcpy(cap_status, h->cov_cap_status.data(), h->cov_cap_status.size() * sizeof(int));
+    if (tag_status && !h->cov_tag_status.empty())
+      std::memcpy(tag_status, h->cov_tag_status.data(), h->cov_tag_status.size() * sizeof(int));
+    if (info) *info = h->cov_info;
+  });
+}
+
+int arslam_lm_covariance_block(arslam_lm *h, const double *block, double *cov, int *status) {
+  if (!h || !block || !cov) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    double *key = const_cast<double *>(block);
+    const auto ci = h->cap_of.find(key);
+    const auto ti = h->tag_of.find(key);
+    fail_if(key != h->camera_ptr && ci == h->cap_of.end() && ti == h->tag_of.end(), ARSLAM_E_INVALID_ARG,
+            "parameter block is not part of the problem");
+    fail_if(!h->pk_loaded || h->pk_dirty, ARSLAM_E_STATE,
+            "covariance_block: no completed arslam_lm_solve of the problem as it stands");
+    if (!h->cov_valid) h->covariance();
+    if (key == h->camera_ptr) {
+      std::fill(cov, cov + 9, 0.0);
+      cov[0] = h->cov_var_f;
+      const bool ok = h->cov_var_f >= 0.0;
+      if (!ok) std::fill(cov, cov + 9, -1.0);
+      if (status)
+        *status = ok ? ARSLAM_COV_OK
+                     : h->cov_info.status == ARSLAM_COV_RANK_DEFICIENT && !h->constant.count(key) ? ARSLAM_COV_RANK_DEFICIENT
+                                                                                                   : ARSLAM_COV_UNAVAILABLE;
+      return;
+    }
+    const bool is_cap = ci != h->cap_of.end();
+    const int i = is_cap ? ci->second : ti->second;
+    const std::vector<double> &c = is_cap ? h->cov_cap : h->cov_tag;
+    const std::vector<int> &st = is_cap ? h->cov_cap_status : h->cov_tag_status;
+    fail_if((size_t)i >= st.size(), ARSLAM_E_STATE, "covariance_block: the block is not part of the solved problem");
+    std::memcpy(cov, c.data() + 36L * i, 36 * sizeof(double));
+    if (status) *status = st[i];
+  });
+}
+
+int arslam_lm_debug_reduced_rows(arslam_lm *h, int *cap_row, int *tag_row, int *cam_row) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    fail_if(!h->loaded || h->multi() || h->elim_used == ARSLAM_ELIM_MIXED, ARSLAM_E_STATE,
+            "reduced_rows: a one-rank problem loaded with capture or tag elimination");
+    const bool swapped = h->elim_used == ARSLAM_ELIM_TAGS;
+    // (the device problem's e-blocks nc, f-blocks nt; no reduced system: the layout has no rows)
+    int *e_row = swapped ? tag_row : cap_row, *f_row = swapped ? cap_row : tag_row;
+    for (int c = 0; c < h->nc && e_row; ++c) e_row[c] = -1;
+    for (int t = 0; t < h->nt && f_row; ++t) f_row[t] = (size_t)t < h->lay.tag_row.size() ? h->lay.tag_row[t] : -1;
+    if (cam_row) *cam_row = h->has_f ? h->P.cam_row : -1;
+  });
+}
+
+int arslam_comm_unique_id(unsigned char id[ARSLAM_COMM_ID_BYTES]) {
+  if (!id) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    static_assert(sizeof(ncclUniqueId) <= ARSLAM_COMM_ID_BYTES, "id size");
+    ncclUniqueId u;
+    NCCL_CHECK(ncclGetUniqueId(&u));
+    std::memset(id, 0, ARSLAM_COMM_ID_BYTES);
+    std::memcpy(id, &u, sizeof(u));
+  });
+}
+
+int arslam_lm_set_comm_callback(arslam_lm *h, int rank, int nranks, arslam_allreduce_fn fn, void *ctx) {
+  if (!h || nranks < 1 || rank < 0 || rank >= nranks || ((nranks > 1 || h->force_multi) && !fn))
+    return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    if (h->comm) { (void)ncclCommDestroy(h->comm); h->comm = nullptr; }
+    h->rank = rank;
+    h->nranks = nranks;
+    h->comm_cb = h->multi() ? fn : nullptr;
+    h->comm_cb_ctx = ctx;
+    h->loaded = false;
+    h->pk_dirty = true;
+  });
+}
+
+int arslam_lm_set_comm(arslam_lm *h, int rank, int nranks, const unsigned char id[ARSLAM_COMM_ID_BYTES]) {
+  if (!h || !id || nranks < 1 || rank < 0 || rank >= nranks) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    h->ensure_stream();
+    if (h->comm) { (void)ncclCommDestroy(h->comm); h->comm = nullptr; }
+    h->comm_cb = nullptr;
+    h->rank = rank;
+    h->nranks = nranks;
+    h->loaded = false;
+    h->pk_dirty = true;
+    if (h->multi()) {   // (one rank only under arslam_debug_force_multirank)
+      ncclUniqueId u;
+      std::memcpy(&u, id, sizeof(u));
+      NCCL_CHECK(ncclCommInitRank(&h->comm, nranks, u, rank));
+    }
+  });
+}
+
+int arslam_lm_owned_captures(const arslam_lm *h, int *out, int cap, int *n) {
+  if (!h || !n || (cap > 0 && !out)) return ARSLAM_E_INVALID_ARG;
+  if (!h->loaded) return ARSLAM_E_STATE;
+  const int k = h->multi() ? (int)h->own_caps.size() : h->nc_user;   // (one rank: every capture)
+  for (int i = 0; i < k && i < cap; ++i) out[i] = h->multi() ? h->own_caps[i] : i;
+  *n = k;
+  return ARSLAM_OK;
+}
+
+int arslam_device_count(void) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+  return n;
+}
+
+int arslam_lm_set_iteration_callback(arslam_lm *h, arslam_iteration_callback fn, void *ctx) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  h->iter_cb = fn;
+  h->iter_cb_ctx = ctx;
+  return ARSLAM_OK;
+}
+
+int arslam_lm_debug_force_indefinite(arslam_lm *h, unsigned long long step_mask) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  h->dbg_indefinite_mask = step_mask;
+  return ARSLAM_OK;
+}
+
+int arslam_lm_debug_force_multirank(arslam_lm *h, int on) {
+  if (!h || (on != 0 && on != 1)) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    if (h->comm) { (void)ncclCommDestroy(h->comm); h->comm = nullptr; }
+    h->comm_cb = nullptr;
+    h->rank = 0;
+    h->nranks = 1;
+    h->force_multi = on != 0;
+    h->loaded = false;
+    h->pk_dirty = true;
+  });
+}
+
+int arslam_lm_debug_break_dependency(arslam_lm *h, long ticket, long *broken) {
+  if (!h || ticket < 0) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    fail_if(!h->loaded || !h->has_f || h->opt.factor_executor != 1, ARSLAM_E_STATE,
+            "break_dependency needs a loaded problem on the persistent executor");
+    arslam::LltPlan &pl = h->plan;
+    long t = ticket;
+    while (t < pl.n_dag_tasks && pl.h_dag_wait_off[t] == pl.h_dag_wait_off[t + 1]) ++t;
+    fail_if(t >= pl.n_dag_tasks, ARSLAM_E_INVALID_ARG, "no task at or after this ticket waits on anything");
+    const int w = pl.h_dag_wait_off[t];
+    h->restore_patched_wait();
+    pl.h_dag_waits[w].y += 1 << 28;   // a count no task ever reaches (for the next solve only)
+    h->dbg_patched_wait = w;
+    HIP_CHECK(hipMemcpyAsync(pl.dag_waits + w, &pl.h_dag_waits[w], sizeof(int2), hipMemcpyHostToDevice,
+                             h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (broken) *broken = t;
+  });
+}
+
+int arslam_lm_debug_tag_pair_tile(arslam_lm *h, const double *tag_a, const double *tag_b, int *status) {
+  if (!h || !tag_a || !tag_b || !status) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    fail_if(!h->loaded || h->multi() || h->elim_used != ARSLAM_ELIM_CAPTURES || !h->has_f, ARSLAM_E_STATE,
+            "tag_pair_tile needs a pointer-keyed problem loaded with capture elimination on one rank");
+    const auto ia = h->tag_of.find(const_cast<double *>(tag_a)), ib = h->tag_of.find(const_cast<double *>(tag_b));
+    *status = -1;
+    if (ia == h->tag_of.end() || ib == h->tag_of.end()) return;
+    const int ra = h->lay.tag_row[ia->second], rb = h->lay.tag_row[ib->second];
+    if (ra < 0 || rb < 0) return;
+    const int T = h->lay.T;
+    int st = 2;
+    for (int x : {ra, ra + 5})
+      for (int y : {rb, rb + 5}) {
+        int ti = x / 64, tj = y / 64;
+        if (ti < tj) std::swap(ti, tj);
+        // (the tiles assembled at the load are numbered first, the fill after them)
+        const int id = h->plan.h_tile_id[(size_t)ti * T + tj];
+        st = std::min(st, id < 0 ? 0 : (id < h->plan.n_assembled ? 2 : 1));
+      }
+    *status = st;
+  });
+}
+
+const char *arslam_lm_last_error(void) { return g_last_error.c_str(); }
+
+#ifndef ARSLAM_BUILD_ID
+#define ARSLAM_BUILD_ID "unknown"
+#endif
+// the build's commit and source digest (ar_slam_amd/build.py build_id): every
+// A/B line and bench line names the library it measured
+const char *arslam_lm_version(void) { return "arslam_lm 0.2 (gfx950, fp64) build " ARSLAM_BUILD_ID; }
+
+}  // extern "C"

@@ -1,0 +1,555 @@
+// lm_handle.h -- the handle behind the C-ABI of include/arslam_lm.h: its
+// buffers and timers, and `struct arslam_lm` with every member.  The methods'
+// bodies live in lm_load.hip (load, upload, append, value reload), lm_solve.hip
+// (the trust-region loop, its stages, the linearization), lm_covariance.hip and
+// lm_capi.hip (the extern "C" entry points); only those include this header.
+#pragma once
+#include "host_threads.h"
+#include "lm_internal.h"
+#include "loss.h"
+#include "arslam_lm.h"
+#include "arslam_lm_debug.h"
+
+#include <rccl/rccl.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cfloat>
+#include <chrono>
+#include <cmath>
+#include <cstddef>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <stdexcept>
+#include <string>
+#include <unordered_map>
+#include <thread>
+#include <unordered_set>
+#include <vector>
+
+namespace arslam {
+namespace lmh {   // the LM handle's host helpers
+
+using Error = arslam::ApiError;
+
+#define HIP_CHECK(expr)                                                                      \
+  do {                                                                                       \
+    hipError_t _e = (expr);                                                                  \
+    if (_e != hipSuccess)                                                                    \
+      throw Error(_e == hipErrorOutOfMemory ? ARSLAM_E_OUT_OF_MEMORY : ARSLAM_E_HIP,         \
+                  std::string(#expr) + ": " + hipGetErrorString(_e));                       \
+  } while (0)
+
+#define NCCL_CHECK(expr)                                                                     \
+  do {                                                                                       \
+    ncclResult_t _r = (expr);                                                                \
+    if (_r != ncclSuccess)                                                                   \
+      throw Error(ARSLAM_E_COMM, std::string(#expr) + ": " + ncclGetErrorString(_r));       \
+  } while (0)
+
+inline void fail_if(bool cond, int code, const std::string &msg) {
+  if (cond) throw Error(code, msg);
+}
+
+inline double now_s() {
+  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// The debug switches of the load and solve paths, read once per process (at
+// the first handle's creation), never inside a loop.
+struct DebugEnv {
+  const char *dag_trace = std::getenv("ARSLAM_DAG_TRACE");   // dump one k_factor_dag task timeline to this path
+  int dag_trace_skip = std::getenv("ARSLAM_DAG_TRACE_SKIP") ? std::atoi(std::getenv("ARSLAM_DAG_TRACE_SKIP")) : 0;
+  bool setup_profile = std::getenv("ARSLAM_SETUP_PROFILE") != nullptr;    // setup phases to stderr
+  bool write_back_dma = std::getenv("ARSLAM_WRITE_BACK_DMA") != nullptr;   // A/B: the copy engine
+};
+inline const DebugEnv &debug_env() {
+  static const DebugEnv e;
+  return e;
+}
+
+// decode the persistent executors' negative flags (lm_solve.hip); for a
+// timed-out wait of k_factor_dag also what its fault record says
+std::string executor_fault_message(int code, int rank, int iteration, const arslam::LltPlan &plan, hipStream_t s);
+
+// Device buffer; grow-only, so reloading a problem of the same or a smaller
+// size (every optimize() of an incremental solve) does no hipMalloc/hipFree.
+template <class T>
+struct DevBuf {
+  T *p = nullptr;
+  size_t n = 0, cap = 0;
+  void alloc(size_t count) {   // grows by half again (a growing incremental problem reallocates rarely)
+    n = count;
+    if (count <= cap) return;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    const size_t want = cap == 0 && count <= 16 ? count : count + count / 2;
+    HIP_CHECK(hipMalloc(&p, want * sizeof(T)));
+    cap = want;
+  }
+  void upload(const T *h, size_t count, hipStream_t s) {
+    if (count) HIP_CHECK(hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, s));
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    n = cap = 0;
+  }
+  ~DevBuf() { release(); }
+};
+
+// page-locked host words: a D2H copy into them stays asynchronous
+struct PinnedBuf {
+  double *p = nullptr;
+  size_t cap = 0;
+  void alloc(size_t count) {   // grows only (by half again: page-locking is slow); kept across solves
+    if (count <= cap) return;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+    const size_t want = count + count / 2;
+    HIP_CHECK(hipHostMalloc(&p, want * sizeof(double), hipHostMallocDefault));
+    cap = want;
+  }
+  ~PinnedBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+};
+
+// The problem's uploaded arrays: one grow-only device allocation, one
+// page-locked host image, one host->device copy per load (instead of a
+// pageable copy and a driver staging pass per array).
+struct UploadArena {
+  char *dev = nullptr, *host = nullptr;
+  size_t dev_cap = 0, host_cap = 0;
+  struct Piece { void **dst; const void *src; size_t bytes, off; };
+  std::vector<Piece> pieces;
+  hipEvent_t copied = nullptr;   // the last commit's transfer has read the host image
+  template <class T>
+  void add(T **dst, const T *src, size_t count) { pieces.push_back({reinterpret_cast<void **>(dst), src, count * sizeof(T), 0}); }
+  // lay the pieces out, copy them into the host image and enqueue the one
+  // transfer; the sources may go out of scope once this returns, the image
+  // stays untouched until the caller's next stream sync
+  void commit(hipStream_t s) {
+    // the previous transfer may still be reading the image (a load with no
+    // reduced system has no stream sync before the next upload)
+    if (copied) HIP_CHECK(hipEventSynchronize(copied));
+    size_t used = 0;
+    for (Piece &p : pieces) {
+      p.off = used;
+      used += (std::max<size_t>(p.bytes, 1) + 255) & ~size_t(255);
+    }
+    if (used > host_cap) {
+      if (host) (void)hipHostFree(host);
+      host = nullptr;
+      host_cap = 0;
+      HIP_CHECK(hipHostMalloc(&host, used + used / 2, hipHostMallocDefault));
+      host_cap = used + used / 2;
+    }
+    if (used > dev_cap) {
+      if (dev) (void)hipFree(dev);
+      dev = nullptr;
+      dev_cap = 0;
+      HIP_CHECK(hipMalloc(&dev, used + used / 2));
+      dev_cap = used + used / 2;
+    }
+    for (Piece &p : pieces) {
+      if (p.bytes) std::memcpy(host + p.off, p.src, p.bytes);
+      *p.dst = dev + p.off;
+    }
+    if (used) {
+      HIP_CHECK(hipMemcpyAsync(dev, host, used, hipMemcpyHostToDevice, s));
+      if (!copied) HIP_CHECK(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
+      HIP_CHECK(hipEventRecord(copied, s));
+    }
+    pieces.clear();
+  }
+  ~UploadArena() {
+    if (copied) (void)hipEventDestroy(copied);
+    if (dev) (void)hipFree(dev);
+    if (host) (void)hipHostFree(host);
+  }
+};
+
+struct Timer {
+  hipEvent_t a = nullptr, b = nullptr;
+  double acc_ms = 0.0;
+  bool pending = false;
+  bool on = true;   // options.phase_timing
+  void init() {
+    if (!a) {
+      // timing only (read after the stream's sync): no system-scope fence at
+      // the record -- its cache writeback and invalidation sat between the
+      // kernels it brackets (~6 us each side of the factorization)
+      HIP_CHECK(hipEventCreateWithFlags(&a, hipEventDisableSystemFence));
+      HIP_CHECK(hipEventCreateWithFlags(&b, hipEventDisableSystemFence));
+    }
+  }
+  void start(hipStream_t s) {
+    if (on) HIP_CHECK(hipEventRecord(a, s));
+  }
+  void stop(hipStream_t s) {
+    if (!on) return;
+    HIP_CHECK(hipEventRecord(b, s));
+    pending = true;
+  }
+  void collect() {  // call after the stream was synchronized (or its flag seen: b may still be pending)
+    if (!pending) return;
+    float ms = 0.f;
+    HIP_CHECK(hipEventSynchronize(b));
+    HIP_CHECK(hipEventElapsedTime(&ms, a, b));
+    acc_ms += ms;
+    pending = false;
+  }
+  void destroy() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+    a = b = nullptr;
+  }
+};
+
+enum { PH_LIN, PH_SCHUR, PH_CHOL, PH_SOLVE, PH_BACK, PH_COST, PH_FAC0, PH_FAC1, PH_N };
+
+}  // namespace lmh
+}  // namespace arslam
+using namespace arslam::lmh;   // (this header is private to the lm_*.hip files)
+
+struct arslam_lm {
+  arslam_lm_options opt;
+
+  // ---- pointer-keyed problem (Ceres API mirror) ----
+  double *camera_ptr = nullptr;
+  std::unordered_map<double *, int> cap_of, tag_of;
+  std::vector<double *> cap_ptrs, tag_ptrs;
+  std::vector<int> pk_obs_cap, pk_obs_tag;
+  std::vector<double> pk_corners;
+  // each residual block's loss (arslam_lm_add_residual_block_loss; the default
+  // loss for arslam_lm_add_residual_block).  Blocks are only ever appended, or
+  // all dropped by arslam_lm_reset (a full load follows), so a resident
+  // problem's losses never go stale under the values-only path, and the
+  // append path uploads the grown arrays with the grown problem.
+  std::vector<unsigned char> pk_loss_kind;
+  std::vector<double> pk_loss_a;
+  int def_loss_kind = ARSLAM_LOSS_NONE;   // arslam_lm_set_loss
+  double def_loss_a = 0.0;
+  std::vector<unsigned char> soa_loss_kind;   // arslam_lm_load_soa's default loss, per observation
+  std::vector<double> soa_loss_a;
+  // the default loss for each of n_obs observations (null arrays: NONE)
+  arslam::ObsLoss default_obs_loss(int n_obs) {
+    if (def_loss_kind == ARSLAM_LOSS_NONE || n_obs <= 0) return arslam::ObsLoss{};
+    soa_loss_kind.assign(n_obs, (unsigned char)def_loss_kind);
+    soa_loss_a.assign(n_obs, def_loss_a);
+    return arslam::ObsLoss{soa_loss_kind.data(), soa_loss_a.data()};
+  }
+  std::unordered_set<double *> constant;
+  // The pointer-keyed structure (blocks, residuals, constants) changed since
+  // the last load: arslam_lm_solve reloads; otherwise it reuses the resident
+  // problem, plan and buffers and uploads only the parameter values.
+  bool pk_dirty = true;
+
+  // ---- loaded problem ----
+  bool loaded = false;
+  arslam_soa_problem soa{};
+  int nc = 0, nt = 0, nb = 0;
+  long n = 0, nR = 0, N = 0;
+  bool has_f = false;
+  std::vector<unsigned char> slot_free;
+  std::vector<double> x0;   // initial slots
+  long nb_global = 0;       // observations over all ranks
+  double setup_s = 0.0;     // host structure + ordering + plan + upload of the last load (or value reload)
+  double setup_phase[5] = {0, 0, 0, 0, 0};   // the last full load's phases (summary.setup_phase_s)
+  double comm_bytes = 0.0;  // bytes this rank all-reduced (RCCL or the host callback) since the count was reset
+  long comm_calls = 0;      // ... and the collectives that carried them
+  arslam::DevProblem P{};
+  hipStream_t stream = nullptr;
+  int device = 0;
+
+  // uploaded arrays (pointers into `upload`, re-laid out by every load)
+  UploadArena upload;
+  int *u_cap_start = nullptr, *u_obs_tag = nullptr, *u_obs_lblk = nullptr, *u_cap_blk_start = nullptr,
+      *u_blk_tag = nullptr, *u_tag_start = nullptr, *u_obs_tpos = nullptr, *u_tag_row = nullptr,
+      *u_row_slot = nullptr, *u_fslot_row = nullptr, *u_dest_start = nullptr, *u_big_caps = nullptr;
+  unsigned char *u_f_own = nullptr;
+  unsigned char *u_cap_kind = nullptr;   // ARSLAM_ELIM_MIXED: DevProblem::cap_kind, f_alias
+  int *u_f_alias = nullptr;
+  std::vector<unsigned char> f_own;   // several ranks: DevProblem::f_own
+  std::vector<int> big_caps;   // captures with more than kSchurMfmaBlocks distinct tags (k_schur's second launch)
+  std::vector<int> chunk_caps;   // captures with more than kObsChunk observations (the chunked launches)
+  int *u_chunk_caps = nullptr;
+  unsigned char *u_obs_active = nullptr, *u_slot_free = nullptr;
+  double *u_corners = nullptr, *u_x0 = nullptr;
+  unsigned char *u_loss_kind = nullptr;   // DevProblem::obs_loss_kind, obs_loss_a (a problem with losses)
+  double *u_loss_a = nullptr;
+  long *u_cap_off = nullptr;
+  int2 *u_dest_row = nullptr;
+  int4 *u_gather_items = nullptr, *u_gather_splits = nullptr;
+  arslam::SchurContrib *u_contrib = nullptr;
+  // One rank, persistent executor: the fill tiles (numbered after the
+  // assembled ones) are never cleared -- their first update stores.  n_clear:
+  // the tiles k_schur clears (the assembled ones; every tile when an appended
+  // problem's gather writes into a fill tile: then no first-update store)
+  long n_clear = 0;
+  DevBuf<double> d_xa, d_xb, d_xbest, d_g, d_colnorm, d_scale, d_diag;
+  DevBuf<double> d_obs_tg, d_parts, d_fparts, d_red, d_S, d_z, d_yF;
+  // the reduced system's tiles: Sp = d_S.p + s_pre.  Several ranks: the top
+  // tags' linearization sums (top_tail_len doubles) ride in the prefix, just in
+  // front of the top tiles, in the step's one bulk all-reduce
+  double *Sp = nullptr;
+  long s_pre = 0;
+  int *u_top_slots = nullptr;
+  int n_top_slots = 0;
+  long top_tail_len() const { return 2L * n_top_slots + 2; }
+  double *d_norms_p = nullptr;   // inside d_red
+  DevBuf<int> d_flag;
+  DevBuf<double> d_slab, d_jrows, d_cap_ui;
+  DevBuf<double> d_gather_part;
+  arslam::LltPlan plan;
+  // x: the current point, xc: the candidate, xbest: the best point so far --
+  // three of d_xa / d_xb / d_xbest by pointer, xc never aliasing the other two
+  double *x = nullptr, *xc = nullptr, *xbest = nullptr;
+  unsigned long long dbg_indefinite_mask = 0;   // arslam_lm_debug_force_indefinite
+  arslam_iteration_callback iter_cb = nullptr;  // arslam_lm_set_iteration_callback
+  void *iter_cb_ctx = nullptr;
+  int n_fparts = 0;
+
+  Timer timers[PH_N];
+  arslam::LaunchTiming upd_timing;
+  std::vector<hipEvent_t> upd_events;
+  double dom_ms = 0.0, dom_flops = 0.0;
+  double scalar_flops = 0.0;   // scalar Cholesky flops of the reduced system's real rows (ReducedLayout)
+  long dom_launches = 0;
+
+  void timing_begin();
+  void timing_collect();   // after a stream synchronize
+
+  // ---- multi-GPU ----
+  int rank = 0, nranks = 1;
+  ncclComm_t comm = nullptr;
+  // debug (arslam_debug_force_multirank): take the multi-rank path -- the
+  // split, the two-phase factorization and every collective -- with one rank,
+  // so its RCCL calls run on a one-GPU box
+  bool force_multi = false;
+  bool multi() const { return nranks > 1 || force_multi; }
+
+  ~arslam_lm();
+
+  // host-callback transport (arslam_lm_set_comm_callback): stage through host memory
+  arslam_allreduce_fn comm_cb = nullptr;
+  void *comm_cb_ctx = nullptr;
+  std::vector<unsigned char> comm_stage;
+
+  // In-place all-reduce of a device buffer over the ranks (RCCL, or the
+  // caller's callback).  Every rank issues the same sequence of calls.
+  void allreduce_any(void *buf, size_t count, int dtype, int op);
+  void allreduce(double *buf, size_t count, int op) { allreduce_any(buf, count, ARSLAM_DT_F64, op); }
+
+  // Every rank derives the split itself (no structure is exchanged), so ranks
+  // that disagree -- a rank-dependent environment, a different problem --
+  // would issue mismatched collectives and hang.  One all-reduce (MAX of h and
+  // of -h, 52-bit hash of the owner maps) proves they agree before the first step.
+  DevBuf<double> d_split_hash;
+  void check_same_split(const arslam::RankSplit &sp);
+
+  int dag_workgroups = 512;
+  const DebugEnv &env = debug_env();
+
+  int cus_device = -1, cus = 0;   // the CU count, queried once per device
+  // The thread and options device the handle's stream was last made ready
+  // for: a later load from the same thread with the same options, while the
+  // thread's current device is still the handle's, makes one hipGetDevice (a
+  // thread-local read) and nothing else.  The current-device check matters
+  // when one thread drives handles on several devices: another handle's load
+  // may have switched it, and this handle's allocations must land on its own
+  // device.
+  std::thread::id ready_thread{};
+  int ready_opt_device = -2;
+  void ensure_stream();
+
+  // (in_loss, here and in try_append: the losses of p's observations, in p's
+  // order, null arrays for none; they go beside the corners into every
+  // host_problem call of the load)
+  void load(const arslam_soa_problem *p, const arslam::ObsLoss &in_loss);
+  // load()'s parts: the e-block side for Ceres' set cs; several ranks: this
+  // rank's problem h, the whole problem's layout L, this rank's column classes
+  int choose_side(const arslam::SchurSide &cs);
+  void local_rank_problem(const arslam_soa_problem *p, const arslam::ObsLoss &in_loss, bool can_reuse,
+                          arslam::HostProblem &h, arslam::ReducedLayout &L, std::vector<int> &col_class);
+  // (extend_from >= 0: captures [extend_from, nc) were appended to the loaded
+  // problem, the others unchanged: the gather plan is extended, not rebuilt)
+  void upload_problem(const arslam::HostProblem &h, const arslam::ReducedLayout &L, int extend_from = -1);
+  void alloc_solve_buffers();   // (upload_problem's: after the gather plan and the tile plan)
+  arslam::SchurGather sg;   // the loaded problem's Schur gather plan
+  bool sg_ready = false;    // load(): sg was built beside the tile plan (upload_problem keeps it)
+  // the append path (lm_load.hip): one entry, a front end per eliminated side, shared checks
+  bool try_append(const arslam_soa_problem *p, const arslam::ObsLoss &in_loss);
+  bool append_as_captures(const arslam_soa_problem *p);
+  bool append_as_mixed(const arslam_soa_problem *p, arslam::MixedProblem &m);
+  bool same_reduced_rows(const arslam::HostProblem &h) const;
+  bool groups_fit_plan(const arslam::HostProblem &h, const std::vector<int> &groups) const;
+  bool order_outgrown(const arslam::HostProblem &h, const std::vector<int> &groups);
+  arslam::ReducedLayout lay;      // the loaded layout (one rank), kept for try_append
+  bool pk_appended_only = false;  // since the last load only residual blocks of known tags were added
+  int setup_kind = ARSLAM_SETUP_LOAD;
+  int elim_used = ARSLAM_ELIM_CAPTURES;   // the side load() eliminates (the device problem is role-swapped for TAGS)
+  arslam::MixedProblem mx;                // ARSLAM_ELIM_MIXED: the regrouped device problem (host_structure.h)
+  int ceres_e_cap = 0, ceres_e_tag = 0;   // Ceres 2.0's e-block set of the loaded problem, by kind
+  void reload_values(const arslam_soa_problem *p);
+  bool pk_loaded = false;   // the resident problem came from the pointer-keyed API
+  // several ranks: the whole problem's capture count, this rank's captures
+  // (ascending; the loaded problem's capture c is own_caps[c]) and its local arrays
+  int nc_full = 0;
+  int nc_user = 0;   // the caller's capture count (the device problem's "captures" are tags or groups under TAGS / MIXED)
+  std::vector<int> own_caps;
+  std::vector<double> loc_cap, loc_corners;
+  std::vector<int> loc_obs_cap, loc_obs_tag;
+  std::vector<unsigned char> loc_cap_const;
+  std::vector<unsigned char> loc_loss_kind;   // this rank's observations' losses
+  std::vector<double> loc_loss_a;
+  double split_top_work = 0.0, split_max_rank_work = 0.0, split_total_work = 0.0;
+  int split_active = 1;   // ranks owning subtrees (RankSplit::n_active)
+  // co-visibility of the free tags (a bit matrix, directed edge count as
+  // ReducedLayout::n_edges), kept up to date through appends: an appended
+  // problem whose graph outgrew the one its elimination order was computed
+  // for by more than a tenth reloads with a fresh order (a stale order on the
+  // incremental cfg2 flow: 18 elimination-tree levels and 358 us per
+  // factorization against 10 and 217 us fresh)
+  std::vector<uint64_t> covis;
+  long covis_nt = 0, covis_edges = 0;
+  void covis_build(const arslam::HostProblem &h, const arslam::ReducedLayout &L);
+  void covis_add(const arslam::HostProblem &h, const arslam::ReducedLayout &L, int c);
+  bool reuse_order = false;  // load(): keep the previous tag order when the free tags are unchanged
+  std::vector<int> prev_tag_row;
+  // ARSLAM_ELIM_MIXED: the rows of the last layout by original block (tag /
+  // capture id, -1 off the reduced side), for a reload whose re-chosen set
+  // renumbers the reduced blocks (reduced_layout by identity)
+  std::vector<int> prev_mx_tag_row, prev_mx_cap_row;
+  int prev_ordering = -1, prev_skip = -1;
+  long prev_order_edges = 0;
+  // the capture count the order was computed at: nested dissection cuts along
+  // the tags' positions, which the first solves of an incremental flow only
+  // roughly know, so a grown problem (by a quarter) gets a fresh order even if
+  // its co-visibility graph barely changed (incremental cfg2: an order kept
+  // from the first load gave 18 elimination-tree levels, a fresh one 10)
+  int prev_order_nc = 0;
+  bool last_order_reused = false;   // summary.order_reused
+  int prev_order_height = 0;   // tile elimination-tree height of the layout the order was computed for
+  static int etree_height(const arslam::ReducedLayout &L);
+  void linearize(double *x_cost, double *fixed_cost, double *gmax, double *gnorm, double *xnorm);
+  // linearize split at the host read: enqueue (results copied to h_lin), collect after a sync
+  void linearize_launch();
+  void linearize_collect(double *x_cost, double *fixed_cost, double *gmax, double *gnorm, double *xnorm);
+  // Several ranks: a linearization's sums over the ranks are not collectives
+  // of their own.  Its tag slots' gradient and column norms and the camera's
+  // f partials (lin_xpending) ride in front of the top tiles in the next
+  // step's bulk all-reduce (or one packed all-reduce, complete_pending_lin,
+  // when no step follows); its cost and norms (norms_pending) ride with the
+  // step's scalars (exchange_scalars; exchange_norms when no step follows).
+  bool lin_xpending = false, norms_pending = false;
+  DevBuf<double> d_lx, d_ag;   // the packed exchange; the all-gathered scalars
+  static constexpr int kLinSave = 16 + 8 + 6 * arslam::kNormBlocks;   // d_red[kLinSave..+1]: the linearization's cost, fixed
+  void complete_pending_lin();
+  void lin_norms();   // k_slot_norms once the linearization's sums are final
+  void exchange_scalars(arslam::AgFields fl, arslam::HostOut *ho = nullptr);   // (+ the pending norms), into d_red
+  void exchange_norms() {
+    if (norms_pending) exchange_scalars(arslam::AgFields{});
+  }
+  PinnedBuf h_lin;   // [0..3] cost, fixed, g_f, col_f; [16..21] slot norms; [16 + kHostSeq] lin_seq
+  double lin_seq = 0.0;   // (one rank) the last linearization's sequence number
+  void lin_sync() {   // the linearization's host words (one rank: its flag; several: after the copies)
+    if (!multi() && lin_seq > 0.0) flag_sync(h_lin.p + 16 + arslam::kHostSeq, lin_seq);
+    else spin_sync();
+  }
+  // host LM loop: the Jacobi scale of this solve is set, so each later
+  // linearization also forms the LM diagonal (k_slot_norms) and the step's
+  // executor reset rides in k_schur's launch
+  bool diag_in_lin = false;
+  PinnedBuf h_x;     // [n] parameter download (write_back)
+  PinnedBuf h_step;  // [0..NPART+1] the step's reduced scalars, [NPART+2..4] the factorization flags
+  hipEvent_t ev_sync = nullptr;
+  // Wait for the stream by polling an event: the LM loop's one host round
+  // trip per step, without the blocking-sync wake-up latency.
+  void spin_sync() {
+    if (!ev_sync) HIP_CHECK(hipEventCreateWithFlags(&ev_sync, hipEventDisableTiming));
+    HIP_CHECK(hipEventRecord(ev_sync, stream));
+    hipError_t e;
+    while ((e = hipEventQuery(ev_sync)) == hipErrorNotReady) {
+    }
+    HIP_CHECK(e);
+  }
+  // One rank: the LM loop's host reads wait for the kernel that stores their
+  // page-locked words to store its sequence number last (hout[kHostSeq]),
+  // instead of an event behind it: ~8 against ~13 us per round trip on
+  // MI355X (tools/sync_bench.hip), ~7 round trips per cfg3 solve and ~7,000
+  // in the incremental cfg2 flow.  The stream is queried now and then so a
+  // launch that never stores it (an error) is reported, not waited for.
+  double host_seq = 0.0;
+  DevBuf<int> d_seq_done;   // k_reduce_parts' finished blocks (zero between launches)
+  double next_seq(double *word) {
+    *(volatile double *)word = -1.0;   // (before the launch: the kernel's store lands after it)
+    return host_seq += 1.0;
+  }
+  void flag_sync(const double *word, double seq) {
+    for (long k = 1;; ++k) {
+      if (*(const volatile double *)word == seq) break;
+      if ((k & 4095) == 0) {
+        const hipError_t e = hipStreamQuery(stream);
+        if (e == hipErrorNotReady) continue;
+        HIP_CHECK(e);
+        if (*(const volatile double *)word == seq) break;
+        throw Error(ARSLAM_E_DEVICE, "the stream finished without storing the host sequence word");
+      }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+  }
+  // solve() is the trust-region loop; its stages are plain members (lm_solve.hip)
+  void solve(arslam_lm_summary *s);
+  void begin_solve(arslam_lm_summary *s);
+  // one step's launches: returns the sequence number h_step will hold (solve_index: from 0)
+  double enqueue_step(double radius, bool reuse_diag, int solve_index);
+  bool prepare_step(bool reuse_diag, arslam::ExecReset *er);   // true: the executor reset rides in k_schur (er)
+  // The one place that factors the reduced system Sp of the loaded plan with
+  // opt.factor_executor.  first_store: launch_dense_llt_dag's bound; record:
+  // kernel timing (after timing_begin); radius, force_indefinite: several ranks
+  // only (the top rows' D^2 and the test hook, between the two phases)
+  void factor_reduced(long first_store, bool record, double radius = 0.0, bool force_indefinite = false);
+  void dump_dag_trace(long first_store);   // ARSLAM_DAG_TRACE: a stamped launch and its file
+  void back_substitute(double radius);
+  double reduce_step_scalars();
+  void fill_summary(arslam_lm_summary *s);
+  void write_back(const double *d_src);
+  // the pointer-keyed solve in progress: its (unswapped) staging problem, whose
+  // arrays soa aliases; write_back also scatters them into the caller's blocks
+  const arslam_soa_problem *pk_stage = nullptr;
+  void scatter_to_blocks();
+  // arslam_lm_debug_break_dependency: the patched wait entry, restored after the next solve
+  int dbg_patched_wait = -1;
+  void restore_patched_wait();
+  // multi-rank: does any rank have an iteration callback (agreed once per solve)
+  bool any_iter_cb = false;
+  DevBuf<double> d_cb;
+  int agree_callback(int r);
+
+  // ---- marginal covariances (arslam_lm_covariance) ----
+  // the last solve of the loaded problem: 0 none completed, 1 completed, 2 ended with EVAL_FAILED
+  int solve_state = 0;
+  // everything below is allocated at the first covariance call
+  arslam::SelinvPlan cov_sp;
+  bool cov_sp_ready = false;   // cov_sp is the loaded plan's
+  DevBuf<double> d_cov_Z, d_cov_Q, d_cov_Y, d_cov_R, d_cov_out, d_cov_diag;   // d_cov_out: e-blocks 36 nc | f-blocks 36 nt | var(f)
+  DevBuf<int> d_cov_status;
+  hipEvent_t cov_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  // the kept result, in the caller's block order (arslam_lm_covariance_block serves it)
+  bool cov_valid = false;
+  std::vector<double> cov_cap, cov_tag;
+  std::vector<int> cov_cap_status, cov_tag_status;
+  double cov_var_f = -1.0;
+  arslam_lm_cov_info cov_info{};
+  void covariance();
+  void cov_invalidate() {
+    solve_state = 0;
+    cov_valid = false;
+  }
+};

@@ -1,5 +1,5 @@
 // lm_internal.h -- device problem layout and kernel launch wrappers shared by
-// the LM driver (lm_solver.hip), the per-capture kernels (lm_kernels.hip) and
+// the LM driver (lm_handle.h, lm_load.hip, lm_solve.hip), the per-capture kernels (lm_kernels.hip) and
 // the reduced-system Cholesky (dense_llt.hip).
 //
 // Parameter slots (one contiguous f64 vector, x):

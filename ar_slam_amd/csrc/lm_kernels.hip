@@ -1566,7 +1566,7 @@ __global__ __launch_bounds__(256) void k_slot_norms(long n, long cap_lo, long ca
   }
 }
 
-// ---- multi-rank exchange buffers (lm_solver.hip) ----
+// ---- multi-rank exchange buffers (lm_solve.hip) ----
 // Segments copied into (unpack = 0) or out of (1) one contiguous buffer, so
 // several arrays cross the ranks in one all-reduce.
 __global__ void k_pack(PackSegs sg, double *__restrict__ buf, int unpack) {

@@ -10,7 +10,7 @@
 #include <string>
 
 namespace arslam {
-void set_last_error(const std::string &msg);   // lm_solver.hip
+void set_last_error(const std::string &msg);   // lm_capi.hip
 }
 
 struct arslam_slam {

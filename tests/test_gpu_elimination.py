@@ -23,6 +23,7 @@ import pytest
 from ar_slam_amd import synth
 from gauge import assert_poses_match
 from oracle.schur_ordering import ceres_e_blocks
+from test_gpu_parity import assert_matches_fresh_load
 
 pytestmark = pytest.mark.gpu
 
@@ -184,6 +185,43 @@ def test_pointer_api_under_mixed_elimination(lm):
     assert abs(s1["final_cost"] - s2["final_cost"]) <= 1e-9 * s1["final_cost"]
     np.testing.assert_allclose(c1, c2, rtol=1e-8)
     assert_poses_match(k2, t2, k1, t1, tags=np.arange(g.n_tag), caps=np.arange(g.n_cap))
+
+
+def test_append_under_mixed_that_fell_back_to_captures(lm):
+    """ELIM_MIXED on a graph whose Ceres set is every capture and no tag (six captures that each
+    see the same four tags: a capture's degree is below a tag's, so the greedy independent set
+    takes the captures) loads with the captures eliminated.  A seventh capture on those tags is
+    then appended through the capture form of the append path (setup_kind APPEND) and the solve
+    gives what a fresh handle's load of the grown problem gives."""
+    g = synth.make_graph(7, 2, 2, seed=5, k=4)
+    first = 6
+    loaded = g.obs_cap < first
+    rule = ceres_e_blocks(g.obs_cap[loaded], g.obs_tag[loaded], first, g.n_tag)
+    assert (rule["captures"], rule["tags"]) == (first, 0)
+    camera = g.camera.copy()
+    caps = [g.cap[c].copy() for c in range(g.n_cap)]
+    tags = [g.tag[t].copy() for t in range(g.n_tag)]
+    prob = lm.Problem(elimination=lm.ELIM_MIXED)
+    order = list(np.nonzero(loaded)[0]) + list(np.nonzero(~loaded)[0])
+    for b in order[:int(loaded.sum())]:
+        prob.add_residual_block(g.corners[b], camera, caps[g.obs_cap[b]], tags[g.obs_tag[b]])
+    s1 = prob.solve()
+    assert s1["ceres_e_tags"] == 0
+    assert s1["elimination_used"] == lm.ELIM_CAPTURES
+    assert s1["setup_kind"] == lm.SETUP_LOAD
+    for b in order[int(loaded.sum()):]:
+        prob.add_residual_block(g.corners[b], camera, caps[g.obs_cap[b]], tags[g.obs_tag[b]])
+    start = (camera.copy(), [c.copy() for c in caps], [t.copy() for t in tags])
+    s2 = prob.solve()
+    assert s2["setup_kind"] == lm.SETUP_APPEND, s2["setup_kind"]
+    fresh = lm.Problem(elimination=lm.ELIM_MIXED)
+    cam_f, caps_f, tags_f = start[0].copy(), [c.copy() for c in start[1]], [t.copy() for t in start[2]]
+    for b in order:
+        fresh.add_residual_block(g.corners[b], cam_f, caps_f[g.obs_cap[b]], tags_f[g.obs_tag[b]])
+    s3 = fresh.solve()
+    assert s3["setup_kind"] == lm.SETUP_LOAD
+    assert s3["elimination_used"] == lm.ELIM_CAPTURES
+    assert_matches_fresh_load(s2, camera, s3, cam_f)
 
 
 def test_invalid_elimination_rejected(lm):

@@ -146,6 +146,16 @@ def test_pointer_api_resolve_reuses_the_resident_problem(lm):
     assert s4["setup_kind"] == lm.SETUP_LOAD
 
 
+def assert_matches_fresh_load(s_app, camera_app, s_fresh, camera_fresh):
+    """An appended problem's solve against a fresh load of the same blocks from the same values:
+    the same accepted / rejected steps, every iteration's cost to 1e-9, the focal length to 1e-8."""
+    assert [i["step_is_successful"] for i in s_app["iterations"]] == \
+        [i["step_is_successful"] for i in s_fresh["iterations"]]
+    for a, b in zip(s_app["iterations"], s_fresh["iterations"]):
+        assert abs(a["cost"] - b["cost"]) <= 1e-9 * b["cost"]
+    assert abs(camera_app[0] - camera_fresh[0]) <= 1e-8 * camera_fresh[0]
+
+
 def test_appended_problem_keeps_plan_and_matches_a_fresh_load(lm, oracle):
     """solveIncremental's growth (ar_slam_util.cpp:720-736): residual blocks of new captures that
     see only known tags are appended to the resident problem.  When their tile pairs are in the
@@ -193,10 +203,7 @@ def test_appended_problem_keeps_plan_and_matches_a_fresh_load(lm, oracle):
         fresh.add_residual_block(g.corners[b], cam_f, caps_f[g.obs_cap[b]], tags_f[g.obs_tag[b]])
     s3 = fresh.solve()
     assert s3["setup_kind"] == lm.SETUP_LOAD
-    assert [i["step_is_successful"] for i in s2["iterations"]] == [i["step_is_successful"] for i in s3["iterations"]]
-    for a, b in zip(s2["iterations"], s3["iterations"]):
-        assert abs(a["cost"] - b["cost"]) <= 1e-9 * b["cost"]
-    assert abs(camera[0] - cam_f[0]) <= 1e-8 * cam_f[0]
+    assert_matches_fresh_load(s2, camera, s3, cam_f)
     # and the oracle on the grown problem from the same start
     cap_ids = sorted({int(g.obs_cap[b]) for b in order})
     cpos = {c: i for i, c in enumerate(cap_ids)}

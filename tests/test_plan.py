@@ -207,7 +207,7 @@ def test_rank_split_partitions_the_factorization(L, name, worlds):
 
 @pytest.mark.parametrize("name,cuts", [("small", [1, 17, 40]), ("cfg2", [300, 700, 999])])
 def test_gather_plan_extension_equals_a_fresh_plan(L, name, cuts):
-    """The appended-problem path (try_extend) extends the loaded Schur gather plan by the new
+    """The appended-problem path (try_append) extends the loaded Schur gather plan by the new
     captures' contributions instead of rebuilding it: every destination keeps its contributions in
     capture order (the gather's fixed summation order) and gains the new ones after them.  The
     result must be the fresh plan of the grown problem, array for array."""
