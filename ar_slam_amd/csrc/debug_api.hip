@@ -356,6 +356,11 @@ extern "C" int arslam_debug_reduced_plan(const arslam_soa_problem *p, int orderi
           std::fwrite(plan.h_targets.data(), sizeof(int2), plan.h_targets.size(), f);
           std::fwrite(plan.h_dag_cont.data(), sizeof(int), n, f);
           std::fwrite(plan.h_dag_maxdep.data(), sizeof(int), n, f);
+          // the backward solve's gather list: {i, k} and the stored tile index of each entry
+          const long ng = (long)plan.h_gather.size();
+          std::fwrite(&ng, 8, 1, f);
+          std::fwrite(plan.h_gather.data(), sizeof(int2), ng, f);
+          std::fwrite(plan.h_gtile.data(), sizeof(int), ng, f);
           std::fclose(f);
         }
       }

@@ -2072,20 +2072,52 @@ __global__ __launch_bounds__(256) void k_bs_solve(const double *__restrict__ Xin
 // launch).  Ticket b takes column bs_cols[b]; the columns are root level
 // first, so every ancestor a column waits for holds an earlier ticket and was
 // drawn by a running workgroup (deadlock-free for any grid).  A column task:
-//   z_k      from the rhs row (as k_init_z);
+//   z_k      from the rhs row (as k_init_z), loaded at the top of the task
+//            beside X_kk: nothing it needs depends on the gathers;
 //   gathers  nearest ancestor LAST (ancestors finish root-first, so all but
 //            the parent's partial are summed while the parent is still being
-//            solved): L_ik is prefetched into registers before the wait on
-//            done[i], y_i is an sc1 load (written this launch), and the
+//            solved), y_i is an sc1 load (written this launch), and the
 //            partials are summed in this fixed order, so every rank of a
 //            sharded solve computes the same bits;
 //   solve    y_k = L_kk^{-T}(z_k - acc) with the prefetched inverse X_kk;
 //            wave 0 stores y_k write-through, drains, bumps done[k].
+// The gather loop is software-pipelined so that no load whose address depends
+// on another load sits between a parent's y and the column's own y:
+//   - the plan stores each gathered tile's compact index (gtile[g] =
+//     tile_id[i*T+k]), so an item's operands are {gather[g].x, gtile[g]} and
+//     the 16 L_ik values per thread: two round trips, not three;
+//   - the ticket is made wave-uniform (readfirstlane), so the plan's arrays
+//     are read with scalar loads: they are counted apart from the vector
+//     loads and never stand in front of a poll;
+//   - item g-1's L_ik values are issued into the second register set (lvA /
+//     lvB, swapped by unrolling the loop twice: no moves) right after the
+//     FIRST poll load of y_i of item g, and the indices of item g-2 with
+//     them.  Vector loads return in order, so a prefetch issued before that
+//     first load would hold every poll back; issued after it, its one round
+//     trip runs beside the poll's own -- and on the root path y_i is a whole
+//     link away when item g starts.  (Chosen over an inline-asm poll with a
+//     counted wait: that form needs every prefetch load in asm and counted by
+//     hand as well.  The compiler barrier pins the order.  ISA, per item:
+//     global_load_dwordx2 sc1 of y, 16 global_load_dwordx2, two s_load_dword,
+//     then the poll loop, whose compare hipcc guards with s_waitcnt vmcnt(0):
+//     the first compare of an item waits for its prefetch too, so an item
+//     costs at least one L_ik round trip -- one, where the dependent fetch
+//     was three -- and that trip is hidden whenever y_i is not there yet.)
+//   No prefetch reads outside the column's range [gbeg[b], gbeg[b+1]): the
+//   index loads are clamped to it and the last item issues no L_ik loads.  A
+//   timed-out wait leaves the task with its prefetched registers unused.
+__device__ __forceinline__ void bs_issue_lik(const double *__restrict__ S, int tile, int w, int lane,
+                                             double (&lv)[16]) {
+  const double *Lik = S + (long)tile * (T64 * T64);
+#pragma unroll
+  for (int m = 0; m < 16; ++m) lv[m] = Lik[(w + 4 * m) * T64 + lane];   // rows w, w+4, ..., lane's column
+}
+
 __global__ __launch_bounds__(256) void k_bsolve_dag(const double *__restrict__ S, const int *__restrict__ tid_map,
                                                     int T, const double *__restrict__ Ld, long nR,
                                                     const int *__restrict__ cols, const int2 *__restrict__ gather,
-                                                    const int *__restrict__ gbeg, int ncols, double *yF,
-                                                    int *counters, int *flag) {
+                                                    const int *__restrict__ gtile, const int *__restrict__ gbeg,
+                                                    int ncols, double *yF, int *counters, int *flag) {
   __shared__ double red[4][T64];
   __shared__ double ys[T64];
   __shared__ int sh[2];
@@ -2097,37 +2129,53 @@ __global__ __launch_bounds__(256) void k_bsolve_dag(const double *__restrict__ S
   for (;;) {
     if (tid == 0) sh[0] = atomicAdd(ticket, 1);
     __syncthreads();
-    const int b = sh[0];
+    const int b = __builtin_amdgcn_readfirstlane(sh[0]);
     if (b >= ncols) break;
     const int k = cols[b];
+    const int g0 = gbeg[b], g1 = gbeg[b + 1];
     const long row0 = (long)k * T64;
     // the inverse's rows 16w..16w+15 for lane's column, in flight during the gathers
     const double *X = Xinv + (long)k * T64 * T64;
     double xv[16];
 #pragma unroll
     for (int rr = 0; rr < 16; ++rr) xv[rr] = X[(16 * w + rr) * T64 + lane];
+    double z = 0.0;   // wave 0: lane's entry of z_k
+    if (w == 0 && row0 + lane < nR) {
+      if (k == kr) z = Ld[kr * T64 * T64 + (nR - kr * T64) * T64 + lane];
+      else z = tile_ptr(S, tid_map, T, (int)kr, k)[(nR - kr * T64) * T64 + lane];
+    }
     double acc = 0.0;   // wave 0: lane's row of sum_i L_ik^T y_i
-    bool ok = true;
-    for (int g = gbeg[b + 1] - 1; g >= gbeg[b]; --g) {
-      const int i = gather[g].x;
-      const long ri = (long)i * T64;
-      const double *Lik = tile_ptr(S, tid_map, T, i, k);
-      double lv[16];   // rows w, w+4, ..., lane's column
-#pragma unroll
-      for (int m = 0; m < 16; ++m) lv[m] = Lik[(w + 4 * m) * T64 + lane];
+    // the pipeline's state: item g is the current one (ancestor i_cur, its
+    // L_ik in flight or landed in one of lvA / lvB), {i_nxt, t_nxt} are item
+    // g-1's ancestor and tile
+    double lvA[16], lvB[16];
+    int g = g1 - 1, i_cur = 0, i_nxt = 0, t_nxt = 0;
+    if (g >= g0) {
+      i_cur = gather[g].x;
+      bs_issue_lik(S, gtile[g], w, lane, lvA);
+      const int gn = max(g - 1, g0);
+      i_nxt = gather[gn].x;
+      t_nxt = gtile[gn];
+    }
+    // one item: lv holds its L_ik, lvn takes the next item's; false = the wait gave up
+    auto item = [&](double (&lv)[16], double (&lvn)[16]) -> bool {
+      const long ri = (long)i_cur * T64;
+      // y_i is its own ready flag: the entries are kYSentinel until column
+      // i's task stores them (8-byte write-through stores, never torn), so
+      // the wait is the load itself -- no counter, no drain before it
+      double yv = 0.0;
+      bool mine = w == 0 && ri + lane < nR;
+      if (mine) yv = ld_wt(yF + ri + lane);
+      asm volatile("" ::: "memory");   // (the first poll load is issued; now the prefetch)
+      if (g > g0) bs_issue_lik(S, t_nxt, w, lane, lvn);
+      const int gnn = max(g - 2, g0);
+      const int i_nn = gather[gnn].x, t_nn = gtile[gnn];
       if (w == 0) {
-        // y_i is its own ready flag: the entries are kYSentinel until column
-        // i's task stores them (8-byte write-through stores, never torn), so
-        // the wait is the load itself -- no counter, no drain before it
-        double yv = 0.0;
-        bool mine = ri + lane < nR;
+        bool ok = true;
         long spins = 0;
         WaitTimer tm;
         for (;;) {
-          if (mine) {
-            yv = ld_wt(yF + ri + lane);
-            mine = (unsigned long long)__double_as_longlong(yv) == kYSentinel;
-          }
+          if (mine) mine = (unsigned long long)__double_as_longlong(yv) == kYSentinel;
           if (__builtin_amdgcn_ballot_w64(mine) == 0) break;
           __builtin_amdgcn_s_sleep(kBsolveSleep);
           if (tm.expired(++spins) || (((spins & 255) == 0) &&
@@ -2136,27 +2184,31 @@ __global__ __launch_bounds__(256) void k_bsolve_dag(const double *__restrict__ S
             ok = false;
             break;
           }
+          if (mine) yv = ld_wt(yF + ri + lane);
         }
         if (lane == 0) sh[1] = ok;
         ys[lane] = (ri + lane < nR) ? yv : 0.0;
       }
       __syncthreads();
-      if (!sh[1]) break;
+      if (!sh[1]) return false;
       double s = 0.0;
 #pragma unroll
       for (int m = 0; m < 16; ++m) s += lv[m] * ys[w + 4 * m];
       red[w][lane] = s;
       __syncthreads();
       if (w == 0) acc += ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+      i_cur = i_nxt;
+      i_nxt = i_nn;
+      t_nxt = t_nn;
+      --g;
+      return true;
+    };
+    while (g >= g0) {
+      if (!item(lvA, lvB)) break;
+      if (g < g0) break;
+      if (!item(lvB, lvA)) break;
     }
-    if (w == 0) {
-      double z = 0.0;
-      if (row0 + lane < nR) {
-        if (k == kr) z = Ld[kr * T64 * T64 + (nR - kr * T64) * T64 + lane];
-        else z = tile_ptr(S, tid_map, T, (int)kr, k)[(nR - kr * T64) * T64 + lane];
-      }
-      ys[lane] = (row0 + lane < nR) ? z - acc : 0.0;
-    }
+    if (w == 0) ys[lane] = (row0 + lane < nR) ? z - acc : 0.0;
     __syncthreads();
     double s = 0.0;
 #pragma unroll
@@ -2302,7 +2354,7 @@ void launch_dense_back_solve_dag(const LltPlan &P, const double *S, long nR, dou
   }
   const int grid = std::min(n_workgroups, ncols);
   hipLaunchKernelGGL(k_bsolve_dag, dim3((unsigned)grid), dim3(256), 0, s, S, P.tile_id, P.T, P.ldiag, nR, P.bs_cols,
-                     P.bs_gather, P.bs_gbeg, ncols, yF, P.bs_counters, flag);
+                     P.bs_gather, P.bs_gtile, P.bs_gbeg, ncols, yF, P.bs_counters, flag);
 }
 
 void launch_dense_back_solve(const LltPlan &P, const double *S, long nR, double *z, double *yF,

@@ -672,7 +672,10 @@ void llt_plan_symbolic(LltPlan &plan, int T, long lda, std::vector<uint8_t> &P, 
       if (cls[k] == 2) continue;
       bcols.push_back(k);
       for (int i = k + 1; i < T; ++i)
-        if (P[(long)i * T + k]) gather.push_back(make_int2(i, k));
+        if (P[(long)i * T + k]) {
+          gather.push_back(make_int2(i, k));
+          plan.h_gtile.push_back(plan.h_tile_id[(long)i * T + k]);   // (what tile_ptr would look up)
+        }
       gbeg.push_back((int)gather.size());   // column's gathers: [gbeg[b], gbeg[b+1])
     }
     plan.h_bs_off.push_back((int)bcols.size());
@@ -1061,6 +1064,7 @@ void llt_plan_upload(LltPlan &plan, hipStream_t s) {
   addv(&plan.bs_cols, plan.h_bcols);
   addv(&plan.bs_gather, plan.h_gather);
   addv(&plan.bs_gbeg, plan.h_gbeg);
+  addv(&plan.bs_gtile, plan.h_gtile);
   add(reinterpret_cast<void **>(&plan.bs_part), nullptr, std::max<size_t>(plan.h_gather.size(), 1) * 64 * sizeof(double));
   add(reinterpret_cast<void **>(&plan.bs_counters), nullptr, ((size_t)T + 1) * sizeof(int));
   addv(&plan.tile_id, plan.h_tile_id);

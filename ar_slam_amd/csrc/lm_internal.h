@@ -243,6 +243,7 @@ struct LltPlan {
   int *bs_cols = nullptr;       // backward-solve columns, root level first
   int2 *bs_gather = nullptr;    // (i,k) tiles gathered by each backward level, root level first
   int *bs_gbeg = nullptr;       // [ncols+1] gather range of each backward column (bs_cols order)
+  int *bs_gtile = nullptr;      // [n_gather] tile_id of bs_gather's (i,k): k_bsolve_dag reads it, not the map
   double *bs_part = nullptr;    // [n_gather*64] per-gather partial sums L_ik^T y_i (summed in order)
   int *bs_counters = nullptr;   // [T+1] persistent backward solve: done[column] | ticket
   int *tile_id = nullptr;       // [T*T] compact index of tile (i,j), -1 if structurally zero
@@ -301,7 +302,7 @@ struct LltPlan {
   std::vector<int2> h_dag_waits;
   // host copies of the device lists (llt_plan_symbolic)
   std::vector<int2> h_panel, h_targets, h_gather, h_split;
-  std::vector<int> h_kstart, h_ks, h_bcols, h_gbeg;
+  std::vector<int> h_kstart, h_ks, h_bcols, h_gbeg, h_gtile;
   std::vector<int4> h_items;
   double total_upd_flops = 0.0;
   double total_factor_flops = 0.0;   // updates + POTRF (+ inverse) + TRSM of the task graph

@@ -56,7 +56,7 @@ def main():
                 so = hashlib.sha256(open(lib, "rb").read()).hexdigest()[:12] if os.path.exists(lib) else "missing"
                 print(n, "FAILED", f"lib {os.path.basename(lib)} sha {so}", out.stdout[-1000:], out.stderr[-600:],
                       flush=True)
-                continue
+                sys.exit(1)   # (nothing more is started on a GPU a child may have faulted)
             d = json.loads(out.stdout.strip().splitlines()[-1])
             res[n].append(d)
             print(f"round {r} {n:12s} factor {d['factor_us']:7.1f} us  {d['it_s']:7.1f} it/s  cost {d['cost']}  {d['digest']}"

@@ -16,4 +16,9 @@ def load(path):
     d["cont"] = np.frombuffer(f.read(4 * n), np.int32)
     d["maxdep"] = np.frombuffer(f.read(4 * n), np.int32)
     d["nt"] = int(d["tmap"].max()) + 1
+    tail = f.read(8)   # (dumps of older builds end here)
+    if len(tail) == 8:
+        ng = int(np.frombuffer(tail, np.int64)[0])
+        d["gather"] = np.frombuffer(f.read(8 * ng), np.int32).reshape(ng, 2)   # {i, k}
+        d["gtile"] = np.frombuffer(f.read(4 * ng), np.int32)                   # the plan's tile index of (i, k)
     return d
