@@ -119,39 +119,125 @@ extern "C" int arslam_debug_angle_axis_rotate(int n, const double *w, const doub
   return ARSLAM_OK;
 }
 
-extern "C" int arslam_debug_dense_llt_ex(long n, double *A, const double *b, double *y, int *info,
-                                         int executor);
 extern "C" int arslam_debug_dense_llt(long n, double *A, const double *b, double *y, int *info) {
   return arslam_debug_dense_llt_ex(n, A, b, y, info, 0);
 }
 
 extern "C" int arslam_debug_dense_llt_ex(long n, double *A, const double *b, double *y, int *info,
                                          int executor) {
-  if (n <= 0 || !A || !b || !y || !info) return ARSLAM_E_INVALID_ARG;
+  // (in place: arslam_debug_tile_llt has read all of A before it writes L)
+  return arslam_debug_tile_llt(n, A, b, nullptr, executor == 1 ? 1 : 0, nullptr, 0, A, y, nullptr, info, nullptr);
+}
+
+namespace {
+int simulate_all(const arslam::LltPlan &plan);   // (below, with the plan entries)
+
+// The lower tile pattern a component entry factors: the given one (null = dense) plus what is
+// always taken, the diagonal tiles and the last tile row (it holds the right-hand side).
+std::vector<uint8_t> taken_pattern(int T, const unsigned char *given) {
+  std::vector<uint8_t> p((size_t)T * T, 0);
+  for (int i = 0; i < T; ++i)
+    for (int j = 0; j <= i; ++j) p[(size_t)i * T + j] = i == j || i == T - 1 || !given || given[(size_t)i * T + j];
+  return p;
+}
+
+// Column classes of a two-phase plan on one rank (null = one phase): 0 / 1 only, and the class-1
+// columns closed under the elimination tree's parent (phase 0 runs first, so a class-1 column
+// under a class-0 ancestor would update a column already factored).
+bool tile_classes(int T, const std::vector<uint8_t> &taken, const unsigned char *col_class, std::vector<int> &cls) {
+  cls.clear();
+  if (!col_class) return true;
+  std::vector<uint8_t> filled = taken;
+  std::vector<int> parent;
+  arslam::tile_fill(T, filled, parent);
+  cls.assign(col_class, col_class + T);
+  for (int k = 0; k < T; ++k)
+    if (cls[k] > 1 || (cls[k] == 1 && parent[k] >= 0 && cls[parent[k]] != 1)) return false;
+  return true;
+}
+
+void tile_plan_facts(const arslam::LltPlan &plan, arslam_tile_plan_facts *f) {
+  std::memset(f, 0, sizeof(*f));
+  f->tiles_per_side = plan.T;
+  f->n_assembled = plan.n_assembled;
+  f->n_tiles = plan.n_tiles;
+  f->n_levels = plan.nlev;
+  f->n_split = (long)plan.h_split.size();
+  f->n_dag_tasks = plan.n_dag_tasks;
+  f->fill_first_ok = plan.fill_first_ok ? 1 : 0;
+  f->phase_split = plan.n_phases > 1 ? plan.phase_split : plan.n_dag_tasks;
+  for (int c : plan.h_dag_cont) f->n_cont_tasks += c >= 0;
+}
+
+// the k_factor_dag grids a request of n_workgroups gives the plan's launch (one phase) or launches
+void tile_plan_grids(const arslam::LltPlan &plan, int n_workgroups, int grid[2]) {
+  const long n0 = plan.n_phases > 1 ? plan.phase_split : plan.n_dag_tasks, n1 = plan.n_dag_tasks - n0;
+  grid[0] = n0 > 0 ? arslam::dag_launch_grid(n0, n_workgroups) : 0;
+  grid[1] = n1 > 0 ? arslam::dag_launch_grid(n1, n_workgroups) : 0;
+}
+}  // namespace
+
+extern "C" int arslam_debug_tile_plan(int T, const unsigned char *tile_pattern, const unsigned char *col_class,
+                                      unsigned char *pattern_out, arslam_tile_plan_facts *facts) {
+  if (T <= 0 || !facts) return ARSLAM_E_INVALID_ARG;
+  try {
+    std::vector<uint8_t> pattern = taken_pattern(T, tile_pattern);
+    std::vector<int> cls;
+    if (!tile_classes(T, pattern, col_class, cls)) return ARSLAM_E_INVALID_ARG;
+    arslam::LltPlan plan;
+    arslam::llt_plan_symbolic(plan, T, (long)T * arslam::kTile, pattern, col_class ? &cls : nullptr);
+    if (pattern_out) std::memcpy(pattern_out, pattern.data(), pattern.size());
+    tile_plan_facts(plan, facts);
+    tile_plan_grids(plan, 512, facts->grid);   // (the default request; no device to clamp it by)
+    facts->dag_valid = arslam::dag_check(plan) ? 1 : 0;
+    if (facts->dag_valid) facts->dag_valid = simulate_all(plan);
+    return ARSLAM_OK;
+  } catch (const arslam::ApiError &e) {
+    return e.code;
+  } catch (...) {
+    return ARSLAM_E_INVALID_ARG;
+  }
+}
+
+extern "C" int arslam_debug_tile_llt(long n, const double *A, const double *b, const unsigned char *tile_pattern,
+                                     int executor, const unsigned char *col_class, unsigned flags, double *L_out,
+                                     double *y, unsigned char *pattern_out, int *info,
+                                     arslam_tile_plan_facts *facts) {
+  if (n <= 0 || !A || !b || !L_out || !y || !info || executor < 0 || executor > 1 || (flags & ~1u))
+    return ARSLAM_E_INVALID_ARG;
+  const bool fill_first = (flags & 1u) != 0, two_phase = col_class != nullptr;
+  if ((fill_first || two_phase) && executor != 1) return ARSLAM_E_INVALID_ARG;
   const long N = (n + 1 + arslam::kTile - 1) / arslam::kTile * arslam::kTile;
   const int T = (int)(N / arslam::kTile);
-  // dense lower matrix with the rhs as row n and identity padding, then compact tiles
-  std::vector<double> h((size_t)N * N, 0.0);
-  for (long i = 0; i < n; ++i)
-    for (long j = 0; j <= i; ++j) h[i * N + j] = A[i * n + j];
-  for (long j = 0; j < n; ++j) h[n * N + j] = b[j];
-  h[n * N + n] = 1e300;
-  for (long i = n + 1; i < N; ++i) h[i * N + i] = 1.0;
-  std::vector<uint8_t> pattern((size_t)T * T, 0);
-  for (int i = 0; i < T; ++i)
-    for (int j = 0; j <= i; ++j) pattern[(size_t)i * T + j] = 1;
+  std::vector<uint8_t> pattern = taken_pattern(T, tile_pattern);
+  const std::vector<uint8_t> given = pattern;
+  std::vector<int> cls;
+  if (!tile_classes(T, pattern, col_class, cls)) return ARSLAM_E_INVALID_ARG;
   arslam::LltPlan plan;
   try {
-    arslam::llt_plan_build(plan, T, N, pattern, 0);
+    arslam::llt_plan_build(plan, T, N, pattern, 0, two_phase ? &cls : nullptr);   // (pattern: filled in place)
   } catch (...) {
+    arslam::llt_plan_free(plan);
     return ARSLAM_E_HIP;
   }
+  if (fill_first && !plan.fill_first_ok) {
+    arslam::llt_plan_free(plan);
+    return ARSLAM_E_INVALID_ARG;
+  }
+  if (pattern_out) std::memcpy(pattern_out, pattern.data(), pattern.size());
+  // the lower matrix on the given tiles, the rhs as row n (pivot 1e300) and identity padding;
+  // the fill tiles zero, or quiet NaNs where the fill-first store has to write them first
   std::vector<double> tiles((size_t)plan.n_tiles * 4096, 0.0);
+  if (fill_first) std::fill(tiles.begin() + (size_t)plan.n_assembled * 4096, tiles.end(), std::nan(""));
   for (int ti = 0; ti < T; ++ti)
     for (int tj = 0; tj <= ti; ++tj) {
+      if (!given[(size_t)ti * T + tj]) continue;
       double *t = tiles.data() + (size_t)plan.h_tile_id[(size_t)ti * T + tj] * 4096;
       for (int r = 0; r < 64; ++r)
-        for (int c = 0; c < 64; ++c) t[r * 64 + c] = h[(ti * 64 + r) * N + tj * 64 + c];
+        for (int c = 0; c < 64; ++c) {
+          const long i = ti * 64L + r, j = tj * 64L + c;
+          t[r * 64 + c] = j > i ? 0.0 : i < n ? A[i * n + j] : i == n ? (j < n ? b[j] : 1e300) : i == j ? 1.0 : 0.0;
+        }
     }
   double *d_S = nullptr, *d_z = nullptr, *d_y = nullptr;
   int *d_flag = nullptr;
@@ -169,7 +255,11 @@ extern "C" int arslam_debug_dense_llt_ex(long n, double *A, const double *b, dou
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
       grid = std::min(grid, arslam::kDagWorkgroupsPerCu * cus);
   }
-  if (executor == 1 && std::getenv("ARSLAM_DAG_PROGRESS")) {
+  if (facts) {
+    tile_plan_facts(plan, facts);
+    if (executor == 1) tile_plan_grids(plan, grid, facts->grid);
+  }
+  if (executor == 1 && !two_phase && !fill_first && std::getenv("ARSLAM_DAG_PROGRESS")) {
     // debug: host-visible progress words, polled while the kernel runs
     int *prog = nullptr;
     DBG_CHECK(hipHostMalloc(&prog, 4 * sizeof(int) * grid, hipHostMallocCoherent));
@@ -193,8 +283,17 @@ extern "C" int arslam_debug_dense_llt_ex(long n, double *A, const double *b, dou
       std::_Exit(3);
     }
   }
-  if (executor == 1) arslam::launch_dense_llt_dag(plan, d_S, d_flag, 0, grid);
-  else arslam::launch_dense_llt(plan, d_S, d_flag, 0);
+  if (executor == 1 && two_phase) {
+    // as factor_reduced launches them: one reset, phase 0, (one rank: no exchange,) phase 1
+    arslam::launch_exec_reset(plan, d_flag, 0);
+    arslam::launch_dense_llt_dag(plan, d_S, d_flag, 0, grid, nullptr, nullptr, false, 0);
+    arslam::launch_dense_llt_dag(plan, d_S, d_flag, 0, grid, nullptr, nullptr, false, 1);
+  } else if (executor == 1) {
+    arslam::launch_dense_llt_dag(plan, d_S, d_flag, 0, grid, nullptr, nullptr, true, -1,
+                                 fill_first ? plan.n_assembled : LONG_MAX);
+  } else {
+    arslam::launch_dense_llt(plan, d_S, d_flag, 0);
+  }
   if (executor == 1) arslam::launch_dense_back_solve_dag(plan, d_S, n, d_y, d_flag, 0, grid);
   else arslam::launch_dense_back_solve(plan, d_S, n, d_z, d_y, d_flag, 0);
   arslam::launch_scatter_diag(plan, d_S, 0);
@@ -205,8 +304,8 @@ extern "C" int arslam_debug_dense_llt_ex(long n, double *A, const double *b, dou
   DBG_CHECK(hipMemcpy(info, d_flag, sizeof(int), hipMemcpyDeviceToHost));
   for (long i = 0; i < n; ++i)
     for (long j = 0; j < n; ++j) {
-      const double *t = tiles.data() + (size_t)plan.h_tile_id[(size_t)(i / 64) * T + (j <= i ? j / 64 : 0)] * 4096;
-      A[i * n + j] = j <= i ? t[(i % 64) * 64 + (j % 64)] : 0.0;
+      const int id = j <= i ? plan.h_tile_id[(size_t)(i / 64) * T + j / 64] : -1;
+      L_out[i * n + j] = id < 0 ? 0.0 : tiles[(size_t)id * 4096 + (i % 64) * 64 + (j % 64)];
     }
   arslam::llt_plan_free(plan);
   (void)hipFree(d_S);

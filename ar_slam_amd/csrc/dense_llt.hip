@@ -2337,7 +2337,7 @@ void launch_dense_llt_dag(const LltPlan &P, double *S, int *flag, hipStream_t s,
   // (n_workgroups: at most the resident count, kDagWorkgroupsPerCu per CU --
   // the claim cap, half the grid, must leave resident workgroups free to draw;
   // DESIGN §8b.  The callers clamp it: a HIP query here would sit on the hot path)
-  const int grid = (int)std::min<long>(n_workgroups, std::max<long>(std::min<long>(64, ntk), ntk / 4));
+  const int grid = dag_launch_grid(ntk, n_workgroups);
   hipLaunchKernelGGL(k_factor_dag, dim3((unsigned)grid), dim3(256), 0, s, a);
 }
 

@@ -11,6 +11,7 @@
 // reduced matrix is an arrow-head (sparse tag block + one dense border).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <climits>
 #include <cstdint>
 #include <stdexcept>
@@ -516,6 +517,11 @@ void launch_dense_llt(const LltPlan &P, double *S, int *flag, hipStream_t s,
 // debug: only the first k workgroups of every k_factor_dag launch start (the
 // others return at once; k <= 0 restores all), process-wide
 void set_dag_workgroup_limit(int k);
+// k_factor_dag's grid for n_tasks tickets when n_workgroups are asked for: a small task graph
+// runs on fewer workgroups (a quarter of its tasks, at least 64; launch_dense_llt_dag)
+inline int dag_launch_grid(long n_tasks, int n_workgroups) {
+  return (int)std::min<long>(n_workgroups, std::max<long>(std::min<long>(64, n_tasks), n_tasks / 4));
+}
 void launch_dense_llt_dag(const LltPlan &P, double *S, int *flag, hipStream_t s, int n_workgroups,
                           int *progress = nullptr, unsigned long long *trace = nullptr, bool reset = true,
                           int phase = -1, long first_store = LONG_MAX);

@@ -47,6 +47,7 @@ EXPORTS = ["arslam_lm_options_init", "arslam_lm_create", "arslam_lm_destroy",
            "arslam_lm_set_loss", "arslam_lm_get_loss", "arslam_lm_add_residual_block_loss",
            "arslam_lm_load_soa_loss", "arslam_debug_residual_jacobian_loss", "arslam_slam_set_loss",
            "arslam_debug_residual_jacobian", "arslam_debug_dense_llt", "arslam_debug_dense_llt_ex",
+           "arslam_debug_tile_llt", "arslam_debug_tile_plan",
            "arslam_debug_angle_axis_rotate", "arslam_debug_selinv", "arslam_lm_debug_force_indefinite",
            "arslam_lm_covariance", "arslam_lm_covariance_block", "arslam_lm_debug_reduced_rows",
            "arslam_lm_debug_force_multirank", "arslam_lm_debug_break_dependency", "arslam_lm_debug_tag_pair_tile",
@@ -269,6 +270,10 @@ def lib():
     L.arslam_debug_dense_llt.argtypes = [C.c_long, _dp, _dp, _dp, C.POINTER(C.c_int)]
     L.arslam_debug_angle_axis_rotate.argtypes = [C.c_int, _dp, _dp, _dp, _ip]
     L.arslam_debug_selinv.argtypes = [C.c_long, _dp, _up, _dp, _up, _ip]
+    if hasattr(L, "arslam_debug_tile_llt"):   # (absent from older variant builds under A/B)
+        L.arslam_debug_tile_llt.argtypes = [C.c_long, _dp, _dp, _up, C.c_int, _up, C.c_uint, _dp, _dp, _up, _ip,
+                                            C.c_void_p]
+        L.arslam_debug_tile_plan.argtypes = [C.c_int, _up, _up, _up, C.c_void_p]
     L.arslam_lm_covariance.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip, _ip, C.POINTER(CovInfo)]
     L.arslam_lm_covariance_block.argtypes = [C.c_void_p, _dp, _dp, _ip]
     L.arslam_lm_debug_reduced_rows.argtypes = [C.c_void_p, _ip, _ip, _ip]
@@ -666,6 +671,60 @@ def debug_dense_llt(A, b, executor=0):
     _check(lib().arslam_debug_dense_llt_ex(C.c_long(n), A.ctypes.data_as(_dp), b.ctypes.data_as(_dp),
                                            y.ctypes.data_as(_dp), C.byref(info), C.c_int(executor)))
     return A, y, info.value
+
+
+class TilePlanFacts(C.Structure):
+    _fields_ = [("tiles_per_side", C.c_int), ("n_assembled", C.c_long), ("n_tiles", C.c_long),
+                ("n_levels", C.c_int), ("n_split", C.c_long), ("n_dag_tasks", C.c_long),
+                ("fill_first_ok", C.c_int), ("phase_split", C.c_long), ("grid", C.c_int * 2),
+                ("n_cont_tasks", C.c_long), ("dag_valid", C.c_int)]
+
+    def as_dict(self):
+        d = {f: getattr(self, f) for f, _ in self._fields_}
+        d["grid"] = tuple(self.grid)
+        return d
+
+
+def _u8_or_none(a, shape):
+    return None if a is None else np.ascontiguousarray(np.asarray(a) != 0, np.uint8).reshape(shape)
+
+
+def debug_tile_llt(A, b, tile_pattern=None, executor=0, col_class=None, fill_first=False):
+    """Device Cholesky + solve of the SPD matrix A restricted to a lower tile pattern
+    (arslam_debug_tile_llt): tile_pattern None (dense) or (T, T), T = (n + 1 + 63) // 64; col_class
+    None or T values 0 / 1 (a two-phase plan on one rank); fill_first: the fill-first store over
+    NaN fill tiles.  Returns (L (n, n), y, info, pattern (T, T) after fill, plan facts dict)."""
+    A = _f64(A)
+    n = A.shape[0]
+    T = (n + 1 + 63) // 64
+    b = _f64(b).reshape(n)
+    pat = _u8_or_none(tile_pattern, (T, T))
+    cls = _u8_or_none(col_class, (T,))
+    Lf = np.zeros((n, n))
+    y = np.zeros(n)
+    out = np.zeros((T, T), np.uint8)
+    info = C.c_int(0)
+    facts = TilePlanFacts()
+    _check(lib().arslam_debug_tile_llt(C.c_long(n), A.ctypes.data_as(_dp), b.ctypes.data_as(_dp),
+                                       pat.ctypes.data_as(_up) if pat is not None else None, C.c_int(executor),
+                                       cls.ctypes.data_as(_up) if cls is not None else None,
+                                       C.c_uint(1 if fill_first else 0), Lf.ctypes.data_as(_dp),
+                                       y.ctypes.data_as(_dp), out.ctypes.data_as(_up), C.byref(info),
+                                       C.byref(facts)))
+    return Lf, y, info.value, out, facts.as_dict()
+
+
+def debug_tile_plan(T, tile_pattern=None, col_class=None):
+    """Host-only (no device): the plan debug_tile_llt builds for T tiles a side.  Returns (pattern
+    (T, T) after fill, plan facts dict with dag_valid)."""
+    pat = _u8_or_none(tile_pattern, (T, T))
+    cls = _u8_or_none(col_class, (T,))
+    out = np.zeros((T, T), np.uint8)
+    facts = TilePlanFacts()
+    _check(lib().arslam_debug_tile_plan(int(T), pat.ctypes.data_as(_up) if pat is not None else None,
+                                        cls.ctypes.data_as(_up) if cls is not None else None,
+                                        out.ctypes.data_as(_up), C.byref(facts)))
+    return out, facts.as_dict()
 
 
 def debug_selinv(A, tile_pattern=None):

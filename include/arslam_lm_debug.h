@@ -42,6 +42,50 @@ int arslam_debug_dense_llt(long n, double *A, const double *b, double *y, int *i
  * info < 0 reports a task-graph wait that timed out */
 int arslam_debug_dense_llt_ex(long n, double *A, const double *b, double *y, int *info, int executor);
 
+/* Facts of a tile plan, as the two entries below built it. */
+typedef struct {
+  int tiles_per_side;
+  long n_assembled;   /* tiles of the taken pattern (a two-phase plan: of the class-1 columns) */
+  long n_tiles;       /* tiles of the factor, after symbolic fill */
+  int n_levels;       /* level launches (a two-phase plan: both phases' lists) */
+  long n_split;       /* update targets whose k-list is split into chunks */
+  long n_dag_tasks;   /* tasks of the persistent executor's graph */
+  int fill_first_ok;  /* 1: every fill tile's first application is an unfolded update item */
+  long phase_split;   /* tickets [0, phase_split) are phase 0 (one phase: = n_dag_tasks) */
+  int grid[2];        /* workgroups of the k_factor_dag launch, or of the phase 0 / phase 1 launches;
+                         0 where nothing is launched (level executor, an empty phase).  tile_plan:
+                         for a request of 512, not clamped by a device */
+  long n_cont_tasks;  /* tasks whose workgroup may go straight on to a continuation target */
+  int dag_valid;      /* tile_plan only: as arslam_plan_info.dag_valid */
+} arslam_tile_plan_facts;
+
+/* The general form of arslam_debug_dense_llt_ex (which calls it with no pattern, classes or
+ * flags): factor the n x n row-major SPD matrix A on a tile pattern as the reduced system is
+ * factored (64 x 64 tiles, b as row n with pivot 1e300, identity padding after it) and solve
+ * A y = b.
+ * tile_pattern: NULL (dense) or T*T bytes, T = (n + 1 + 63) / 64, non-zero where lower tile
+ *   (i, j), j <= i, of A is taken; A is not read elsewhere, nor above its diagonal.  Diagonal
+ *   tiles and the whole last tile row (it holds row n) are always taken.
+ * executor: 0 level launches, 1 persistent task graph and persistent backward solve.
+ * col_class: NULL, or T bytes, 0 own subtree / 1 replicated top: the two-phase plan of a
+ *   multi-rank solve on one rank -- phase 0, then phase 1 with no exchange between them.
+ *   Executor 1 only; the class-1 columns must be closed under the elimination tree's parent.
+ * flags bit 0: the fill-first store, as the solver runs it -- first_store = n_assembled, and
+ *   the fill tiles are uploaded as quiet NaNs instead of zeros, so a read of a fill tile before
+ *   its first store poisons the factor.  Executor 1, one phase, and a plan with fill_first_ok.
+ * A broken rule above is ARSLAM_E_INVALID_ARG.
+ * L_out [n*n]: the factor on its tiles, 0 elsewhere (may be A itself).  y [n].  pattern_out
+ * (nullable) [T*T]: the pattern after fill.  *info: 0, k + 1 if pivot k was not positive, < 0 a
+ * task-graph wait that timed out.  facts: nullable. */
+int arslam_debug_tile_llt(long n, const double *A, const double *b, const unsigned char *tile_pattern,
+                          int executor, const unsigned char *col_class, unsigned flags, double *L_out,
+                          double *y, unsigned char *pattern_out, int *info, arslam_tile_plan_facts *facts);
+/* Host only (no HIP call): the plan arslam_debug_tile_llt would build for T tiles a side, its
+ * pattern after fill (pattern_out, nullable) and its facts, with dag_valid from the ticket-order
+ * check and the simulated interleavings. */
+int arslam_debug_tile_plan(int T, const unsigned char *tile_pattern, const unsigned char *col_class,
+                           unsigned char *pattern_out, arslam_tile_plan_facts *facts);
+
 /* The selected inverse behind arslam_lm_covariance, alone: factor the n x n
  * row-major SPD matrix A as the reduced system is factored (64 x 64 tiles, a
  * zero right-hand side as row n, identity padding after it; level launches)

@@ -4,7 +4,9 @@ Tolerances (fp64 everywhere; the oracle restates Ceres' arithmetic, the
 device sums in a different order and scatters the reduced system with
 atomics, so agreement is to rounding, not bitwise):
   * residual / Jacobian rows: 1e-12 relative to the row scale;
-  * dense Cholesky solve: 1e-10 relative residual on SPD test matrices;
+  * dense Cholesky solve: 1e-10 relative residual on SPD test matrices (well conditioned, a
+    dense tile pattern: a smoke test of the entry; the sparse plans, the ill-conditioned
+    classes and the backward-error bounds are tests/test_gpu_tile_llt.py's);
   * LM traces: per-iteration cost 1e-9 relative for the first 5 iterations,
     final cost 1e-8 relative, same termination type and rule, iteration
     count +-1, focal 1e-8 relative; every capture and tag pose after one rigid
