@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.environ.get("ARSLAM_LIB") or os.path.join(HERE, "libarslam_lm.so")   # (override: variant builds)
-SOURCES = ["lm_kernels.hip", "dense_llt.hip", "lm_load.hip", "lm_solve.hip", "lm_covariance.hip", "lm_capi.hip",
+SOURCES = ["lm_kernels.hip", "llt_levels.hip", "llt_dag.hip", "lm_load.hip", "lm_solve.hip", "lm_covariance.hip", "lm_capi.hip",
            "debug_api.hip", "llt_plan.cpp", "host_structure.cpp", "localize.hip", "selinv.hip"]
 HOST = os.path.join(HERE, "host")
 HOST_SOURCES = ["yaml_lite.cpp", "ar_slam_solver.cpp", "slam_capi.cpp"]   # plain C++ (g++)
@@ -79,14 +79,19 @@ def build_id():
     return f"{commit} src {h.hexdigest()[:12]}"
 
 
+def hip_flags(root, build_id_str):
+    """hipcc's flags for the sources of the checkout at root (tools/isa_cmp.py compiles other trees with them)."""
+    # (-fconstexpr-steps: schur_store_table.h builds its 33,280 descriptors at compile time)
+    return ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-munsafe-fp-atomics", "-fconstexpr-steps=100000000",
+            "-Wall", "-Wno-unused-function", "-I", os.path.join(root, "include"), "-I", os.path.join(root, "ar_slam_amd", "csrc"),
+            f'-DARSLAM_BUILD_ID="{build_id_str}"'] + os.environ.get("ARSLAM_EXTRA_FLAGS", "").split()
+
+
 def _build_locked(verbose):
     extra = os.environ.get("ARSLAM_EXTRA_FLAGS", "")
     objdir = os.path.join(HERE, "_obj" + ("_" + "".join(c for c in extra if c.isalnum()) if extra else ""))
     os.makedirs(objdir, exist_ok=True)
-    # (-fconstexpr-steps: schur_store_table.h builds its 33,280 descriptors at compile time)
-    flags = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-munsafe-fp-atomics", "-fconstexpr-steps=100000000",
-             "-Wall", "-Wno-unused-function", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-             f'-DARSLAM_BUILD_ID="{build_id()}"'] + os.environ.get("ARSLAM_EXTRA_FLAGS", "").split()
+    flags = hip_flags(ROOT, build_id())
     objs = []
     procs = []
     for src in SOURCES:

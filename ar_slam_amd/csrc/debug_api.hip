@@ -262,8 +262,8 @@ extern "C" int arslam_debug_tile_llt(long n, const double *A, const double *b, c
   if (executor == 1 && !two_phase && !fill_first && std::getenv("ARSLAM_DAG_PROGRESS")) {
     // debug: host-visible progress words, polled while the kernel runs
     int *prog = nullptr;
-    DBG_CHECK(hipHostMalloc(&prog, 4 * sizeof(int) * grid, hipHostMallocCoherent));
-    std::memset(prog, 0xff, 4 * sizeof(int) * grid);
+    DBG_CHECK(hipHostMalloc(&prog, arslam::kDagProgressInts * sizeof(int) * grid, hipHostMallocCoherent));
+    std::memset(prog, 0xff, arslam::kDagProgressInts * sizeof(int) * grid);
     hipStream_t st;
     DBG_CHECK(hipStreamCreate(&st));
     DBG_CHECK(hipMemcpy(d_S, tiles.data(), tiles.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -273,8 +273,10 @@ extern "C" int arslam_debug_tile_llt(long n, const double *A, const double *b, c
       if (hipStreamQuery(st) == hipSuccess) break;
       std::fprintf(stderr, "t=%d00ms:", it + 1);
       for (int g = 0; g < grid && g < 16; ++g)
-        std::fprintf(stderr, " [wg%d t%d ph%d ty%d]", g, ((volatile int *)prog)[4 * g], ((volatile int *)prog)[4 * g + 1],
-                     ((volatile int *)prog)[4 * g + 2]);
+        std::fprintf(stderr, " [wg%d t%d ph%d ty%d]", g, 
+                     ((volatile int *)prog)[arslam::kDagProgressInts * g + arslam::kProgTicket],
+                     ((volatile int *)prog)[arslam::kDagProgressInts * g + arslam::kProgPhase],
+                     ((volatile int *)prog)[arslam::kDagProgressInts * g + arslam::kProgType]);
       std::fprintf(stderr, "\n");
     }
     if (hipStreamQuery(st) != hipSuccess) {

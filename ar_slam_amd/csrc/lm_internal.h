@@ -1,6 +1,6 @@
 // lm_internal.h -- device problem layout and kernel launch wrappers shared by
 // the LM driver (lm_handle.h, lm_load.hip, lm_solve.hip), the per-capture kernels (lm_kernels.hip) and
-// the reduced-system Cholesky (dense_llt.hip).
+// the reduced-system Cholesky (llt_levels.hip, llt_dag.hip).
 //
 // Parameter slots (one contiguous f64 vector, x):
 //   [0,3)                camera  f, l1, l2
@@ -218,7 +218,30 @@ enum DagRecField {
   kDagRecInts = 32
 };
 
-// Tile plan of the reduced-system Cholesky (dense_llt.hip), level-scheduled
+// k_factor_dag's debug outputs.  A ticket's trace words (launch_dense_llt_dag's trace, [n_tasks][kDagTraceWords],
+// s_memrealtime ticks of 10 ns) -- tools/dag_trace.py, dag_phases.py and dag_critical.py read the dumped file by
+// these numbers, so a change here is a change there:
+enum DagTraceWord {
+  kTrDraw = 0,           // the ticket was drawn (or its claimed run began)
+  kTrMet = 1,            // its early waits were met
+  kTrEnd = 2,            // the task ended
+  kTrWg = 3,             // the workgroup; above bit 32 a POTRF with a fused tile adds 1 premet, 2 A_kk came in D,
+                         // 4 fused tile prefetched, 8 the continuation's early waits seen met, 16 continuation claimed
+  kTrLoaded = 4,         // POTRF: A_kk loaded and folded; TRSM: operands loaded
+  kTrFactored = 5,       // POTRF: factorized; TRSM: solved
+  kTrPublished = 6,      // POTRF: L_kk published
+  kTrSubPublished = 7,   // POTRF: the fused tile published (0: none)
+  kDagTraceWords = 8
+};
+// and a workgroup's host-visible progress ints (launch_dense_llt_dag's progress, [grid][kDagProgressInts]):
+enum DagProgressSlot {
+  kProgTicket = 0,   // the ticket in hand
+  kProgPhase = 1,    // 1 drawn, 2 waits met, 3 update item's products done, 4 task done, 9 left the loop
+  kProgType = 2,     // its task type (kRecType)
+  kDagProgressInts = 4
+};
+
+// Tile plan of the reduced-system Cholesky (llt_levels.hip, llt_dag.hip), level-scheduled
 // over the tile elimination tree.  Device arrays, host per-level offsets.
 struct LltPlan {
   // every device array of the plan lives in one grow-only arena (one
@@ -362,7 +385,7 @@ void llt_plan_reset(LltPlan &plan);                // host side only; the arena 
 
 
 // ---- lm_kernels.hip ----
-struct ExecReset;   // (dense_llt section below)
+struct ExecReset;   // (llt_dag.hip section below)
 void launch_linearize(const DevProblem &P, const double *x, double *g, double *colnorm,
                       double *obs_tg, double *parts, hipStream_t s);
 // k_linearize's reductions in one launch: the per-capture partials into
@@ -500,7 +523,7 @@ struct LaunchTiming {
   double flops = 0.0;         // algorithmic flops of the recorded launches
 };
 
-// ---- dense_llt.hip ----
+// ---- llt_levels.hip (launch_dense_llt, launch_dense_back_solve), llt_dag.hip (the rest) ----
 // Cholesky of the lower triangle of S (row-major, lda) over the plan's tiles,
 // in place.  Row nR carries the right-hand side, so on exit row nR =
 // (L^{-1} b)^T.  *flag is set non-zero if a pivot is not positive.  Then

@@ -8,7 +8,7 @@
 // problem, the parameters and the reduced system stay resident in HBM.
 #include "lm_handle.h"
 
-// decode the persistent executors' negative flags (dense_llt.hip) ...
+// decode the persistent executors' negative flags (llt_dag.hip) ...
 std::string arslam::lmh::executor_fault_message(int code, int rank, int iteration, const arslam::LltPlan &plan,
                                                 hipStream_t s) {
   std::string what;
@@ -336,10 +336,10 @@ int g_dag_trace_seen = 0;    // ... of the launch after ARSLAM_DAG_TRACE_SKIP ot
 // file tools/dag_*.py and potrf_*.py read
 void arslam_lm::dump_dag_trace(long first_store) {
   DevBuf<unsigned long long> tr;
-  tr.alloc(8 * plan.n_dag_tasks);
+  tr.alloc(arslam::kDagTraceWords * plan.n_dag_tasks);
   HIP_CHECK(hipMemsetAsync(tr.p, 0, tr.n * 8, stream));
   arslam::launch_dense_llt_dag(plan, Sp, d_flag.p, stream, dag_workgroups, nullptr, tr.p, false, -1, first_store);
-  std::vector<unsigned long long> h(8 * plan.n_dag_tasks);
+  std::vector<unsigned long long> h(arslam::kDagTraceWords * plan.n_dag_tasks);
   HIP_CHECK(hipMemcpyAsync(h.data(), tr.p, h.size() * 8, hipMemcpyDeviceToHost, stream));
   HIP_CHECK(hipStreamSynchronize(stream));
   if (FILE *f = std::fopen(env.dag_trace, "wb")) {

@@ -18,19 +18,13 @@
 // of X_kk are read as zero.  The leading block of a triangular inverse is the
 // inverse of the leading block, so Z on the real rows is exact, and zero on
 // the others.
-#include "lm_internal.h"
+#include "llt_tile.h"
 
 #include <algorithm>
 
 namespace arslam {
 
 namespace {
-
-typedef double dbl4 __attribute__((ext_vector_type(4)));
-typedef double dbl2 __attribute__((ext_vector_type(2)));
-
-constexpr int T64 = kTile;
-constexpr int LQ = 66;   // LDS pitch of the MFMA operand tiles (as dense_llt.hip)
 
 // 256-thread load of a 64x64 row-major tile into LDS (pitch LQ): element
 // (r, c) to lds[r][c], or to lds[c][r] (tr); rows and columns >= lim read as 0
@@ -53,33 +47,6 @@ __device__ __forceinline__ void load_tile(const double *__restrict__ g, double *
       *reinterpret_cast<dbl2 *>(lds + r * LQ + c2) = dbl2{x, y};
     }
   }
-}
-
-// acc += A B^T for two 64x64 LDS tiles (pitch LQ), 4 waves x 32x32 on
-// v_mfma_f64_16x16x4_f64; acc layout col = lane & 15, row = (lane >> 4) + 4 reg
-__device__ __forceinline__ void gemm64_nt(const double *sA, const double *sB, int tid, dbl4 acc[4]) {
-  const int w = tid >> 6, lane = tid & 63;
-  const int r0 = (w >> 1) * 32, c0 = (w & 1) * 32;
-  const int li = lane & 15, lk = lane >> 4;
-#pragma unroll 4
-  for (int kk = 0; kk < T64 / 4; ++kk) {
-    const int kc = kk * 4 + lk;
-    const double a0 = sA[(r0 + li) * LQ + kc];
-    const double a1 = sA[(r0 + 16 + li) * LQ + kc];
-    const double b0 = sB[(c0 + li) * LQ + kc];
-    const double b1 = sB[(c0 + 16 + li) * LQ + kc];
-    acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0], 0, 0, 0);
-    acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[1], 0, 0, 0);
-    acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[2], 0, 0, 0);
-    acc[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[3], 0, 0, 0);
-  }
-}
-
-// the accumulators' element (row, col) for q = 0..3, reg = 0..3
-__device__ __forceinline__ void acc_pos(int tid, int q, int reg, int &row, int &col) {
-  const int w = tid >> 6, lane = tid & 63;
-  row = (w >> 1) * 32 + (q >> 1) * 16 + (lane >> 4) + 4 * reg;
-  col = (w & 1) * 32 + (q & 1) * 16 + (lane & 15);
 }
 
 // valid rows of tile row i: those below the rhs row nR

@@ -4,13 +4,13 @@ What arslam_debug_tile_llt (include/arslam_lm_debug.h) is held to by tests/test_
 
   patterns   named lower tile patterns, each chosen for something a dense pattern's plan lacks;
   inputs     SPD matrices restricted to a pattern, equilibrated, in four conditioning classes;
-  tile_llt   the device's tile algorithm (dense_llt.hip, llt_plan.cpp) restated in float64;
+  tile_llt   the device's tile algorithm (llt_tile.h, llt_levels.hip, llt_dag.hip, llt_plan.cpp) restated in float64;
   metrics    backward errors of a factor (eta) and of a solve (omega), evaluated in np.longdouble;
   pivots     a longdouble Cholesky, for the first failed pivot and the smallest pivot.
 
 The device multiplies by explicit inverses where LAPACK substitutes, so its backward error grows
 with the conditioning of the diagonal tiles; the restatement has the same operations and is the
-yardstick for that growth.  What dense_llt.hip does, and tile_llt restates:
+yardstick for that growth.  What the device code does, and tile_llt restates:
 
   POTRF 64    right-looking over 16-column panels.  A 16 x 16 diagonal block is factored by one
               pass of Gaussian elimination (diag16): the multipliers, -a_ij times a Newton-refined

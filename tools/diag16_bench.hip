@@ -1,9 +1,9 @@
 // Diagnostic micro-benchmark: one diag16 call (16x16 diagonal-block
-// elimination of dense_llt.hip) on one wave, alone on the chip, in cycles
+// elimination of llt_tile.h) on one wave, alone on the chip, in cycles
 // (s_memtime) per call, plus its error against a host Cholesky.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I ar_slam_amd/csrc
 //   tools/diag16_bench.hip -o tools/diag16_bench
-#include "../ar_slam_amd/csrc/dense_llt.hip"
+#include "llt_tile.h"
 
 #include <cmath>
 #include <cstdio>

@@ -1,6 +1,6 @@
 // Diagnostic micro-benchmark: dependent-chain latency (cycles, s_memtime) of
 // the fp64 VALU / DPP / LDS operations the diagonal-block elimination of
-// dense_llt.hip is built from, one wave alone on the chip.
+// llt_tile.h is built from, one wave alone on the chip.
 // Build: hipcc --offload-arch=gfx950 -O3 tools/lat_bench.hip -o tools/lat_bench
 #include <hip/hip_runtime.h>
 #include <cmath>

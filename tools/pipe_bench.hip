@@ -5,7 +5,8 @@
 // Times in us (s_memrealtime, 100 MHz) from the start to X solved.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I ar_slam_amd/csrc
 //   tools/pipe_bench.hip -o tools/pipe_bench
-#include "../ar_slam_amd/csrc/dense_llt.hip"
+#include "llt_tile.h"
+#include "llt_wt.h"
 
 #include <cstdio>
 #include <vector>

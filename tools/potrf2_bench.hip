@@ -1,4 +1,4 @@
-// Diagnostic micro-benchmark: the POTRF variants of dense_llt.hip on one
+// Diagnostic micro-benchmark: the POTRF variants of llt_tile.h on one
 // workgroup alone on the chip, timed with s_memrealtime (100 MHz) per call:
 //   v1       blocked_potrf64 (workgroup barriers between panels)
 //   v2       blocked_potrf64_async (LDS counters)
@@ -7,7 +7,8 @@
 //   diag16x4 the four diagonal-block factorizations alone (the chain's floor)
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I ar_slam_amd/csrc
 //   tools/potrf2_bench.hip -o tools/potrf2_bench
-#include "../ar_slam_amd/csrc/dense_llt.hip"
+#include "llt_tile.h"
+#include "llt_wt.h"
 
 #include <cstdio>
 #include <vector>

@@ -4,7 +4,7 @@
 // (ARSLAM_STAMPS) at each phase of wave 0, averaged over reps.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -DARSLAM_STAMPS -I include
 //   -I ar_slam_amd/csrc tools/potrf_stamps.hip -o tools/potrf_stamps
-#include "../ar_slam_amd/csrc/dense_llt.hip"
+#include "llt_tile.h"
 
 #include <cstdio>
 #include <vector>
