@@ -382,6 +382,74 @@ extern "C" int arslam_debug_selinv(long n, const double *A, const unsigned char 
   return hip_fail(e);
 }
 
+extern "C" int arslam_debug_tile_solve(long n, const double *A, const unsigned char *tile_pattern, int nrhs,
+                                       const double *B, double *X_out, int *info) {
+  if (n <= 0 || nrhs <= 0 || !A || !B || !X_out || !info) return ARSLAM_E_INVALID_ARG;
+  const long N = (n + 1 + arslam::kTile - 1) / arslam::kTile * arslam::kTile;
+  const int T = (int)(N / arslam::kTile);
+  std::vector<uint8_t> pattern((size_t)T * T, 0);
+  for (int i = 0; i < T; ++i)
+    for (int j = 0; j <= i; ++j) pattern[(size_t)i * T + j] = i == j || !tile_pattern || tile_pattern[(size_t)i * T + j];
+  const std::vector<uint8_t> given = pattern;
+  arslam::LltPlan plan;
+  arslam::TileSolvePlan tp;
+  try {
+    arslam::llt_plan_build(plan, T, N, pattern, 0);   // (pattern: filled in place)
+    arslam::tile_solve_plan_build(plan, tp, 0);
+  } catch (...) {
+    arslam::tile_solve_plan_free(tp);
+    arslam::llt_plan_free(plan);
+    return ARSLAM_E_HIP;
+  }
+  // the matrix on the given tiles, a zero rhs as row n (pivot 1e300) and identity padding
+  std::vector<double> tiles((size_t)plan.n_tiles * 4096, 0.0);
+  for (int ti = 0; ti < T; ++ti)
+    for (int tj = 0; tj <= ti; ++tj) {
+      if (!given[(size_t)ti * T + tj]) continue;
+      double *t = tiles.data() + (size_t)plan.h_tile_id[(size_t)ti * T + tj] * 4096;
+      for (int r = 0; r < 64; ++r)
+        for (int c = 0; c < 64; ++c) {
+          const long i = ti * 64L + r, j = tj * 64L + c;
+          t[r * 64 + c] = j > i ? 0.0 : i < n ? A[i * n + j] : i == j ? (i == n ? 1e300 : 1.0) : 0.0;
+        }
+    }
+  // the right-hand sides, sixty columns to a panel of T row-major 64x64 tiles
+  const int per_panel = 6 * arslam::kCovPanelBlocks;
+  const int n_panels = (nrhs + per_panel - 1) / per_panel;
+  std::vector<double> panels((size_t)n_panels * T * 4096, 0.0);
+  const auto pel = [&](long r, int c) -> double & {
+    return panels[((size_t)(c / per_panel) * T + r / 64) * 4096 + (r % 64) * 64 + c % per_panel];
+  };
+  for (long r = 0; r < n; ++r)
+    for (int c = 0; c < nrhs; ++c) pel(r, c) = B[r * nrhs + c];
+  double *d_S = nullptr, *d_B = nullptr;
+  int *d_flag = nullptr;
+  const size_t bytes = tiles.size() * sizeof(double), pbytes = panels.size() * sizeof(double);
+  hipError_t e = hipMalloc(&d_S, bytes);
+  if (e == hipSuccess) e = hipMalloc(&d_B, pbytes);
+  if (e == hipSuccess) e = hipMalloc(&d_flag, sizeof(int));
+  if (e == hipSuccess) e = hipMemcpy(d_S, tiles.data(), bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_B, panels.data(), pbytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d_flag, 0, sizeof(int));
+  if (e == hipSuccess) {
+    arslam::launch_dense_llt(plan, d_S, d_flag, 0);
+    arslam::launch_tile_solve(plan, tp, d_S, n, d_B, n_panels, nullptr, nullptr, d_flag, 0);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(panels.data(), d_B, pbytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(info, d_flag, sizeof(int), hipMemcpyDeviceToHost);
+  if (e == hipSuccess)
+    for (long r = 0; r < n; ++r)
+      for (int c = 0; c < nrhs; ++c) X_out[r * nrhs + c] = pel(r, c);
+  arslam::tile_solve_plan_free(tp);
+  arslam::llt_plan_free(plan);
+  (void)hipFree(d_S);
+  (void)hipFree(d_B);
+  (void)hipFree(d_flag);
+  return hip_fail(e);
+}
+
 namespace {
 // The protocol simulation over grids and policies (arslam::dag_simulate):
 // 1 if deadlock-free in every run, else -(grid * 16 + policy) of the first

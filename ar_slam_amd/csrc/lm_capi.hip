@@ -10,6 +10,9 @@ arslam_lm::~arslam_lm() {
   for (auto e : cov_ev)
     if (e) (void)hipEventDestroy(e);
   arslam::selinv_plan_free(cov_sp);
+  for (auto e : pair_ev)
+    if (e) (void)hipEventDestroy(e);
+  arslam::tile_solve_plan_free(cov_tp);
   arslam::llt_plan_free(plan);
   if (comm) (void)ncclCommDestroy(comm);
   if (stream) (void)hipStreamDestroy(stream);
@@ -364,6 +367,51 @@ int arslam_lm_covariance_block(arslam_lm *h, const double *block, double *cov, i
     fail_if((size_t)i >= st.size(), ARSLAM_E_STATE, "covariance_block: the block is not part of the solved problem");
     std::memcpy(cov, c.data() + 36L * i, 36 * sizeof(double));
     if (status) *status = st[i];
+  });
+}
+
+int arslam_lm_covariance_pairs(arslam_lm *h, const arslam_lm_cov_pair *pairs, int n_pairs, double *cov, int *status,
+                               arslam_lm_cov_info *info) {
+  if (!h || n_pairs < 0 || (n_pairs > 0 && (!pairs || !cov))) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] { h->covariance_pairs(pairs, n_pairs, cov, status, info); });
+}
+
+int arslam_lm_covariance_block_pair(arslam_lm *h, const double *block_a, const double *block_b, double *cov,
+                                    int *status) {
+  if (!h || !block_a || !block_b || !cov) return ARSLAM_E_INVALID_ARG;
+  return guarded([&] {
+    arslam_lm_cov_pair pr{};
+    int size[2] = {6, 6};
+    const double *blocks[2] = {block_a, block_b};
+    for (int s = 0; s < 2; ++s) {
+      double *key = const_cast<double *>(blocks[s]);
+      const auto ci = h->cap_of.find(key);
+      const auto ti = h->tag_of.find(key);
+      fail_if(key != h->camera_ptr && ci == h->cap_of.end() && ti == h->tag_of.end(), ARSLAM_E_INVALID_ARG,
+              "parameter block is not part of the problem");
+      const int kind = key == h->camera_ptr ? ARSLAM_BLOCK_CAMERA : ci != h->cap_of.end() ? ARSLAM_BLOCK_CAPTURE : ARSLAM_BLOCK_TAG;
+      const int index = kind == ARSLAM_BLOCK_CAMERA ? 0 : kind == ARSLAM_BLOCK_CAPTURE ? ci->second : ti->second;
+      if (kind == ARSLAM_BLOCK_CAMERA) size[s] = 3;
+      (s == 0 ? pr.kind_a : pr.kind_b) = kind;
+      (s == 0 ? pr.index_a : pr.index_b) = index;
+    }
+    fail_if(!h->pk_loaded || h->pk_dirty, ARSLAM_E_STATE,
+            "covariance_block_pair: no completed arslam_lm_solve of the problem as it stands");
+    double c[36];
+    int st = ARSLAM_COV_UNAVAILABLE;
+    h->covariance_pairs(&pr, 1, c, &st, nullptr);
+    // Ceres' shapes: rows of a by columns of b, the camera block 3 wide (l1 / l2 rows and columns 0)
+    const int ra = size[0], cb = size[1];
+    if (st != ARSLAM_COV_OK) {
+      std::fill(cov, cov + ra * cb, -1.0);
+    } else {
+      std::fill(cov, cov + ra * cb, 0.0);
+      if (ra == 6 && cb == 6) std::copy(c, c + 36, cov);
+      else if (ra == 3 && cb == 6) std::copy(c, c + 6, cov);                    // row 0: cov(f, b)
+      else if (ra == 6 && cb == 3) for (int r = 0; r < 6; ++r) cov[3 * r] = c[r];   // column 0: cov(a, f)
+      else cov[0] = c[0];
+    }
+    if (status) *status = st;
   });
 }
 

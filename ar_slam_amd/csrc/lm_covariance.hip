@@ -1,23 +1,28 @@
-// lm_covariance.hip -- arslam_lm_covariance on the LM handle (lm_handle.h).
+// lm_covariance.hip -- arslam_lm_covariance and arslam_lm_covariance_pairs on the LM handle (lm_handle.h).
 #include "lm_handle.h"
 
-// Marginal covariances at the point the last solve returned (arslam_lm.h): the
-// structural gauge check on the host, then one linearization, the reduced
-// system without the LM diagonal (its own elimination kernel, the LM step's
-// gather) and its factorization as in an LM step, the selected inverse over
-// the factor's tiles and the two block kernels (selinv.hip).  Everything it writes on the device is scratch the next
-// solve rebuilds from the loaded state; the result is kept on the host in the
-// caller's block order.
-void arslam_lm::covariance() {
-  fail_if(!loaded || solve_state == 0, ARSLAM_E_STATE, "covariance: no completed solve of the loaded problem");
-  fail_if(solve_state == 2, ARSLAM_E_STATE, "covariance: the last solve ended with rule EVAL_FAILED");
-  fail_if(multi(), ARSLAM_E_UNSUPPORTED, "covariance: single-rank only");
+#include <map>
+
+void arslam_lm::cov_check_state(const char *who) const {
+  const std::string w(who);
+  fail_if(!loaded || solve_state == 0, ARSLAM_E_STATE, w + ": no completed solve of the loaded problem");
+  fail_if(solve_state == 2, ARSLAM_E_STATE, w + ": the last solve ended with rule EVAL_FAILED");
+  fail_if(multi(), ARSLAM_E_UNSUPPORTED, w + ": single-rank only");
   fail_if(elim_used == ARSLAM_ELIM_MIXED, ARSLAM_E_UNSUPPORTED,
-          "covariance: the mixed e-block set is not supported (ARSLAM_ELIM_CAPTURES or _TAGS)");
-  cov_valid = false;
+          w + ": the mixed e-block set is not supported (ARSLAM_ELIM_CAPTURES or _TAGS)");
+}
+
+// The structural gauge check on the host, then one linearization at the point
+// the last solve returned, the reduced system without the LM diagonal (its own
+// elimination kernel, the LM step's gather) and its factorization as in an LM
+// step.  Everything it writes on the device is scratch the next solve rebuilds
+// from the loaded state.
+void arslam_lm::cov_factor(CovFactor &cf) {
   ensure_stream();
   // the device problem's structure (its host copy is not kept after a load)
-  std::vector<int> h_cs(nc + 1, 0), h_ot(std::max(nb, 1));
+  std::vector<int> &h_cs = cf.cap_start;
+  h_cs.assign(nc + 1, 0);
+  std::vector<int> h_ot(std::max(nb, 1));
   std::vector<unsigned char> h_act(std::max(nb, 1));
   int n_blk = 0;
   HIP_CHECK(hipMemcpyAsync(h_cs.data(), u_cap_start, (nc + 1) * sizeof(int), hipMemcpyDeviceToHost, stream));
@@ -27,8 +32,6 @@ void arslam_lm::covariance() {
   HIP_CHECK(hipStreamSynchronize(stream));
   // Gauge: every connected component of the e-block / f-block graph over the
   // active observations that holds a free block must hold a constant one
-  const auto e_free = [&](int c) { return slot_free[3 + 6L * c] != 0; };
-  const auto f_free = [&](int t) { return slot_free[3 + 6L * nc + 6L * t] != 0; };
   bool deficient = false;
   {
     std::vector<int> par(nc + nt);
@@ -47,94 +50,81 @@ void arslam_lm::covariance() {
       }
     std::vector<unsigned char> anchored(nc + nt, 0), needs(nc + nt, 0);
     for (int i = 0; i < nc + nt; ++i) {
-      const bool fr = i < nc ? e_free(i) : f_free(i - nc);
+      const bool fr = i < nc ? cov_e_free(i) : cov_f_free(i - nc);
       if (fr) needs[find(i)] = 1;
       else if (used[i]) anchored[find(i)] = 1;
     }
     for (int i = 0; i < nc + nt; ++i) deficient = deficient || (needs[i] && !anchored[i]);
   }
-  std::vector<double> out(36L * nc + 36L * nt + 1, -1.0);
-  std::vector<int> st_e(std::max(nc, 1), 0);
-  arslam_lm_cov_info info{};
+  cf.deficient = deficient;
+  cf.factored = false;
+  arslam_lm_cov_info &info = cf.info;
+  info = arslam_lm_cov_info{};
   info.status = ARSLAM_COV_OK;
   info.min_pivot = -1.0;
   info.n_reduced = has_f ? nR : 0;
   info.n_factor_tiles = has_f ? plan.n_tiles : 0;
-  if (!deficient) {
-    for (auto &e : cov_ev)
-      if (!e) HIP_CHECK(hipEventCreate(&e));
-    // 1. the linearization at the returned point (jrows; the handle's Jacobi scale stays)
-    x = xbest;
-    HIP_CHECK(hipEventRecord(cov_ev[0], stream));
-    double c0, c1, c2, c3, c4;
-    linearize(&c0, &c1, &c2, &c3, &c4);
-    HIP_CHECK(hipEventRecord(cov_ev[1], stream));
-    // 2. the reduced system with no LM diagonal, eliminated by an orthogonal
-    // factorization of each e-block's columns (k_cov_schur: the normal
-    // equations' F'F - W'U^-1 W loses cond(U) digits, too many for a
-    // covariance), gathered as an LM step's is, then factored.  The gather's
-    // diagonal is 0 on the free slots; the camera's l1 / l2 rows, which hold
-    // nothing else, get the pivot 1
-    std::vector<double> dg(n);
-    for (long i = 0; i < n; ++i) dg[i] = slot_free[i] ? 0.0 : 1.0;
-    dg[1] = dg[2] = 1.0;
-    d_cov_diag.alloc(n);
-    HIP_CHECK(hipMemcpyAsync(d_cov_diag.p, dg.data(), n * sizeof(double), hipMemcpyHostToDevice, stream));
-    d_cov_Q.alloc(std::max(48L * nb, 1L));
-    d_cov_Y.alloc(std::max(6L * (nc + 6L * n_blk), 1L));
-    d_cov_R.alloc(std::max(36L * nc, 1L));
-    arslam::launch_cov_schur(P, d_scale.p, d_cov_Q.p, d_cov_Y.p, d_cov_R.p, has_f, stream);
-    if (has_f) {
-      const bool dag = opt.factor_executor == 1;
-      if (dag) {
-        const arslam::LmDiagArgs ld{0, d_scale.p, d_colnorm.p, 0.0, 0.0, d_diag.p, d_yF.p, nR};
-        arslam::launch_exec_reset(plan, d_flag.p, stream, &ld);
-      } else {
-        HIP_CHECK(hipMemsetAsync(d_flag.p, 0, sizeof(int), stream));
-      }
-      arslam::launch_zero_tiles(plan, Sp, stream);
-      arslam::launch_schur_gather(P, d_cov_diag.p, 1.0, Sp, stream);
-      factor_reduced(LONG_MAX, false);   // (every tile was cleared: no first-update store)
+  if (deficient) return;
+  for (auto &e : cov_ev)
+    if (!e) HIP_CHECK(hipEventCreate(&e));
+  // 1. the linearization at the returned point (jrows; the handle's Jacobi scale stays)
+  x = xbest;
+  HIP_CHECK(hipEventRecord(cov_ev[0], stream));
+  double c0, c1, c2, c3, c4;
+  linearize(&c0, &c1, &c2, &c3, &c4);
+  HIP_CHECK(hipEventRecord(cov_ev[1], stream));
+  // 2. the reduced system with no LM diagonal, eliminated by an orthogonal
+  // factorization of each e-block's columns (k_cov_schur: the normal
+  // equations' F'F - W'U^-1 W loses cond(U) digits, too many for a
+  // covariance), gathered as an LM step's is, then factored.  The gather's
+  // diagonal is 0 on the free slots; the camera's l1 / l2 rows, which hold
+  // nothing else, get the pivot 1
+  std::vector<double> dg(n);
+  for (long i = 0; i < n; ++i) dg[i] = slot_free[i] ? 0.0 : 1.0;
+  dg[1] = dg[2] = 1.0;
+  d_cov_diag.alloc(n);
+  HIP_CHECK(hipMemcpyAsync(d_cov_diag.p, dg.data(), n * sizeof(double), hipMemcpyHostToDevice, stream));
+  d_cov_Q.alloc(std::max(48L * nb, 1L));
+  d_cov_Y.alloc(std::max(6L * (nc + 6L * n_blk), 1L));
+  d_cov_R.alloc(std::max(36L * nc, 1L));
+  arslam::launch_cov_schur(P, d_scale.p, d_cov_Q.p, d_cov_Y.p, d_cov_R.p, has_f, stream);
+  if (has_f) {
+    const bool dag = opt.factor_executor == 1;
+    if (dag) {
+      const arslam::LmDiagArgs ld{0, d_scale.p, d_colnorm.p, 0.0, 0.0, d_diag.p, d_yF.p, nR};
+      arslam::launch_exec_reset(plan, d_flag.p, stream, &ld);
     } else {
       HIP_CHECK(hipMemsetAsync(d_flag.p, 0, sizeof(int), stream));
     }
-    HIP_CHECK(hipEventRecord(cov_ev[2], stream));
-    // 3. the selected inverse on the factor's tiles
-    if (has_f) {
-      if (!cov_sp_ready) {
-        arslam::selinv_plan_build(plan, cov_sp, stream);
-        cov_sp_ready = true;
-      }
-      d_cov_Z.alloc((size_t)plan.n_tiles * 4096);
-      arslam::launch_selinv(plan, cov_sp, Sp, nR, d_cov_Z.p, d_flag.p, stream);
-      info.n_selinv_products = cov_sp.n_products;
-      info.n_factor_products = plan.total_upd_tiles + (long)plan.h_gather.size() + plan.T;
-    }
-    HIP_CHECK(hipEventRecord(cov_ev[3], stream));
-    // 4. the blocks
-    d_cov_out.alloc(out.size());
-    d_cov_status.alloc(std::max(nc, 1));
-    arslam::launch_cov_blocks(P, has_f ? d_cov_Z.p : nullptr, d_scale.p, d_cov_Y.p, d_cov_R.p, d_cov_out.p, d_cov_status.p,
-                              d_cov_out.p + 36L * nc, d_cov_out.p + 36L * nc + 36L * nt, d_flag.p, stream);
-    HIP_CHECK(hipEventRecord(cov_ev[4], stream));
+    arslam::launch_zero_tiles(plan, Sp, stream);
+    arslam::launch_schur_gather(P, d_cov_diag.p, 1.0, Sp, stream);
+    factor_reduced(LONG_MAX, false);   // (every tile was cleared: no first-update store)
+    info.n_factor_products = plan.total_upd_tiles + (long)plan.h_gather.size() + plan.T;
+  } else {
+    HIP_CHECK(hipMemsetAsync(d_flag.p, 0, sizeof(int), stream));
+  }
+  HIP_CHECK(hipEventRecord(cov_ev[2], stream));
+  cf.factored = true;
+}
+
+// The calls' one stream sync, behind everything the caller enqueued after
+// cov_factor; then the numeric test: no failed pivot, and the smallest squared
+// pivot of the real rows (not l1 / l2, the padding or the rhs) at least 1e-14.
+void arslam_lm::cov_numeric_test(CovFactor &cf) {
+  arslam_lm_cov_info &info = cf.info;
+  if (cf.factored) {
     int flag = 0;
     std::vector<double> ld(has_f ? (size_t)plan.T * 4096 : 0);
-    HIP_CHECK(hipMemcpyAsync(out.data(), d_cov_out.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (nc) HIP_CHECK(hipMemcpyAsync(st_e.data(), d_cov_status.p, nc * sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipMemcpyAsync(&flag, d_flag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
     if (has_f) HIP_CHECK(hipMemcpyAsync(ld.data(), plan.ldiag, ld.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     if (flag < 0) throw Error(ARSLAM_E_DEVICE, executor_fault_message(flag, rank, -1, plan, stream));
-    float ms[4] = {0, 0, 0, 0};
-    for (int i = 0; i < 4; ++i) HIP_CHECK(hipEventElapsedTime(&ms[i], cov_ev[i], cov_ev[i + 1]));
+    float ms[2] = {0, 0};
+    for (int i = 0; i < 2; ++i) HIP_CHECK(hipEventElapsedTime(&ms[i], cov_ev[i], cov_ev[i + 1]));
     info.t_linearize_ms = ms[0];
     info.t_factor_ms = ms[1];
-    info.t_selinv_ms = ms[2];
-    info.t_blocks_ms = ms[3];
-    // the numeric test: no failed pivot, and the smallest squared pivot of the
-    // real rows (not l1 / l2, the padding or the rhs) at least 1e-14
     if (flag > 0) {
-      deficient = true;
+      cf.deficient = true;
     } else {
       double mp = 1.0;
       bool first = true;
@@ -147,27 +137,276 @@ void arslam_lm::covariance() {
         first = false;
       }
       info.min_pivot = mp;
-      if (!(mp >= 1e-14)) deficient = true;
+      if (!(mp >= 1e-14)) cf.deficient = true;
     }
   }
-  if (deficient) {
-    info.status = ARSLAM_COV_RANK_DEFICIENT;
-    std::fill(out.begin(), out.end(), -1.0);
+  if (cf.deficient) info.status = ARSLAM_COV_RANK_DEFICIENT;
+}
+
+// Marginal covariances at the point the last solve returned (arslam_lm.h):
+// cov_factor, the selected inverse over the factor's tiles and the two block
+// kernels (selinv.hip).  The result is kept on the host in the caller's block
+// order.
+void arslam_lm::covariance() {
+  cov_check_state("covariance");
+  cov_valid = false;
+  CovFactor cf;
+  cov_factor(cf);
+  arslam_lm_cov_info &info = cf.info;
+  std::vector<double> out(36L * nc + 36L * nt + 1, -1.0);
+  std::vector<int> st_e(std::max(nc, 1), 0);
+  if (cf.factored) {
+    // 3. the selected inverse on the factor's tiles
+    if (has_f) {
+      if (!cov_sp_ready) {
+        arslam::selinv_plan_build(plan, cov_sp, stream);
+        cov_sp_ready = true;
+      }
+      d_cov_Z.alloc((size_t)plan.n_tiles * 4096);
+      arslam::launch_selinv(plan, cov_sp, Sp, nR, d_cov_Z.p, d_flag.p, stream);
+      info.n_selinv_products = cov_sp.n_products;
+    }
+    HIP_CHECK(hipEventRecord(cov_ev[3], stream));
+    // 4. the blocks
+    d_cov_out.alloc(out.size());
+    d_cov_status.alloc(std::max(nc, 1));
+    arslam::launch_cov_blocks(P, has_f ? d_cov_Z.p : nullptr, d_scale.p, d_cov_Y.p, d_cov_R.p, d_cov_out.p, d_cov_status.p,
+                              d_cov_out.p + 36L * nc, d_cov_out.p + 36L * nc + 36L * nt, d_flag.p, stream);
+    HIP_CHECK(hipEventRecord(cov_ev[4], stream));
+    HIP_CHECK(hipMemcpyAsync(out.data(), d_cov_out.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (nc) HIP_CHECK(hipMemcpyAsync(st_e.data(), d_cov_status.p, nc * sizeof(int), hipMemcpyDeviceToHost, stream));
   }
+  cov_numeric_test(cf);
+  if (cf.factored) {
+    float ms[2] = {0, 0};
+    for (int i = 0; i < 2; ++i) HIP_CHECK(hipEventElapsedTime(&ms[i], cov_ev[2 + i], cov_ev[3 + i]));
+    info.t_selinv_ms = ms[0];
+    info.t_blocks_ms = ms[1];
+  }
+  const bool deficient = cf.deficient;
+  if (deficient) std::fill(out.begin(), out.end(), -1.0);
   // statuses in the device problem's order, then the caller's arrays (tag
   // elimination: the e-blocks are the caller's tags)
   std::vector<int> se(nc), sf(nt);
   for (int c = 0; c < nc; ++c)
-    se[c] = !e_free(c) ? ARSLAM_COV_UNAVAILABLE : (deficient || st_e[c] == 2) ? ARSLAM_COV_RANK_DEFICIENT : ARSLAM_COV_OK;
+    se[c] = !cov_e_free(c) ? ARSLAM_COV_UNAVAILABLE : (deficient || st_e[c] == 2) ? ARSLAM_COV_RANK_DEFICIENT : ARSLAM_COV_OK;
   for (int t = 0; t < nt; ++t)
-    sf[t] = !f_free(t) ? ARSLAM_COV_UNAVAILABLE : deficient ? ARSLAM_COV_RANK_DEFICIENT : ARSLAM_COV_OK;
+    sf[t] = !cov_f_free(t) ? ARSLAM_COV_UNAVAILABLE : deficient ? ARSLAM_COV_RANK_DEFICIENT : ARSLAM_COV_OK;
   const bool swapped = elim_used == ARSLAM_ELIM_TAGS;
-  std::vector<double> ce(out.begin(), out.begin() + 36L * nc), cf(out.begin() + 36L * nc, out.begin() + 36L * (nc + nt));
-  cov_cap = swapped ? cf : ce;
-  cov_tag = swapped ? ce : cf;
+  std::vector<double> ce(out.begin(), out.begin() + 36L * nc), cf_(out.begin() + 36L * nc, out.begin() + 36L * (nc + nt));
+  cov_cap = swapped ? cf_ : ce;
+  cov_tag = swapped ? ce : cf_;
   cov_cap_status = swapped ? sf : se;
   cov_tag_status = swapped ? se : sf;
   cov_var_f = out.back();
   cov_info = info;
   cov_valid = true;
+}
+
+// Cross-covariance blocks of the same matrix (arslam_lm.h): cov_factor, then
+// whole columns of Z = S^-1 by the multi-right-hand-side tile solve
+// (cov_pairs.hip) on the factor itself -- this call never runs the selected
+// inverse, whose first kernel overwrites the off-diagonal factor tiles in
+// place, and it refactors every time, so an earlier covariance() leaves it
+// nothing to trip over.  Each unordered pair is computed once, with the block
+// of the smaller key (the focal, then the reduced side's blocks, then the
+// eliminated side's, by index) as the solved side; the other order is its
+// transpose.  The distinct solved blocks go through the solve in batches of at
+// most kCovBatchPanels panels and kCovBatchBytes.  A right-hand side is
+// non-zero only in the tile rows of its block, so the forward pass touches
+// their ancestors in the elimination tree and nothing else, and the backward
+// pass computes only the tile rows some pair of the panel reads (and their
+// ancestors): per-panel byte masks, built here.
+void arslam_lm::covariance_pairs(const arslam_lm_cov_pair *pairs, int n_pairs, double *cov, int *status,
+                                 arslam_lm_cov_info *info_out) {
+  cov_check_state("covariance_pairs");
+  const bool swapped = elim_used == ARSLAM_ELIM_TAGS;
+  const int n_caller_cap = swapped ? nt : nc, n_caller_tag = swapped ? nc : nt;
+  // the caller's block in the device problem: {role, idx} (tag elimination: the e-blocks are the caller's tags)
+  struct Blk {
+    int role, idx;
+    long key() const { return role == arslam::kCovFocal ? 0L : role == arslam::kCovF ? 1L + idx : (1L << 40) + idx; }
+  };
+  const auto device_block = [&](int kind, int index) -> Blk {
+    fail_if(kind != ARSLAM_BLOCK_CAMERA && kind != ARSLAM_BLOCK_CAPTURE && kind != ARSLAM_BLOCK_TAG,
+            ARSLAM_E_INVALID_ARG, "covariance_pairs: kind must be ARSLAM_BLOCK_CAMERA, _CAPTURE or _TAG");
+    if (kind == ARSLAM_BLOCK_CAMERA) {
+      fail_if(index != 0, ARSLAM_E_INVALID_ARG, "covariance_pairs: the camera's index is 0");
+      return Blk{arslam::kCovFocal, 0};
+    }
+    const bool cap = kind == ARSLAM_BLOCK_CAPTURE;
+    fail_if(index < 0 || index >= (cap ? n_caller_cap : n_caller_tag), ARSLAM_E_INVALID_ARG,
+            "covariance_pairs: block index out of range");
+    return Blk{cap != swapped ? arslam::kCovE : arslam::kCovF, index};
+  };
+  std::vector<Blk> blk(2L * n_pairs);
+  for (int i = 0; i < n_pairs; ++i) {
+    blk[2L * i] = device_block(pairs[i].kind_a, pairs[i].index_a);
+    blk[2L * i + 1] = device_block(pairs[i].kind_b, pairs[i].index_b);
+  }
+  CovFactor cf;
+  cov_factor(cf);
+  const auto available = [&](const Blk &b) {
+    if (b.role == arslam::kCovFocal) return has_f && P.cam_row >= 0;
+    if (b.role == arslam::kCovF)
+      return has_f && cov_f_free(b.idx) && (size_t)b.idx < lay.tag_row.size() && lay.tag_row[b.idx] >= 0;
+    return cov_e_free(b.idx) && cf.cap_start[b.idx + 1] > cf.cap_start[b.idx];
+  };
+  // the distinct unordered pairs of available blocks, keyed (solved side, other side): in batch order
+  std::map<std::pair<long, long>, int> task_of;
+  std::vector<unsigned char> avail(n_pairs, 0);
+  for (int i = 0; i < n_pairs; ++i) {
+    avail[i] = available(blk[2L * i]) && available(blk[2L * i + 1]);
+    if (!avail[i]) continue;
+    const long ka = blk[2L * i].key(), kb = blk[2L * i + 1].key();
+    task_of.emplace(std::make_pair(std::min(ka, kb), std::max(ka, kb)), 0);
+  }
+  const auto block_of = [&](long key) -> Blk {
+    return key == 0 ? Blk{arslam::kCovFocal, 0}
+                    : key < (1L << 40) ? Blk{arslam::kCovF, (int)(key - 1)} : Blk{arslam::kCovE, (int)(key - (1L << 40))};
+  };
+  std::vector<arslam::CovPairTask> tasks;
+  std::vector<int2> rhs;
+  std::vector<int> task_rhs;   // the solved block's position in rhs
+  {
+    long last = -1;
+    for (auto &kv : task_of) {
+      const Blk b = block_of(kv.first.first), a = block_of(kv.first.second);
+      if (rhs.empty() || kv.first.first != last) rhs.push_back(make_int2(b.role, b.idx));
+      last = kv.first.first;
+      kv.second = (int)tasks.size();
+      task_rhs.push_back((int)rhs.size() - 1);
+      tasks.push_back(arslam::CovPairTask{a.role, a.idx, b.role, b.idx, 0, (int)tasks.size()});
+    }
+  }
+  const int n_tasks = (int)tasks.size(), n_rhs = (int)rhs.size();
+  // panels per batch: what fits kCovBatchBytes, kCovBatchPanels at most (a panel is T x 32 KB)
+  const size_t panel = (size_t)std::max(plan.T, 1) * 4096;
+  const int batch_panels = (int)std::min<size_t>(kCovBatchPanels, std::max<size_t>(1, kCovBatchBytes / (panel * sizeof(double))));
+  const int per_batch = batch_panels * arslam::kCovPanelBlocks;
+  for (int t = 0; t < n_tasks; ++t) tasks[t].slot = task_rhs[t] % per_batch;
+  std::vector<double> out(36L * std::max(n_tasks, 1), -1.0);
+  std::vector<int> st(std::max(n_tasks, 1), 2);
+  arslam_lm_cov_info &info = cf.info;
+  const int n_batches = (n_rhs + per_batch - 1) / per_batch;
+  const bool run = cf.factored && n_tasks > 0;
+  if (run) {
+    const int T = plan.T;
+    const int all_panels = (n_rhs + arslam::kCovPanelBlocks - 1) / arslam::kCovPanelBlocks;   // (a batch holds whole panels)
+    // per panel, the tile rows its right-hand sides touch (active) and those its pairs read (needed)
+    std::vector<unsigned char> mask(has_f ? 2 * (size_t)all_panels * T : 0, 0);
+    unsigned char *active = mask.data(), *needed = mask.data() + (size_t)all_panels * T;
+    if (has_f) {
+      if (!cov_tp_ready) {
+        arslam::tile_solve_plan_build(plan, cov_tp, stream);
+        cov_tp_ready = true;
+      }
+      // the e-blocks' local f-blocks (their reduced rows are where an e-block's columns and rows live)
+      std::vector<int> h_bs(nc + 1, 0), h_bt;
+      bool any_e = false;
+      for (const auto &t : tasks) any_e = any_e || t.role_a == arslam::kCovE || t.role_b == arslam::kCovE;
+      if (any_e) {
+        HIP_CHECK(hipMemcpyAsync(h_bs.data(), u_cap_blk_start, (nc + 1) * sizeof(int), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        h_bt.resize(std::max(h_bs[nc], 1));
+        if (h_bs[nc]) HIP_CHECK(hipMemcpyAsync(h_bt.data(), u_blk_tag, h_bs[nc] * sizeof(int), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+      }
+      const auto f_row = [&](int t) -> long { return (size_t)t < lay.tag_row.size() ? lay.tag_row[t] : -1; };
+      const auto mark = [&](unsigned char *m, int role, int idx) {
+        const auto rows6 = [&](long r) {
+          if (r < 0) return;
+          arslam::tile_solve_mark(cov_tp, m, r);
+          arslam::tile_solve_mark(cov_tp, m, r + 5);
+        };
+        if (role == arslam::kCovFocal) {
+          if (P.cam_row >= 0) arslam::tile_solve_mark(cov_tp, m, P.cam_row);
+        } else if (role == arslam::kCovF) {
+          rows6(f_row(idx));
+        } else {
+          if (P.cam_row >= 0) arslam::tile_solve_mark(cov_tp, m, P.cam_row);
+          for (int u = h_bs[idx]; u < h_bs[idx + 1]; ++u) rows6(f_row(h_bt[u]));
+        }
+      };
+      for (int r = 0; r < n_rhs; ++r) mark(active + (size_t)(r / arslam::kCovPanelBlocks) * T, rhs[r].x, rhs[r].y);
+      for (int t = 0; t < n_tasks; ++t)
+        mark(needed + (size_t)(task_rhs[t] / arslam::kCovPanelBlocks) * T, tasks[t].role_a, tasks[t].idx_a);
+      d_pair_mask.alloc(mask.size());
+      d_pair_mask.upload(mask.data(), mask.size(), stream);
+      d_pair_B.alloc(panel * std::min(batch_panels, all_panels));
+      while ((int)pair_ev.size() < 2 * n_batches) {
+        hipEvent_t e = nullptr;
+        HIP_CHECK(hipEventCreate(&e));
+        pair_ev.push_back(e);
+      }
+    }
+    d_pair_rhs.alloc(n_rhs);
+    d_pair_tasks.alloc(n_tasks);
+    d_pair_out.alloc(36L * n_tasks);
+    d_pair_status.alloc(n_tasks);
+    d_pair_rhs.upload(rhs.data(), n_rhs, stream);
+    d_pair_tasks.upload(tasks.data(), n_tasks, stream);
+    int t0 = 0;
+    for (int bt = 0; bt < n_batches; ++bt) {
+      const int r0 = bt * per_batch, nr = std::min(per_batch, n_rhs - r0);
+      const int np = (nr + arslam::kCovPanelBlocks - 1) / arslam::kCovPanelBlocks;
+      int t1 = t0;
+      while (t1 < n_tasks && task_rhs[t1] < r0 + nr) ++t1;
+      if (has_f) {
+        const size_t m0 = (size_t)bt * batch_panels * T;   // this batch's first panel in the masks
+        HIP_CHECK(hipMemsetAsync(d_pair_B.p, 0, panel * np * sizeof(double), stream));
+        arslam::launch_cov_pair_rhs(P, d_cov_Y.p, d_cov_R.p, d_pair_rhs.p + r0, nr, d_pair_B.p, stream);
+        HIP_CHECK(hipEventRecord(pair_ev[2 * bt], stream));
+        arslam::launch_tile_solve(plan, cov_tp, Sp, nR, d_pair_B.p, np, d_pair_mask.p + m0,
+                                  d_pair_mask.p + (size_t)all_panels * T + m0, d_flag.p, stream);
+        HIP_CHECK(hipEventRecord(pair_ev[2 * bt + 1], stream));
+        for (int p = 0; p < np; ++p)
+          info.n_selinv_products += arslam::tile_solve_products(plan, cov_tp, active + m0 + (size_t)p * T, needed + m0 + (size_t)p * T);
+      }
+      arslam::launch_cov_pair_blocks(P, has_f ? d_pair_B.p : nullptr, d_scale.p, d_cov_Y.p, d_cov_R.p, d_pair_tasks.p + t0,
+                                     t1 - t0, d_pair_out.p, d_pair_status.p, d_flag.p, stream);
+      t0 = t1;
+    }
+    HIP_CHECK(hipEventRecord(cov_ev[3], stream));
+    HIP_CHECK(hipMemcpyAsync(out.data(), d_pair_out.p, 36L * n_tasks * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(st.data(), d_pair_status.p, n_tasks * sizeof(int), hipMemcpyDeviceToHost, stream));
+  }
+  cov_numeric_test(cf);
+  if (run) {
+    float all = 0.f, solve = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&all, cov_ev[2], cov_ev[3]));
+    for (int bt = 0; has_f && bt < n_batches; ++bt) {
+      float ms = 0.f;
+      HIP_CHECK(hipEventElapsedTime(&ms, pair_ev[2 * bt], pair_ev[2 * bt + 1]));
+      solve += ms;
+    }
+    info.t_selinv_ms = solve;
+    info.t_blocks_ms = std::max(0.f, all - solve);
+  }
+  // the caller's pairs: its (a, b) as computed or transposed; the focal's 6 values first
+  for (int i = 0; i < n_pairs; ++i) {
+    double *c = cov + 36L * i;
+    int s = ARSLAM_COV_UNAVAILABLE;
+    if (avail[i]) {
+      const Blk &ba = blk[2L * i], &bb = blk[2L * i + 1];
+      const long ka = ba.key(), kb = bb.key();
+      const int t = task_of.at(std::make_pair(std::min(ka, kb), std::max(ka, kb)));
+      s = (cf.deficient || st[t] != 0) ? ARSLAM_COV_RANK_DEFICIENT : ARSLAM_COV_OK;
+      if (s == ARSLAM_COV_OK) {
+        const double *o = out.data() + 36L * t;   // rows: the larger key's block; columns: the smaller's
+        const bool as_is = ka >= kb;
+        double m[36];
+        for (int r = 0; r < 6; ++r)
+          for (int q = 0; q < 6; ++q) m[6 * r + q] = as_is ? o[6 * r + q] : o[6 * q + r];
+        const bool fa = ba.role == arslam::kCovFocal, fb = bb.role == arslam::kCovFocal;
+        std::fill(c, c + 36, 0.0);
+        if (fa) std::copy(m, m + (fb ? 1 : 6), c);                 // row 0: cov(f, b)
+        else if (fb) for (int r = 0; r < 6; ++r) c[r] = m[6 * r];   // column 0: cov(a, f)
+        else std::copy(m, m + 36, c);
+      }
+    }
+    if (s != ARSLAM_COV_OK) std::fill(c, c + 36, -1.0);
+    if (status) status[i] = s;
+  }
+  if (info_out) *info_out = info;
 }

@@ -552,4 +552,37 @@ struct arslam_lm {
     solve_state = 0;
     cov_valid = false;
   }
+  // What covariance() and covariance_pairs() share (lm_covariance.hip):
+  // cov_check_state: the calls' preconditions.  cov_factor: the structural
+  // gauge check, then -- unless it fails -- the linearization at xbest,
+  // k_cov_schur, the gather with the covariance's diagonal and the
+  // factorization, all enqueued (cov_ev[0..2] around them); S then holds the
+  // factor itself.  cov_numeric_test: after the caller's own launches, the
+  // one stream sync, the flag and the min_pivot test; fills the times.
+  struct CovFactor {
+    std::vector<int> cap_start;   // the device problem's e-block CSR
+    bool deficient = false;
+    bool factored = false;        // the device work was enqueued
+    arslam_lm_cov_info info{};
+  };
+  bool cov_e_free(int c) const { return slot_free[3 + 6L * c] != 0; }
+  bool cov_f_free(int t) const { return slot_free[3 + 6L * nc + 6L * t] != 0; }
+  void cov_check_state(const char *who) const;
+  void cov_factor(CovFactor &cf);
+  void cov_numeric_test(CovFactor &cf);
+
+  // ---- cross-covariance blocks (arslam_lm_covariance_pairs) ----
+  // everything below is allocated at the first covariance_pairs call
+  arslam::TileSolvePlan cov_tp;
+  bool cov_tp_ready = false;   // cov_tp is the loaded plan's
+  static constexpr int kCovBatchPanels = 16;              // panels solved per batch at most (160 right-hand blocks) ...
+  static constexpr size_t kCovBatchBytes = 256u << 20;   // ... within this many bytes of panels, one panel at least
+  DevBuf<unsigned char> d_pair_mask;   // per panel: active tile rows, then needed tile rows
+  DevBuf<double> d_pair_B, d_pair_out;
+  DevBuf<int2> d_pair_rhs;
+  DevBuf<arslam::CovPairTask> d_pair_tasks;
+  DevBuf<int> d_pair_status;
+  std::vector<hipEvent_t> pair_ev;   // two per batch, around its solve
+  void covariance_pairs(const arslam_lm_cov_pair *pairs, int n_pairs, double *cov, int *status,
+                        arslam_lm_cov_info *info);
 };

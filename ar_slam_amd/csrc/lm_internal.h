@@ -629,4 +629,61 @@ void launch_cov_blocks(const DevProblem &P, const double *Z, const double *scale
 void launch_cov_schur(const DevProblem &P, const double *scale, double *Qb, double *Gb, double *Rb, bool write_slab,
                       hipStream_t s);
 
+// ---- cov_pairs.hip ----
+// Multi-right-hand-side solve X = L^{-T} L^{-1} B over the factor's tiles
+// (one-rank plans).  The forward pass is left-looking: per backward column b
+// (bs_cols order) the off-diagonal tiles (k, j) of tile row k = bs_cols[b],
+// ascending j, as {j, tile id} in flist[fbeg[b] .. fbeg[b + 1]).
+struct TileSolvePlan {
+  int *fbeg = nullptr;
+  int2 *flist = nullptr;
+  std::vector<int> h_fbeg;     // host copies
+  std::vector<int2> h_flist;
+  std::vector<int> parent;     // [T] tile elimination tree: the first off-diagonal tile row of column k, -1 for a root
+};
+void tile_solve_plan_build(const LltPlan &P, TileSolvePlan &tp, hipStream_t s);
+void tile_solve_plan_free(TileSolvePlan &tp);
+// A panel's masks, [T] bytes each (both closed under the elimination tree's
+// ancestors; tile_solve_mark closes them): active: the tile rows where the
+// right-hand sides are non-zero -- the forward pass skips every other tile row
+// and every product with an inactive Y_j, all exactly zero; needed: the tile
+// rows of X somebody reads -- the backward pass computes those alone (a column
+// reads its ancestors only).
+void tile_solve_mark(const TileSolvePlan &tp, unsigned char *mask, long row);   // the tile of reduced row `row` and its ancestors
+// 64x64x64 tile products of one panel's solve under its masks (null: none), the diagonal inverses included
+long tile_solve_products(const LltPlan &P, const TileSolvePlan &tp, const unsigned char *active,
+                         const unsigned char *needed);
+// B: n_panels panels of 64 right-hand sides, each P.T row-major 64x64 tiles
+// (tile row k of panel p at B + (p T + k) 4096), rows >= nR zero; solved in
+// place against the factor in S (off-diagonal tiles) and P.ldiag, as
+// launch_dense_llt / launch_dense_llt_dag leave them -- not after
+// launch_selinv, which overwrites S.  Rows >= nR of X are zero.  active, needed:
+// device masks [n_panels * P.T] as above, or null for a full solve (tile rows
+// that are not needed keep their forward values).  Level launches on s; nothing
+// is written when *flag != 0.
+void launch_tile_solve(const LltPlan &P, const TileSolvePlan &tp, const double *S, long nR, double *B, int n_panels,
+                       const unsigned char *active, const unsigned char *needed, const int *flag, hipStream_t s);
+// A parameter block of the device problem: the focal, f-block idx (reduced
+// side) or e-block idx (eliminated side).  A panel holds kCovPanelBlocks
+// 6-column blocks and 4 zero columns, so no block straddles two panels.
+enum { kCovFocal = 0, kCovF = 1, kCovE = 2 };
+constexpr int kCovPanelBlocks = 10;
+// The right-hand sides of rhs[0 .. n_rhs) ({role, idx}, device) into the
+// zeroed panels B, block s in columns 6 (s % 10) .. of panel s / 10: unit
+// columns for the focal (one) and an f-block, -(R^{-1} G)^T scattered for an
+// e-block (from launch_cov_schur's G and R).
+void launch_cov_pair_rhs(const DevProblem &P, const double *Gb, const double *Rb, const int2 *rhs, int n_rhs,
+                         double *B, hipStream_t s);
+// Block (a, b) of the covariance from the solved panels X, b the block whose
+// columns sit in panel slot `slot`; 36 values (rows of a, columns of b; the
+// focal has one row / column, the rest 0) to out + 36 `out`, and status[out]:
+// 0 computed, 2 an e-block's R is singular or *flag != 0 (then -1).
+struct CovPairTask {
+  int role_a, idx_a, role_b, idx_b, slot, out;
+};
+// X may be null when there is no reduced system.
+void launch_cov_pair_blocks(const DevProblem &P, const double *X, const double *scale, const double *Gb,
+                            const double *Rb, const CovPairTask *tasks, int n_tasks, double *out, int *status,
+                            const int *flag, hipStream_t s);
+
 }  // namespace arslam

@@ -132,6 +132,7 @@ void arslam_lm::load(const arslam_soa_problem *p_in, const arslam::ObsLoss &in_l
   loaded = false;
   cov_invalidate();
   cov_sp_ready = false;
+  cov_tp_ready = false;
   // (the process's first HIP call starts the runtime, 0.02-0.2 s: the first
   // load of a process pays it here, in summary.setup_phase_s[0] -- round 4's
   // "1.2 ms per full load" was that one start averaged over 179 loads)

@@ -50,6 +50,7 @@ EXPORTS = ["arslam_lm_options_init", "arslam_lm_create", "arslam_lm_destroy",
            "arslam_debug_tile_llt", "arslam_debug_tile_plan",
            "arslam_debug_angle_axis_rotate", "arslam_debug_selinv", "arslam_lm_debug_force_indefinite",
            "arslam_lm_covariance", "arslam_lm_covariance_block", "arslam_lm_debug_reduced_rows",
+           "arslam_lm_covariance_pairs", "arslam_lm_covariance_block_pair", "arslam_debug_tile_solve",
            "arslam_lm_debug_force_multirank", "arslam_lm_debug_break_dependency", "arslam_lm_debug_tag_pair_tile",
            "arslam_debug_reduced_plan", "arslam_debug_reduced_plan_side", "arslam_debug_schur_stamps", "arslam_debug_ceres_e_blocks",
            "arslam_debug_mixed_groups",
@@ -157,6 +158,7 @@ class Summary(C.Structure):
 
 
 COV_OK, COV_UNAVAILABLE, COV_RANK_DEFICIENT = 0, 1, 2   # arslam_lm.h ARSLAM_COV_*
+BLOCK_CAMERA, BLOCK_CAPTURE, BLOCK_TAG = 0, 1, 2         # arslam_lm.h ARSLAM_BLOCK_* (covariance_pairs)
 
 
 class CovInfo(C.Structure):
@@ -276,6 +278,9 @@ def lib():
         L.arslam_debug_tile_plan.argtypes = [C.c_int, _up, _up, _up, C.c_void_p]
     L.arslam_lm_covariance.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip, _ip, C.POINTER(CovInfo)]
     L.arslam_lm_covariance_block.argtypes = [C.c_void_p, _dp, _dp, _ip]
+    L.arslam_lm_covariance_pairs.argtypes = [C.c_void_p, _ip, C.c_int, _dp, _ip, C.POINTER(CovInfo)]
+    L.arslam_lm_covariance_block_pair.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip]
+    L.arslam_debug_tile_solve.argtypes = [C.c_long, _dp, _up, C.c_int, _dp, _dp, _ip]
     L.arslam_lm_debug_reduced_rows.argtypes = [C.c_void_p, _ip, _ip, _ip]
     L.arslam_debug_ceres_e_blocks.argtypes = [C.POINTER(SoaProblem), _ip]
     L.arslam_debug_mixed_groups.argtypes = [C.POINTER(SoaProblem), _ip, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]
@@ -508,6 +513,22 @@ class ResidentProblem(_Handle):
         return {"cap": cap, "tag": tag, "var_f": var_f.value, "cap_status": cs[:n_cap], "tag_status": ts[:n_tag],
                 "info": info.to_dict()}
 
+    def covariance_pairs(self, pairs):
+        """Cross-covariance blocks at the point the last ``solve()`` returned
+        (arslam_lm_covariance_pairs).  pairs: a sequence of ((kind_a, index_a), (kind_b, index_b)),
+        kind BLOCK_CAMERA (index 0), BLOCK_CAPTURE or BLOCK_TAG.  Returns ``cov`` (n, 6, 6): rows
+        of a by columns of b (a pair with the camera: cov(f, pose) in the first six values, var(f)
+        at [0, 0] for the camera against itself, 0 elsewhere), ``status`` (n,) (COV_*) and ``info``."""
+        flat = np.ascontiguousarray([[a[0], a[1], b[0], b[1]] for a, b in pairs], np.int32).reshape(-1, 4)
+        n = len(flat)
+        cov = np.zeros((n, 6, 6))
+        st = np.zeros(max(n, 1), np.int32)
+        info = CovInfo()
+        _check(lib().arslam_lm_covariance_pairs(self._h, flat.ctypes.data_as(_ip) if n else None, C.c_int(n),
+                                                cov.ctypes.data_as(_dp) if n else None, st.ctypes.data_as(_ip),
+                                                C.byref(info)))
+        return cov, st[:n], info.to_dict()
+
     def debug_reduced_rows(self):
         """(cap_row (n_cap,), tag_row (n_tag,), cam_row): the first reduced row of each block, -1 off
         the reduced side (arslam_lm_debug_reduced_rows)."""
@@ -596,6 +617,19 @@ class Problem(_Handle):
         st = C.c_int(0)
         _check(lib().arslam_lm_covariance_block(self._h, block.ctypes.data_as(_dp), out.ctypes.data_as(_dp),
                                                 C.byref(st)))
+        return out, st.value
+
+    def covariance_block_pair(self, a, b):
+        """Covariance::GetCovarianceBlock(a, b) after ``solve()`` in Ceres' shapes -- (6, 6), (3, 6),
+        (6, 3) or (3, 3), the camera block 3 wide with cov(f, .) in its first row / column -- and its
+        status (COV_*) (arslam_lm_covariance_block_pair)."""
+        for blk in (a, b):
+            if not (isinstance(blk, np.ndarray) and blk.dtype == np.float64 and blk.size in (3, 6)):
+                raise TypeError("parameter block must be a float64 array of size 3 or 6")
+        out = np.zeros((a.size, b.size))
+        st = C.c_int(0)
+        _check(lib().arslam_lm_covariance_block_pair(self._h, a.ctypes.data_as(_dp), b.ctypes.data_as(_dp),
+                                                     out.ctypes.data_as(_dp), C.byref(st)))
         return out, st.value
 
     def reset(self):
@@ -745,6 +779,26 @@ def debug_selinv(A, tile_pattern=None):
                                      pat.ctypes.data_as(_up) if pat is not None else None,
                                      Z.ctypes.data_as(_dp), out.ctypes.data_as(_up), C.byref(info)))
     return Z, out, info.value
+
+
+def debug_tile_solve(A, B, tile_pattern=None):
+    """X = A^-1 B from the device's multi-right-hand-side tile solve alone (the step behind
+    ``covariance_pairs()``): A (n, n) SPD, factored as ``debug_selinv`` factors it, B (n, nrhs).
+    Returns (X (n, nrhs), info)."""
+    A = _f64(A)
+    n = A.shape[0]
+    B = np.ascontiguousarray(B, np.float64).reshape(n, -1)
+    T = (n + 1 + 63) // 64
+    pat = None
+    if tile_pattern is not None:
+        pat = np.ascontiguousarray(tile_pattern, np.uint8).reshape(T, T)
+    X = np.zeros_like(B)
+    info = C.c_int(0)
+    _check(lib().arslam_debug_tile_solve(C.c_long(n), A.ctypes.data_as(_dp),
+                                         pat.ctypes.data_as(_up) if pat is not None else None,
+                                         C.c_int(B.shape[1]), B.ctypes.data_as(_dp), X.ctypes.data_as(_dp),
+                                         C.byref(info)))
+    return X, info.value
 
 
 class PlanInfo(C.Structure):

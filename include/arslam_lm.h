@@ -384,6 +384,70 @@ int arslam_lm_covariance(arslam_lm *h, double *cov_cap, double *cov_tag, double 
  * pointer that is not a block of the problem. */
 int arslam_lm_covariance_block(arslam_lm *h, const double *block, double *cov, int *status);
 
+/* ---- cross-covariance blocks (ceres::Covariance::Compute(pairs), GetCovarianceBlock(a, b)) ----
+ * Block (a, b) of the same matrix C = H^-1 as arslam_lm_covariance: the same
+ * free-parameter set, loss-corrected rows, no LM diagonal, unit-variance
+ * residuals, at the point the last solve returned, in the gauge of whatever
+ * the caller held constant.  What the marginals cannot give: how well tag j is
+ * known relative to tag i (C_ii + C_jj - C_ij - C_ji over the translations), a
+ * capture relative to the tags it saw, the focal against a pose.
+ *
+ * A block is {kind, index}: ARSLAM_BLOCK_CAMERA (index 0), _CAPTURE or _TAG
+ * with the caller's index.  cov [n_pairs*36]: block (a, b) is rows of a by
+ * columns of b, row-major, 6x6 for two poses ([t, w] each).  With the camera in
+ * a pair the stride stays 36: for the focal against a pose, in either order,
+ * the first 6 values are cov(f, pose) and the other 30 are 0; camera against
+ * camera has var(f) at [0] and 0 elsewhere (l1 / l2 are never free).
+ *
+ * status [n_pairs] (nullable): ARSLAM_COV_UNAVAILABLE, and -1 in the 36
+ * values, if either block is constant or unused; ARSLAM_COV_RANK_DEFICIENT,
+ * and -1, for every other pair when the problem is rank deficient (the
+ * structural and numeric rule of arslam_lm_covariance, unchanged) or when an
+ * eliminated block of the pair is itself singular; ARSLAM_COV_OK otherwise.
+ * info (nullable) as in arslam_lm_covariance, except that n_selinv_products
+ * counts the 64x64x64 tile products of the triangular solves below and
+ * t_selinv_ms is their device time (t_blocks_ms: the right-hand sides and the
+ * blocks).
+ *
+ * (a, b) and (b, a) are transposes of the same bits -- each unordered pair is
+ * computed once, with a fixed choice of the side solved for, and transposed --
+ * (a, a) is exactly symmetric, a pair listed twice and a repeated call give
+ * the same bits, and a later solve returns what it would have returned without
+ * the call.  (a, a) agrees with the marginal of arslam_lm_covariance to
+ * rounding, not to the bit: the route differs.
+ *
+ * The device work: the linearization, reduced system and tile Cholesky of
+ * arslam_lm_covariance, then, instead of the selected inverse (which holds
+ * S^-1 only on the factor's tile pattern: two tags far apart under nested
+ * dissection share no tile), a forward and a backward triangular solve of the
+ * tile factor with six right-hand sides per distinct solved block, ten blocks
+ * to a 64-column panel, level by level over the elimination tree; then one
+ * wavefront per pair.  The panels go through in bounded batches, so device
+ * memory does not grow with n_pairs beyond the 36 values per distinct pair.
+ *
+ * Preconditions and errors as arslam_lm_covariance: ARSLAM_E_STATE without a
+ * completed solve, ARSLAM_E_UNSUPPORTED with several ranks and under
+ * ARSLAM_ELIM_MIXED (so not for the SLAM mirror, which runs MIXED and holds no
+ * block constant); an earlier arslam_lm_covariance call is neither needed nor
+ * in the way.  ARSLAM_E_INVALID_ARG for a bad kind or index or n_pairs < 0;
+ * n_pairs == 0 is OK.  Nothing is allocated or launched for this before its
+ * first call. */
+enum { ARSLAM_BLOCK_CAMERA = 0, ARSLAM_BLOCK_CAPTURE = 1, ARSLAM_BLOCK_TAG = 2 };
+typedef struct { int kind_a, index_a, kind_b, index_b; } arslam_lm_cov_pair;
+int arslam_lm_covariance_pairs(arslam_lm *h, const arslam_lm_cov_pair *pairs, int n_pairs,
+                               double *cov /* [n_pairs*36] */, int *status /* [n_pairs], nullable */,
+                               arslam_lm_cov_info *info /* nullable */);
+/* Covariance::GetCovarianceBlock(block_a, block_b, cov) for blocks added
+ * through arslam_lm_add_residual_block, in Ceres' shapes, row-major: 6x6 for
+ * two poses; 3x6 for the camera against a pose (row 0 = cov(f, pose)), 6x3 for
+ * a pose against the camera (column 0), 3x3 for the camera against itself
+ * (var(f) at [0]); the l1 / l2 rows and columns are 0, as in
+ * arslam_lm_covariance_block.  Computes on every call.  *status (nullable) =
+ * ARSLAM_COV_*; -1 in every value unless OK.  ARSLAM_E_INVALID_ARG for a
+ * pointer that is not a block of the problem. */
+int arslam_lm_covariance_block_pair(arslam_lm *h, const double *block_a, const double *block_b,
+                                    double *cov, int *status);
+
 /* Diagnostics */
 int arslam_device_count(void);
 const char *arslam_lm_last_error(void);

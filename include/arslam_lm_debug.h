@@ -99,6 +99,16 @@ int arslam_debug_tile_plan(int T, const unsigned char *tile_pattern, const unsig
 int arslam_debug_selinv(long n, const double *A, const unsigned char *tile_pattern, double *Z_out,
                         unsigned char *pattern_out, int *info);
 
+/* The multi-right-hand-side tile solve behind arslam_lm_covariance_pairs,
+ * alone: factor A exactly as arslam_debug_selinv does (zero right-hand side
+ * as row n, identity padding, optional tile pattern with symbolic fill) and
+ * return X = A^{-1} B from the forward and backward solve kernels over the
+ * factor's tiles.  B, X_out [n*nrhs] row-major; the columns travel sixty to a
+ * 64-column panel, as the covariance's blocks do.  info as in
+ * arslam_debug_selinv. */
+int arslam_debug_tile_solve(long n, const double *A, const unsigned char *tile_pattern, int nrhs, const double *B,
+                            double *X_out, int *info);
+
 /* The loaded problem's reduced rows, by the caller's blocks (one rank, capture
  * or tag elimination): cap_row [n_cap], tag_row [n_tag] = the first of the
  * block's 6 rows in the reduced system, -1 for a block that is eliminated,

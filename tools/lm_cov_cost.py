@@ -5,11 +5,14 @@ and covariance, then ROUNDS rounds of solve() + covariance().  Prints the four d
 covariance call (HIP events: linearization, reduced system + factorization, selected inverse,
 marginal blocks), one LM iteration's device time of the same problem (the solve's phase timers
 over its linear solves), their ratio, the tile products of the selected inverse against the
-factorization's, and the fp64 MFMA rate the selected inverse's time implies.
+factorization's, and the fp64 MFMA rate the selected inverse's time implies.  Then, on the same
+handle, covariance_pairs() for one pair and for 100 pairs over distinct tags (profiles/lm_cov_pairs):
+its device times, its tile products against the selected inverse's, and the host wall time of a call.
 
 usage: python tools/lm_cov_cost.py [rounds] [config]"""
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -62,6 +65,43 @@ def main():
     pos = np.sqrt(np.einsum("bii->b", out["tag"][ok_t][:, :3, :3]))
     print(f"  1-sigma tag position at 0.5 px: median {500 * np.median(pos):.3f} mm, largest {500 * pos.max():.3f} mm; "
           f"sigma_f {0.5 * np.sqrt(out['var_f']):.4f} px")
+    pairs_cost(rp, rounds, np.median(total), sel, np.nonzero(ok_t)[0])
+
+
+def pairs_cost(rp, rounds, cov_total_ms, selinv_products, tags):
+    """covariance_pairs() on the same handle, in the same process: one pair, and 100 pairs over 200
+    distinct tags (100 solved blocks: ten panels, three batches)."""
+    lists = {"1 pair": [((lm.BLOCK_TAG, int(tags[0])), (lm.BLOCK_TAG, int(tags[len(tags) // 2])))],
+             "100 pairs": [((lm.BLOCK_TAG, int(tags[2 * k])), (lm.BLOCK_TAG, int(tags[2 * k + 1]))) for k in range(100)]}
+    print(f"covariance_pairs on the same handle, medians of {rounds} rounds (min - max), device ms by HIP events "
+          "(selinv: the tile solves; blocks: right-hand sides and blocks)")
+    for label, pairs in lists.items():
+        t = {p: [] for p in PHASES}
+        wall = []
+        for r in range(1 + rounds):
+            rp.solve()
+            t0 = time.perf_counter()
+            cov, st, info = rp.covariance_pairs(pairs)
+            t1 = time.perf_counter()
+            assert np.all(st == lm.COV_OK)
+            if r == 0:
+                continue
+            wall.append(1e3 * (t1 - t0))
+            for p in PHASES:
+                t[p].append(info[p])
+        total = np.zeros(rounds)
+        line = []
+        for p in PHASES:
+            v = np.array(t[p])
+            total += v
+            line.append(f"{p[2:-3]} {np.median(v):.3f} ({v.min():.3f} - {v.max():.3f})")
+        prod = info["n_selinv_products"]
+        tf = 2.0 * 64 ** 3 * prod / (1e-3 * np.median(t["t_selinv_ms"])) / 1e12
+        print(f"  {label:9s} " + "; ".join(line))
+        print(f"  {'':9s} total {np.median(total):.3f} ({total.min():.3f} - {total.max():.3f}) = "
+              f"{np.median(total) / cov_total_ms:.2f} of a covariance() call; host wall {np.median(wall):.3f} ms; "
+              f"tile products {prod} = {prod / max(selinv_products, 1):.2f} of the selected inverse's {selinv_products}; "
+              f"the solves' time implies {tf:.2f} TFLOP/s fp64")
 
 
 if __name__ == "__main__":
