@@ -34,6 +34,7 @@
 // rows >= nR of every factor tile and rows and columns >= nR of L_kk^{-1} are
 // read as zero, so those rows contribute exactly nothing and stay zero in X.
 #include "llt_tile.h"
+#include "lm_cov.h"
 
 #include <algorithm>
 #include <stdexcept>

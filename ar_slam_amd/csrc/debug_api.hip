@@ -1,8 +1,13 @@
 // debug_api.hip -- component entry points (include/arslam_lm_debug.h) that run
 // one device stage in isolation so the parity tests can pin it to the oracle.
 #include <chrono>
-#include "lm_internal.h"
+#include "llt_plan.h"
+#include "lm_cov.h"
+#include "lm_launch.h"
+#include "lm_problem.h"
+#include "lm_rows.h"
 #include "loss.h"
+#include "projection.h"
 #include "schur_store_table.h"
 #include "arslam_lm.h"
 #include "arslam_lm_debug.h"
@@ -16,14 +21,83 @@
 #include <vector>
 
 namespace arslam {
-void debug_read_schur_stamps(unsigned long long *out);
+namespace {
+
+// one thread per (observation, row): residual and 15-column Jacobian row
+__global__ void k_debug_rj(int n, const double *__restrict__ cam, const double *__restrict__ cap,
+                           const double *__restrict__ tag, const double *__restrict__ corners,
+                           double *__restrict__ r, double *__restrict__ J) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= 8L * n) return;
+  const long o = e / 8;
+  const int row = (int)(e % 8), corner = row >> 1, comp = row & 1;
+  double j13[13];
+  r[e] = residual_jacobian_row(cam + 3 * o, cap + 6 * o, tag + 6 * o, corner, comp,
+                               corners[8 * o + row], j13);
+  double *out = J + e * 15;
+  out[0] = j13[0];
+  out[1] = 0.0;
+  out[2] = 0.0;
+  for (int j = 0; j < 12; ++j) out[3 + j] = j13[1 + j];
+}
+
+// the same rows corrected for each observation's loss (robustify_row, as
+// fill_rows<true> forms them) and rho(s) per observation; 8 n is a multiple of
+// 8, so an observation's 8 lanes are active together
+__global__ void k_debug_rj_loss(int n, const double *__restrict__ cam, const double *__restrict__ cap,
+                                const double *__restrict__ tag, const double *__restrict__ corners,
+                                const unsigned char *__restrict__ kind, const double *__restrict__ a,
+                                double *__restrict__ r, double *__restrict__ J, double *__restrict__ rho) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= 8L * n) return;
+  const long o = e / 8;
+  const int row = (int)(e % 8), corner = row >> 1, comp = row & 1;
+  double j13[13];
+  double rv = residual_jacobian_row(cam + 3 * o, cap + 6 * o, tag + 6 * o, corner, comp,
+                                    corners[8 * o + row], j13);
+  const double rh = robustify_row(kind[o], a[o], rv, j13);
+  r[e] = rv;
+  if (row == 0) rho[o] = rh;
+  double *out = J + e * 15;
+  out[0] = j13[0];
+  out[1] = 0.0;
+  out[2] = 0.0;
+  for (int j = 0; j < 12; ++j) out[3 + j] = j13[1 + j];
+}
+
+// AngleAxisRotatePoint of n (w, p) pairs with the branch each one took
+// (1: theta^2 > DBL_EPSILON, Rodrigues; 0: x + w x p) -- parity of the
+// small-angle branch, ar_slam_util.cpp:145,155.
+__global__ void k_debug_aa(int n, const double *__restrict__ w, const double *__restrict__ p,
+                           double *__restrict__ out, int *__restrict__ branch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const AngleAxis a = aa_prepare(w + 3L * i);
+  aa_rotate(a, p + 3L * i, out + 3L * i);
+  branch[i] = a.big ? 1 : 0;
+}
+
 void debug_residual_jacobian(int n, const double *cam, const double *cap, const double *tag,
-                             const double *corners, double *r, double *J, hipStream_t s);
+                             const double *corners, double *r, double *J, hipStream_t s) {
+  const long m = 8L * n;
+  hipLaunchKernelGGL(k_debug_rj, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, n, cam, cap, tag,
+                     corners, r, J);
+}
+
 void debug_residual_jacobian_loss(int n, const double *cam, const double *cap, const double *tag,
                                   const double *corners, const unsigned char *kind, const double *a, double *r,
-                                  double *J, double *rho, hipStream_t s);
-void debug_angle_axis(int n, const double *w, const double *p, double *out, int *branch, hipStream_t s);
+                                  double *J, double *rho, hipStream_t s) {
+  const long m = 8L * n;
+  hipLaunchKernelGGL(k_debug_rj_loss, dim3((unsigned)((m + 127) / 128)), dim3(128), 0, s, n, cam, cap, tag, corners,
+                     kind, a, r, J, rho);
 }
+
+void debug_angle_axis(int n, const double *w, const double *p, double *out, int *branch, hipStream_t s) {
+  hipLaunchKernelGGL(k_debug_aa, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, s, n, w, p, out, branch);
+}
+
+}  // namespace
+}  // namespace arslam
 
 namespace {
 int hip_fail(hipError_t e) { return e == hipSuccess ? ARSLAM_OK : ARSLAM_E_HIP; }

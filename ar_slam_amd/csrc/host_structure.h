@@ -17,7 +17,7 @@ namespace arslam {
 constexpr int kTileRows = 64;
 // the most distinct f-blocks (tags; captures under tag elimination) one
 // eliminated block may couple: its k_schur wave holds the local system in LDS
-// (lm_internal.h schur_lds_bytes; every ArUco dictionary the reference
+// (lm_problem.h schur_lds_bytes; every ArUco dictionary the reference
 // supports has at most 250 ids, aruco_detector.cpp:146-150)
 constexpr int kMaxSchurBlocks = 256;
 

@@ -14,7 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include "lm_internal.h"
+#include "llt_plan.h"
 
 #include <algorithm>
 #include <deque>

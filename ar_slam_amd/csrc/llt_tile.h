@@ -12,7 +12,8 @@
 // (profiles/llt_split/README.md).
 #pragma once
 
-#include "lm_internal.h"
+#include "llt_plan.h"
+#include "lm_problem.h"   // kTile
 
 #include <utility>
 

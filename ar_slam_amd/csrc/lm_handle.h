@@ -5,7 +5,10 @@
 // lm_capi.hip (the extern "C" entry points); only those include this header.
 #pragma once
 #include "host_threads.h"
-#include "lm_internal.h"
+#include "llt_plan.h"
+#include "lm_cov.h"
+#include "lm_launch.h"
+#include "lm_problem.h"
 #include "loss.h"
 #include "arslam_lm.h"
 #include "arslam_lm_debug.h"

@@ -12,7 +12,9 @@
 // radius update and termination rules -- no host
 // round trip until every query has terminated.  The control flow restates
 // the oracle's or_solve (oracle/arslam_oracle.c) for a single free block.
-#include "lm_internal.h"
+#include <hip/hip_runtime.h>
+
+#include "host_structure.h"
 #include "loss.h"
 #include "projection.h"
 #include "arslam_localize.h"

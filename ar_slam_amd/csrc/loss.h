@@ -1,7 +1,7 @@
 // loss.h -- the robust loss functions of a residual block (Ceres 2.0
 // loss_function.cc): rho(s) and rho'(s) of s = |r|^2, by kind and scale a.
-// Shared by the per-capture kernels (lm_kernels.hip: the corrected rows
-// sqrt(rho') r, sqrt(rho') J and the cost rho / 2), the debug entry
+// Shared by the per-capture kernels (lm_rows.h: the corrected rows
+// sqrt(rho') r, sqrt(rho') J; lm_step.hip: the cost rho / 2), the debug entry
 // arslam_debug_residual_jacobian_loss and the host's argument checks.
 //
 // Every loss here has rho'' <= 0, so Ceres' Corrector (corrector.cc) always

@@ -1,5 +1,5 @@
 // projection.h -- device restatement of the reference's residual and its
-// analytic Jacobian, shared by the per-capture LM kernels (lm_kernels.hip)
+// analytic Jacobian, shared by the per-capture LM kernels (lm_rows.h, lm_step.hip)
 // and the batched localizer (localize.hip).
 //
 //   projectCorner<T>            ar_slam_util.cpp:131-172

@@ -14,7 +14,7 @@
 #pragma once
 #include <cstdint>
 
-#include "lm_internal.h"
+#include "lm_problem.h"
 
 namespace arslam {
 

@@ -19,6 +19,7 @@
 // inverse of the leading block, so Z on the real rows is exact, and zero on
 // the others.
 #include "llt_tile.h"
+#include "lm_cov.h"
 
 #include <algorithm>
 

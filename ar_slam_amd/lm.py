@@ -865,7 +865,7 @@ def debug_dag_workgroup_limit(k):
 
 
 def debug_dag_fault_detail(g, rec):
-    """Host-only: the text an executor fault carries for fault record rec[8] (lm_internal.h
+    """Host-only: the text an executor fault carries for fault record rec[8] (llt_plan.h
     DagFaultField) on g's one-rank plan."""
     A = _Soa(g.camera, g.cap, g.tag, g.obs_cap, g.obs_tag, g.corners)
     r = (C.c_int * 9)(*([int(v) for v in rec] + [0] * (9 - len(rec))))
