@@ -760,6 +760,39 @@ extern "C" int arslam_debug_rank_split(const arslam_soa_problem *p, int nranks, 
   }
 }
 
+// Host-only: the task graph of the plan the solver makes for `rank` of `nranks` (1: the one-rank plan), in ticket
+// order: tasks[4 t ..] = {type, y, z, w} (LltPlan::h_dag_tasks) and phase[t], for the first `cap` tickets; *n_tasks
+// the plan's count; info = {tile columns T, phase_split, n_phases, root_inv_col}.
+extern "C" int arslam_debug_dag_tasks(const arslam_soa_problem *p, int nranks, int rank, int *tasks, int *phase,
+                                      long cap, long *n_tasks, int info[4]) {
+  if (!p || !n_tasks || !info || nranks < 1 || rank < 0 || rank >= nranks || cap < 0 || (cap > 0 && (!tasks || !phase)))
+    return ARSLAM_E_INVALID_ARG;
+  try {
+    const arslam::HostProblem h = arslam::host_problem(p, nullptr);
+    arslam::ReducedLayout L = arslam::reduced_layout(h, 2, true, nullptr, nullptr);
+    if (L.nR <= 0) throw arslam::ApiError(ARSLAM_E_INVALID_ARG, "no reduced system");
+    arslam::LltPlan plan;
+    if (nranks > 1) {
+      const std::vector<int> cls = arslam::rank_split(h, L, nranks).col_class(rank);
+      arslam::llt_plan_symbolic(plan, L.T, L.N, L.pattern, &cls);
+    } else {
+      arslam::llt_plan_symbolic(plan, L.T, L.N, L.pattern);
+    }
+    *n_tasks = plan.n_dag_tasks;
+    for (long t = 0; t < std::min(cap, plan.n_dag_tasks); ++t) {
+      const int4 k = plan.h_dag_tasks[t];
+      tasks[4 * t] = k.x, tasks[4 * t + 1] = k.y, tasks[4 * t + 2] = k.z, tasks[4 * t + 3] = k.w;
+      phase[t] = plan.h_dag_phase[t];
+    }
+    info[0] = plan.T, info[1] = (int)plan.phase_split, info[2] = plan.n_phases, info[3] = plan.root_inv_col;
+    return ARSLAM_OK;
+  } catch (const arslam::ApiError &e) {
+    return e.code;
+  } catch (...) {
+    return ARSLAM_E_INVALID_ARG;
+  }
+}
+
 extern "C" int arslam_debug_ceres_e_blocks(const arslam_soa_problem *p, int out[4]) {
   if (!p || !out) return ARSLAM_E_INVALID_ARG;
   try {

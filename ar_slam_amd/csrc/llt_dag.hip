@@ -168,6 +168,21 @@ static_assert(kShContMet0 + 1 < kShRec && kShInts % 2 == 0, "the slots fit befor
                          __HIP_MEMORY_SCOPE_SYSTEM);                                            \
   } while (0)
 
+// The trace's stamps between a POTRF's two publishes (kTrSolveTop .. kTrAcked,
+// tools/potrf_cont.py) exist only in a build with -DARSLAM_DAG_SUBSTAMPS
+// (ARSLAM_EXTRA_FLAGS): as run-time debug code like the other stamps they
+// reallocate the kernel (110 spilled SGPRs against 107), and at 256 VGPRs an
+// allocation is worth 1-4 %; the stretch is measured on a build of
+// its own and the library's kernel does not depend on them.
+#ifdef ARSLAM_DAG_SUBSTAMPS
+#define DAG_SUBSTAMP(word)                                                                      \
+  do {                                                                                          \
+    if (a.trace && tid == 0) a.trace[kDagTraceWords * (long)t + (word)] = realtime();           \
+  } while (0)
+#else
+#define DAG_SUBSTAMP(word) do {} while (0)
+#endif
+
 __global__ __launch_bounds__(256, kDagWorkgroupsPerCu) void k_factor_dag(DagArgs a) {
   // one LDS array carved per task type (POTRF: D, X, inv, LTd; GEMMs: sA, sB)
   // D | X | inv | LTd | the protocol's slots and record (DagShSlot) | colx
@@ -284,10 +299,10 @@ __global__ __launch_bounds__(256, kDagWorkgroupsPerCu) void k_factor_dag(DagArgs
       const int k = task.y;
       // The continuation's A_kk, prefetched by waves 2-3 into registers beside
       // the last POTRF panel once its early waits are met (apf: the target
-      // folds this task's solved tile alone, so A_kk is all it loads).  This
-      // task's tile stores are then made by waves 0-1 alone, so their release
-      // (s_waitcnt vmcnt(0)) never waits for those loads; waves 2-3 move the
-      // registers into D after the fused solve, as the target's A_kk.
+      // folds this task's solved tile alone, so A_kk is all it loads).  Waves
+      // 2-3 wait for those loads right after the solve anyway (they move the
+      // registers into D, as the target's A_kk), before the wait for their
+      // share of the solved tile's stores: the release never waits for them.
       const int c = sub.x >= 0 ? r[kRecCont] : -1;
       const int apf_tile = sub.x >= 0 ? r[kRecContAkk] : -1;
       const bool apf = apf_tile >= 0;
@@ -540,6 +555,7 @@ __global__ __launch_bounds__(256, kDagWorkgroupsPerCu) void k_factor_dag(DagArgs
           ap_ok = true;
         }
         __syncthreads();
+        DAG_SUBSTAMP(kTrSolveTop);
         // blocked_trsm64, its steps inline (row block w per wave), from the
         // first step not applied beside the last panel
         const int s0 = pref ? sh[kShSolveStep0 + w] : 0;
@@ -548,17 +564,24 @@ __global__ __launch_bounds__(256, kDagWorkgroupsPerCu) void k_factor_dag(DagArgs
         // drawer waits for this tile, so it cannot have claimed it yet.  (The
         // CAS goes out here and is answered beside the last two steps.)
         const bool want = c >= 0 && tid == 0 && a.t_begin + tk_seen > r[kRecContMaxdep] && infl_old < started_seen / 2;
+#ifdef ARSLAM_DAG_SUBSTAMPS
+        if (a.trace && tid == 0) asm volatile("" ::"v"(tk_seen), "v"(started_seen), "v"(infl_old));   // (the prelude's answers are in)
+#endif
+        DAG_SUBSTAMP(kTrWantKnown);
         int cas_old = 1;
         if (want) cas_old = atomicCAS(a.claimed + c, 0, 1);
         for (int st = max(s0, 2); st < 4; ++st) trsm_step(X, D, LTd, w, st, lane);
+        // every wave stores the row block it solved (no other wave wrote it)
+        // as soon as its own steps are done, its LDS reads in one batch; the
+        // acknowledgements come in beside the barrier and the A_kk move
+        store_elems_wt<64, 512>(Ct, X, 512 * w, lane, false);
         if (keep_flag && tid == 0)
           __hip_atomic_store(cu_flag + cu_key, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
-        // wave 1 stores the solved tile, waves 2-3 move the continuation's
-        // A_kk into D (free: L_kk's last reader was the solve)
-        if (w == 1) {
-          store_tile_wt<64>(Ct, X, tid - 64, false);
-        } else if (w >= 2) {
+        DAG_SUBSTAMP(kTrSolved);
+        // waves 2-3 move the continuation's A_kk into D (free: L_kk's last
+        // reader was the solve)
+        if (w >= 2) {
           if (ap_ok) {
             ld_wt16x16_wait(apv);
             const int t2 = tid - 128;
@@ -575,10 +598,12 @@ __global__ __launch_bounds__(256, kDagWorkgroupsPerCu) void k_factor_dag(DagArgs
           if (c >= 0 && claim < 0) atomicSub(inflight, 1);
           sh[kShClaim] = claim;
         }
-        // (wave 1 alone waits for the stores' acknowledgements; releasing
-        // the tile from the continuation instead was measured slower)
-        if (w == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // (every wave waits for its own stores' acknowledgements: waves 2-3
+        // have waited for A_kk by now, thread 0 for the claim's answer;
+        // releasing the tile from the continuation instead was measured slower)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
+        DAG_SUBSTAMP(kTrAcked);
         if (tid == 0) __hip_atomic_fetch_add(ready + sub.x, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (a.trace && tid == 0) {
           a.trace[kDagTraceWords * (long)t + kTrSubPublished] = realtime();
@@ -592,6 +617,21 @@ __global__ __launch_bounds__(256, kDagWorkgroupsPerCu) void k_factor_dag(DagArgs
         next = sh[kShClaim];
         next_met = next >= 0 && sh[kShContMet0] && sh[kShContMet0 + 1];
         if (next >= 0) prev_k = k;
+      } else if (r[kRecInv] > 0) {
+        // the root column: no fused tile, no continuation, and no INV task --
+        // L_kk and its block inverses are still in D and LTd, X is free, so the
+        // inverse is formed here (the INV branch's products in its order: the
+        // same bits) instead of closing the launch with a task that reloads them
+        blocked_trinv64(D, LTd, X, tid);
+        __syncthreads();
+        double *Xg = a.Ld + ((long)a.T + k) * T64 * T64;
+        // (fully unrolled, where the INV branch unrolls by 4: with this loop at
+        // 1, 2, 4 or 8 the kernel spills an eighth VGPR, 36 B of scratch per lane)
+#pragma unroll
+        for (int m = 0; m < 16; ++m) {
+          const int e = m * 256 + tid, row = e >> 6, col = e & 63;
+          Xg[e] = (row >= col) ? X[col * LQ + row] : 0.0;   // read by the next kernel only
+        }
       }
     } else if (task.x == 3) {
       // ---- INV k: L_kk^{-1} for the backward solve (off the critical chain) ----

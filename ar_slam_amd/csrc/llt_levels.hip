@@ -206,8 +206,8 @@ __global__ void k_init_z(const double *__restrict__ S, const int *__restrict__ t
 //   k_bs_gather: one workgroup per gathered tile (i,k) (i > k, an ancestor
 //     already solved): part_g = L_ik^T y_i, stored to its own slot;
 //   k_bs_solve:  one workgroup per column k: sums its gathers' partials in
-//     plan order (deterministic: every rank of a sharded solve computes the
-//     same bits), then solves L_kk^T y_k = z_k - sum (lane r owns row r,
+//     the plan's order reversed (deterministic: every rank of a sharded solve
+//     computes the same bits; k_bsolve_dag's order), then solves L_kk^T y_k = z_k - sum (lane r owns row r,
 //     16-row blocks, scalar broadcasts of y).
 __global__ __launch_bounds__(256) void k_bs_gather(const double *__restrict__ S,
                                                    const int *__restrict__ tid_map, int T, long nR,
@@ -221,17 +221,19 @@ __global__ __launch_bounds__(256) void k_bs_gather(const double *__restrict__ S,
   const int2 t = tasks[blockIdx.x];
   const long ri = (long)t.x * T64;
   const double *Lik = tile_ptr(S, tid_map, T, t.x, t.y);
-  double a0 = 0.0, a1 = 0.0;
+  // (wave w: rows w, w + 4, ... into one accumulator, then the four waves'
+  // sums left to right -- k_bsolve_dag's order, so the two executors give the
+  // same bits of y)
+  double a = 0.0;
 #pragma unroll
-  for (int r = w; r < T64; r += 8) {
-    const double y0 = (ri + r < nR) ? yF[ri + r] : 0.0;
-    const double y1 = (ri + r + 4 < nR) ? yF[ri + r + 4] : 0.0;
-    a0 += Lik[r * T64 + lane] * y0;
-    a1 += Lik[(r + 4) * T64 + lane] * y1;
+  for (int m = 0; m < 16; ++m) {
+    const int r = w + 4 * m;
+    const double y = (ri + r < nR) ? yF[ri + r] : 0.0;
+    a += Lik[r * T64 + lane] * y;
   }
-  part[w][lane] = a0 + a1;
+  part[w][lane] = a;
   __syncthreads();
-  if (w == 0) part_out[(long)blockIdx.x * T64 + lane] = part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane];
+  if (w == 0) part_out[(long)blockIdx.x * T64 + lane] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
 }
 
 // y_k = L_kk^{-T} (z_k - sum of the column's gathered partials), with the
@@ -253,12 +255,14 @@ __global__ __launch_bounds__(256) void k_bs_solve(const double *__restrict__ Xin
   if (w == 0) {
     double acc = 0.0;
     const int ga = gbeg[blockIdx.x], gb = gbeg[blockIdx.x + 1];
-    for (int g = ga; g < gb; g += 8) {   // 8 loads in flight, summed in plan order
+    // 8 loads in flight, summed from the end of the plan's list to its start:
+    // the nearest ancestor last, as k_bsolve_dag sums them
+    for (int g = gb - 1; g >= ga; g -= 8) {
       double v[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = part[(long)min(g + u, gb - 1) * T64 + lane];
+      for (int u = 0; u < 8; ++u) v[u] = part[(long)max(g - u, ga) * T64 + lane];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) acc += (g + u < gb) ? v[u] : 0.0;
+      for (int u = 0; u < 8; ++u) acc += (g - u >= ga) ? v[u] : 0.0;
     }
     accs[lane] = (row0 + lane < nR) ? z[row0 + lane] - acc : 0.0;
   }

@@ -342,12 +342,23 @@ void dag_build(LltPlan &plan) {
   }
   // L_kk^{-1} of every column (for the backward solve) as its own task, off
   // the chain: the POTRF task can go straight on to its parent
+  // The root column (the last tile column, when its POTRF ends the last phase
+  // and has no fused tile: nothing follows it on its workgroup) has no INV
+  // task: its POTRF task inverts the L_kk it still holds in LDS (kRecInv), so
+  // the launch does not end with a task that reloads what was just stored.
+  // Of a multi-rank plan only the true root qualifies, never phase 0's last column.
+  auto inv_phase = [&](int k) { return plan.h_col_class.empty() ? 0 : (plan.h_col_class[k] == 1 ? 1 : 0); };
+  plan.root_inv_col = -1;
+  for (const Node &n : nodes)
+    if (n.type == 0 && n.task.y == T - 1 && n.sub < 0 && n.phase == std::max(plan.n_phases, 1) - 1 &&
+        inv_phase(T - 1) == n.phase)
+      plan.root_inv_col = T - 1;
   for (int k = 0; k < T; ++k) {
-    if (tid(k, k) < 0) continue;
+    if (tid(k, k) < 0 || k == plan.root_inv_col) continue;
     Node n;
     n.type = 3;
     n.idx = k;
-    n.phase = plan.h_col_class.empty() ? 0 : (plan.h_col_class[k] == 1 ? 1 : 0);
+    n.phase = inv_phase(k);
     n.task = make_int4(3, k, 0, tid(k, k));
     n.waits.push_back(make_int2(tid(k, k), 1));
     nodes.push_back(std::move(n));
@@ -472,6 +483,7 @@ void dag_build(LltPlan &plan) {
       if (c >= 0)
         r[kRecContMaxdep] = plan.h_dag_maxdep[c], r[kRecContWait0] = plan.h_dag_wait_off[c],
         r[kRecContLate] = plan.h_dag_sub[c].y;
+      if (tk.x == 0 && tk.y == plan.root_inv_col) r[kRecInv] = 1;
       if (tk.x == 0 && tk.z >= 0) {
         const int4 it = plan.h_items[tk.z];
         r[kRecQ0] = it.y, r[kRecQ1] = it.z, r[kRecFoldK0] = plan.h_ks[it.y], r[kRecFoldTile0] = tid(tk.y, plan.h_ks[it.y]);

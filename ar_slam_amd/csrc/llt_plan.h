@@ -50,6 +50,7 @@ enum DagRecField {
   kRecSub, kRecLate, kRecWait0, kRecWait1,     // fused TRSM tile, start of the late waits, the wait list
   kRecCont, kRecContAkk, kRecMaxdep,           // continuation target, its A_kk tile, own maxdep
   kRecContMaxdep, kRecContWait0, kRecContLate, // the target's maxdep and early-wait range
+  kRecInv,                                     // POTRF: 1 if the task also inverts L_kk (the root column: no INV task)
   kRecQ0 = 16, kRecQ1,                         // POTRF fold / update item: columns [q0, q1) of ks
   kRecFoldK0, kRecFoldTile0,                   // POTRF: ks[q0] and tid(k, ks[q0])
   kRecSid = 18, kRecTi, kRecTj,                // update item: split slot, target tile (ti, tj)
@@ -71,8 +72,16 @@ enum DagTraceWord {
   kTrFactored = 5,       // POTRF: factorized; TRSM: solved
   kTrPublished = 6,      // POTRF: L_kk published
   kTrSubPublished = 7,   // POTRF: the fused tile published (0: none)
-  kDagTraceWords = 8
+  // POTRF with a fused tile, the stretch between the two publishes (tools/potrf_cont.py; the trace file keeps
+  // these four words in a block of their own behind the others, [n_tasks][kDagTraceSubWords]):
+  kTrSolveTop = 8,       // the fused tile is in X and every wave is at the solve (the barrier before it)
+  kTrWantKnown = 9,      // the claim's ticket count, started count and reservation are in hand
+  kTrSolved = 10,        // every wave's solve steps are done (the barrier after them)
+  kTrAcked = 11,         // the solved tile's stores are acknowledged (the barrier before its publish)
+  kDagTraceWords = 12
 };
+constexpr int kDagTraceFileWords = 8;   // the words of a ticket in the trace file's main block
+constexpr int kDagTraceSubWords = kDagTraceWords - kDagTraceFileWords;
 // and a workgroup's host-visible progress ints (launch_dense_llt_dag's progress, [grid][kDagProgressInts]):
 enum DagProgressSlot {
   kProgTicket = 0,   // the ticket in hand
@@ -146,6 +155,9 @@ struct LltPlan {
   std::vector<int2> h_dag_sub;
   int *dag_claimed = nullptr;
   std::vector<int> h_dag_cont, h_dag_maxdep, h_dag_cont_akk;
+  // the column whose POTRF task also computes L_kk^{-1} (kRecInv) and that has
+  // no INV task: the last tile column when it ends the last phase, else -1
+  int root_inv_col = -1;
   // dag_rec[32 t ..]: every field the executor reads about ticket t, in one
   // 128-byte record (kDagRec* offsets), fetched with two scalar loads -- the
   // separate arrays were a chain of dependent loads (task -> item -> column

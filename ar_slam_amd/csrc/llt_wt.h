@@ -330,6 +330,27 @@ __device__ __forceinline__ void store_tile_wt(double *__restrict__ g, const doub
   }
 }
 
+// NE elements (16 bytes each, from element e0 on) of an LDS tile by NT threads,
+// every LDS read of the thread issued before its first store.  st_wt16 is a
+// compiler barrier, so in store_tile_wt's loop each read waits behind the store
+// before it: one LDS round trip per element, in sequence.  (k_factor_dag's
+// chain stores only: the other users of store_tile_wt keep their code.)
+template <int NT, int NE>
+__device__ __forceinline__ void store_elems_wt(double *__restrict__ g, const double *lds, int e0, int tid, bool lower) {
+  dbl2 v[NE / NT];
+#pragma unroll
+  for (int q = 0; q < NE / NT; ++q) {
+    const int e = e0 + q * NT + tid, r = e >> 5, c2 = (e & 31) * 2;
+    v[q] = *reinterpret_cast<const dbl2 *>(lds + r * LQ + c2);
+    if (lower) {
+      if (c2 > r) v[q].x = 0.0;
+      if (c2 + 1 > r) v[q].y = 0.0;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < NE / NT; ++q) st_wt16(g + 2 * (e0 + q * NT + tid), v[q]);
+}
+
 // wave 0: spin until counter[idx] >= val for every wait; false on timeout,
 // or at once when another workgroup already timed out (flag < 0), so a
 // broken graph drains in one spin cap instead of one per task.  Lane q polls

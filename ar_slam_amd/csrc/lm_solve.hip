@@ -346,12 +346,15 @@ void arslam_lm::dump_dag_trace(long first_store) {
     const long n = plan.n_dag_tasks;
     std::fwrite(&n, 8, 1, f);
     std::fwrite(plan.h_dag_tasks.data(), sizeof(int4), n, f);
-    std::fwrite(h.data(), 8, h.size(), f);
+    // (a ticket's first kDagTraceFileWords words here; the rest in a block of their own at the end)
+    for (long t = 0; t < n; ++t) std::fwrite(h.data() + t * arslam::kDagTraceWords, 8, arslam::kDagTraceFileWords, f);
     const long nw = (long)plan.h_dag_waits.size();   // the dependency lists, for dag_critical.py
     std::fwrite(&nw, 8, 1, f);
     std::fwrite(plan.h_dag_wait_off.data(), sizeof(int), n + 1, f);
     std::fwrite(plan.h_dag_waits.data(), sizeof(int2), nw, f);
     std::fwrite(plan.h_dag_sub.data(), sizeof(int2), n, f);   // fused TRSM tiles
+    for (long t = 0; t < n; ++t)   // the stamps between a POTRF's two publishes, for potrf_cont.py
+      std::fwrite(h.data() + t * arslam::kDagTraceWords + arslam::kDagTraceFileWords, 8, arslam::kDagTraceSubWords, f);
     std::fclose(f);
   }
   g_dag_traced = true;

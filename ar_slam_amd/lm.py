@@ -57,6 +57,7 @@ EXPORTS = ["arslam_lm_options_init", "arslam_lm_create", "arslam_lm_destroy",
            "arslam_debug_dag_simulate", "arslam_debug_dag_simulate_started", "arslam_debug_dag_workgroup_limit",
            "arslam_debug_dag_fault_detail", "arslam_debug_box_fingerprint",
            "arslam_debug_rank_split", "arslam_debug_gather_extend", "arslam_debug_schur_store_table",
+           "arslam_debug_dag_tasks",
            "arslam_localize_many", "arslam_localizer_create", "arslam_localizer_destroy",
            "arslam_localizer_load", "arslam_localizer_solve",
            "arslam_localizer_set_loss", "arslam_localizer_get_loss", "arslam_localizer_load_loss",
@@ -293,6 +294,9 @@ def lib():
         L.arslam_lm_debug_tag_pair_tile.argtypes = [C.c_void_p, _dp, _dp, C.POINTER(C.c_int)]
     if hasattr(L, "arslam_debug_schur_store_table"):   # (likewise)
         L.arslam_debug_schur_store_table.argtypes = [C.c_int, _ip, C.POINTER(C.c_ubyte)]
+    if hasattr(L, "arslam_debug_dag_tasks"):   # (likewise)
+        L.arslam_debug_dag_tasks.argtypes = [C.POINTER(SoaProblem), C.c_int, C.c_int, _ip, _ip, C.c_long,
+                                             C.POINTER(C.c_long), _ip]
     _lib = L
     return L
 
@@ -910,6 +914,21 @@ def debug_rank_split(camera, cap, tag, obs_cap, obs_tag, corners, nranks, rank):
     owner = np.zeros(max(A.cap.shape[0], 1), np.int32)
     _check(lib().arslam_debug_rank_split(C.byref(A.s), nranks, rank, C.byref(info), owner.ctypes.data_as(_ip)))
     return {f: getattr(info, f) for f, _ in SplitInfo._fields_}, owner[:A.cap.shape[0]]
+
+
+def debug_dag_tasks(g, nranks=1, rank=0):
+    """Host-only: the factorization's task graph in the plan the solver makes for `rank` of `nranks`
+    (1: the one-rank plan).  Returns {"tasks": [n, 4] (type, y, z, w; type 0 POTRF k = y, 1 TRSM,
+    2 update item, 3 INV k = y) in ticket order, "phase": [n], "T", "phase_split", "n_phases",
+    "root_inv_col": the column whose POTRF task also inverts L_kk and that has no INV task, or -1}."""
+    A = _Soa(g.camera, g.cap, g.tag, g.obs_cap, g.obs_tag, g.corners)
+    n, info = C.c_long(0), (C.c_int * 4)()
+    _check(lib().arslam_debug_dag_tasks(C.byref(A.s), int(nranks), int(rank), None, None, 0, C.byref(n), info))
+    tasks, phase = np.zeros((max(n.value, 1), 4), np.int32), np.zeros(max(n.value, 1), np.int32)
+    _check(lib().arslam_debug_dag_tasks(C.byref(A.s), int(nranks), int(rank), tasks.ctypes.data_as(_ip),
+                                        phase.ctypes.data_as(_ip), n.value, C.byref(n), info))
+    return {"tasks": tasks[:n.value], "phase": phase[:n.value], "T": info[0], "phase_split": info[1],
+            "n_phases": info[2], "root_inv_col": info[3]}
 
 
 def debug_ceres_e_blocks(camera, cap, tag, obs_cap, obs_tag, corners=None, camera_const=False, cap_const=None,

@@ -254,6 +254,14 @@ typedef struct {
 } arslam_split_info;
 int arslam_debug_rank_split(const arslam_soa_problem *p, int nranks, int rank, arslam_split_info *info,
                             int *cap_owner);
+/* Host-only: the factorization's task graph in the plan the solver makes for
+ * `rank` of `nranks` (1: the one-rank plan), in ticket order: tasks[4 t ..] =
+ * {type, y, z, w} (0 POTRF k = y; 1 TRSM; 2 update item; 3 INV k = y) and
+ * phase[t], for the first `cap` tickets; *n_tasks the plan's count; info =
+ * {tile columns T, phase_split, phases, the column whose POTRF task also
+ * inverts L_kk and that has no INV task (-1: none)}. */
+int arslam_debug_dag_tasks(const arslam_soa_problem *p, int nranks, int rank, int *tasks, int *phase, long cap,
+                           long *n_tasks, int info[4]);
 /* Host-only: the Schur gather plan of p's first c0 captures (their residual
  * blocks, p's order), extended by captures c0.. (schur_gather_extend, the
  * appended-problem path), against the plan built afresh for all of p with the

@@ -82,3 +82,26 @@ for t in last:
             for s_, u in applied_prod.get(int(c) - n_tiles, []):
                 if s_ < v and us[u, 2] > best: best, who = us[u, 2], ("UPD", int(u))
     print(f"{tasks[t, 1]:4d} {us[t, 5]:9.1f} {best:10.1f} {us[t, 5] - best:6.1f}  {who}")
+# the stretch between the two publishes of those links (kTrSolveTop .. kTrAcked, thread 0's stamps; a block of its
+# own at the end of the file): L_kk published -> every wave at the solve -> the claim's prelude answered -> solve
+# steps done (barrier) -> the solved tile's stores acknowledged (barrier) -> its publish
+# (all zero unless the library was built with -DARSLAM_DAG_SUBSTAMPS)
+raw = f.read(32 * n)
+if len(raw) == 32 * n and np.frombuffer(raw, np.uint64).any():
+    ss = (np.frombuffer(raw, np.uint64).reshape(n, 4).astype(np.int64) - t0) / 100.0
+    rows = []
+    print("   k  publ->top  ->want  ->solved  ->acked  ->subpub   total  flags(premet,AkkD,pref,next_met,claim) cont")
+    for t in last:
+        if sub[t, 0] < 0 or us[t, 7] <= 0:
+            continue
+        u, s_ = us[t], ss[t]
+        d = [s_[0] - u[6], s_[1] - s_[0], s_[2] - s_[1], s_[3] - s_[2], u[7] - s_[3], u[7] - u[6]]
+        rows.append((int(flags[t]), d))
+        print(f"{tasks[t, 1]:4d} {d[0]:9.2f} {d[1]:7.2f} {d[2]:9.2f} {d[3]:8.2f} {d[4]:9.2f} {d[5]:7.2f}"
+              f"   {int(flags[t]):05b}  {'c' if t in cont else '-'}")
+    for nm, want_pref in (("pref", 4), ("not pref", 0)):
+        sel = np.array([d for fl_, d in rows if (fl_ & 4) == want_pref])
+        if len(sel):
+            print(f"mean {nm:8s} n={len(sel):3d} " + " ".join(f"{v:7.2f}" for v in sel.mean(axis=0)) +
+                  "   median " + " ".join(f"{v:7.2f}" for v in np.median(sel, axis=0)))
+    print("claimed on these links: %d of %d" % (sum(1 for fl_, _ in rows if fl_ & 16), len(rows)))
