@@ -8,6 +8,7 @@
 
 #include <cstdint>
 #include <functional>
+#include <new>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -32,6 +33,28 @@ void set_last_error(const std::string &msg);
 
 inline void api_check(bool ok, int code, const char *msg) {
   if (!ok) throw ApiError(code, msg);
+}
+
+// The C boundary of the HIP library's entry points: runs f and turns what it
+// throws into the C-ABI code, leaving the text for arslam_lm_last_error().
+template <class F>
+int api_guarded(F &&f) {
+  try {
+    f();
+    return ARSLAM_OK;
+  } catch (const ApiError &e) {
+    set_last_error(e.what());
+    return e.code;
+  } catch (const std::bad_alloc &) {
+    set_last_error("host out of memory");
+    return ARSLAM_E_OUT_OF_MEMORY;
+  } catch (const std::exception &e) {
+    set_last_error(e.what());
+    return ARSLAM_E_HIP;
+  } catch (...) {
+    set_last_error("unknown error");
+    return ARSLAM_E_HIP;
+  }
 }
 
 // In-place all-reduce hooks of the capture-sharded path (null: one rank).

@@ -1017,6 +1017,22 @@ bool dag_simulate(const LltPlan &plan, int n_workers, unsigned seed, int policy,
   return true;
 }
 
+// 448 is the executor's grid (1.75 per CU on 256 CUs); `small` the small-graph rule of launch_dense_llt_dag.
+int dag_simulate_all(const LltPlan &plan) {
+  const long n = plan.n_dag_tasks;
+  const int small = (int)std::min<long>(448, std::max<long>(std::min<long>(64, n), n / 4));
+  for (int wk : {1, 2, 7, 64, small, 448, 512})
+    for (int pol = 0; pol < kDagSimPolicies; ++pol)
+      for (unsigned seed = 1; seed <= (pol == 0 || pol == 3 ? 3u : 1u); ++seed)
+        if (!dag_simulate(plan, wk, seed, pol)) return -(wk * 16 + pol);
+  // a 448-workgroup grid of which only k ever become resident (a GPU shared
+  // with another process, or several ranks' launches on one GPU)
+  for (int k : {1, 2, 7, 64})
+    for (int pol = 0; pol < kDagSimPolicies; ++pol)
+      if (!dag_simulate(plan, 448, 1u, pol, k)) return -(100000 * k + 448 * 16 + pol);
+  return 1;
+}
+
 std::string dag_fault_detail(const LltPlan &plan, const int *rec) {
   const long nt = plan.n_tiles, n = plan.n_dag_tasks;
   const int t = rec[kFaultTicket], ctr = rec[kFaultCounter];

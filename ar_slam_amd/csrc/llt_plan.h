@@ -224,6 +224,10 @@ bool dag_simulate(const LltPlan &plan, int n_workers, unsigned seed, int policy 
 constexpr int kDagSimPolicies = 4;
 constexpr int kDagSimNoCap = 16;
 constexpr int kDagSimGridCap = 32;   // (tests) round 5's cap: half the grid, not half the started workgroups
+// dag_simulate over small grids, the executor's own and 512, every policy, and
+// grids of which only a few workgroups start: 1 if deadlock-free in every run,
+// else -(grid * 16 + policy) of the first deadlock (-100000 k more when only k started).
+int dag_simulate_all(const LltPlan &plan);
 // The fault record of a timed-out executor wait (kDagFault*) in words: the
 // stuck task, the awaited counter, its producers and how far the launch drew.
 std::string dag_fault_detail(const LltPlan &plan, const int *rec);

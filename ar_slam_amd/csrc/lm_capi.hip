@@ -1,6 +1,6 @@
 // lm_capi.hip -- the C-ABI of include/arslam_lm.h over the LM handle
 // (lm_handle.h): argument checks, the pointer-keyed problem's staging, and
-// the translation of exceptions into error codes.
+// the translation of exceptions into error codes (api_guarded).
 #include "lm_handle.h"
 
 arslam_lm::~arslam_lm() {
@@ -28,28 +28,6 @@ thread_local std::string g_last_error;
 namespace arslam {
 void set_last_error(const std::string &msg) { g_last_error = msg; }
 }  // namespace arslam
-namespace {
-template <class F>
-int guarded(F &&f) {
-  try {
-    f();
-    return ARSLAM_OK;
-  } catch (const Error &e) {
-    g_last_error = e.what();
-    return e.code;
-  } catch (const std::bad_alloc &) {
-    g_last_error = "host out of memory";
-    return ARSLAM_E_OUT_OF_MEMORY;
-  } catch (const std::exception &e) {
-    g_last_error = e.what();
-    return ARSLAM_E_HIP;
-  } catch (...) {
-    g_last_error = "unknown error";
-    return ARSLAM_E_HIP;
-  }
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -83,7 +61,7 @@ int arslam_lm_options_init(arslam_lm_options *o) {
 int arslam_lm_create(arslam_lm **out, const arslam_lm_options *opt) {
   if (!out) return ARSLAM_E_INVALID_ARG;
   *out = nullptr;
-  return guarded([&] {
+  return arslam::api_guarded([&] {
     auto *h = new arslam_lm();
     if (opt) h->opt = *opt; else arslam_lm_options_init(&h->opt);
     if (h->opt.elimination < ARSLAM_ELIM_AUTO || h->opt.elimination > ARSLAM_ELIM_MIXED) {
@@ -98,7 +76,7 @@ void arslam_lm_destroy(arslam_lm *h) { delete h; }
 
 int arslam_lm_set_options(arslam_lm *h, const arslam_lm_options *opt) {
   if (!h || !opt) return ARSLAM_E_INVALID_ARG;
-  return guarded([&] {
+  return arslam::api_guarded([&] {
     fail_if(opt->elimination < ARSLAM_ELIM_AUTO || opt->elimination > ARSLAM_ELIM_MIXED, ARSLAM_E_INVALID_ARG,
             "elimination must be ARSLAM_ELIM_AUTO, _CAPTURES, _TAGS or _MIXED");
     fail_if(opt->factor_executor != 0 && opt->factor_executor != 1, ARSLAM_E_INVALID_ARG,
@@ -123,7 +101,7 @@ int arslam_lm_get_options(const arslam_lm *h, arslam_lm_options *opt) {
 
 int arslam_lm_set_loss(arslam_lm *h, int kind, double a) {
   if (!h) return ARSLAM_E_INVALID_ARG;
-  return guarded([&] {
+  return arslam::api_guarded([&] {
     fail_if(!arslam::loss_valid(kind, a), ARSLAM_E_INVALID_ARG,
             "loss: kind must be ARSLAM_LOSS_NONE, _HUBER, _SOFT_L_ONE or _CAUCHY, its scale finite and > 0");
     h->def_loss_kind = kind;
@@ -151,7 +129,7 @@ int arslam_lm_add_residual_block(arslam_lm *h, const double corners[8], double *
 int arslam_lm_add_residual_block_loss(arslam_lm *h, const double corners[8], double *camera,
                                       double *capture, double *tag, int kind, double a) {
   if (!h || !corners || !camera || !capture || !tag) return ARSLAM_E_INVALID_ARG;
-  return guarded([&] {
+  return arslam::api_guarded([&] {
     fail_if(!arslam::loss_valid(kind, a), ARSLAM_E_INVALID_ARG,
             "loss: kind must be ARSLAM_LOSS_NONE, _HUBER, _SOFT_L_ONE or _CAUCHY, its scale finite and > 0");
     fail_if(h->camera_ptr && h->camera_ptr != camera, ARSLAM_E_UNSUPPORTED,
@@ -191,7 +169,7 @@ int arslam_lm_add_residual_block_loss(arslam_lm *h, const double corners[8], dou
 
 int arslam_lm_set_parameter_block_constant(arslam_lm *h, double *block) {
   if (!h || !block) return ARSLAM_E_INVALID_ARG;
-  return guarded([&] {
+  return arslam::api_guarded([&] {
     fail_if(block != h->camera_ptr && !h->cap_of.count(block) && !h->tag_of.count(block),
             ARSLAM_E_INVALID_ARG, "parameter block is not part of the problem");
     if (h->constant.insert(block).second) h->pk_dirty = true, h->pk_appended_only = false;
@@ -200,7 +178,7 @@ int arslam_lm_set_parameter_block_constant(arslam_lm *h, double *block) {
 
 int arslam_lm_set_parameter_block_variable(arslam_lm *h, double *block) {
   if (!h || !block) return ARSLAM_E_INVALID_ARG;
-  return guarded([&] {
+  return arslam::api_guarded([&] {
     if (h->constant.erase(block)) h->pk_dirty = true, h->pk_appended_only = false;
   });
 }
@@ -211,7 +189,7 @@ int arslam_lm_num_residual_blocks(const arslam_lm *h) {
 
 int arslam_lm_solve(arslam_lm *h, arslam_lm_summary *summary) {
   if (!h || !summary) return ARSLAM_E_INVALID_ARG;
-  return guarded([&] {
+  return arslam::api_guarded([&] {
     std::memset(summary, 0, sizeof(*summary));
     if (h->pk_obs_cap.empty()) {   // empty problem: nothing to do (Ceres returns immediately)
       summary->termination = ARSLAM_CONVERGENCE;
@@ -262,7 +240,7 @@ int arslam_lm_solve(arslam_lm *h, arslam_lm_summary *summary) {
 
 int arslam_lm_reset(arslam_lm *h) {
   if (!h) return ARSLAM_E_INVALID_ARG;
-  return guarded([&] {
+  return arslam::api_guarded([&] {
     h->camera_ptr = nullptr;
     h->cap_of.clear(); h->tag_of.clear();
     h->cap_ptrs.clear(); h->tag_ptrs.clear();
@@ -285,7 +263,7 @@ int arslam_lm_load_soa(arslam_lm *h, const arslam_soa_problem *p) {
 int arslam_lm_load_soa_loss(arslam_lm *h, const arslam_soa_problem *p, const unsigned char *obs_loss_kind,
                             const double *obs_loss_a) {
   if (!h || !p || (obs_loss_kind == nullptr) != (obs_loss_a == nullptr)) return ARSLAM_E_INVALID_ARG;
-  return guarded([&] {
+  return arslam::api_guarded([&] {
     fail_if(p->n_obs < 0, ARSLAM_E_INVALID_ARG, "negative sizes");   // (before n_obs sizes anything here)
     if (obs_loss_kind)
       for (int b = 0; b < p->n_obs; ++b)
@@ -302,7 +280,7 @@ int arslam_lm_load_soa_loss(arslam_lm *h, const arslam_soa_problem *p, const uns
 
 int arslam_lm_solve_loaded(arslam_lm *h, arslam_lm_summary *summary) {
   if (!h || !summary) return ARSLAM_E_INVALID_ARG;
-  return guarded([&] {
+  return arslam::api_guarded([&] {
     fail_if(h->pk_loaded, ARSLAM_E_STATE, "no problem loaded by arslam_lm_load_soa");
     h->solve(summary);
   });
@@ -314,7 +292,7 @@ int arslam_lm_solve_soa(arslam_soa_problem *p, const arslam_lm_options *opt,
   arslam_lm *h = nullptr;
   int rc = arslam_lm_create(&h, opt);
   if (rc) return rc;
-  rc = guarded([&] {
+  rc = arslam::api_guarded([&] {
     h->load(p, arslam::ObsLoss{});   // (a handle of its own: no default loss to apply)
     h->solve(summary);
   });
@@ -325,7 +303,7 @@ int arslam_lm_solve_soa(arslam_soa_problem *p, const arslam_lm_options *opt,
 int arslam_lm_covariance(arslam_lm *h, double *cov_cap, double *cov_tag, double *var_f, int *cap_status,
                          int *tag_status, arslam_lm_cov_info *info) {
   if (!h) return ARSLAM_E_INVALID_ARG;
-  return guarded([&] {
+  return arslam::api_guarded([&] {
     h->covariance();
     if (cov_cap && !h->cov_cap.empty()) std::memcpy(cov_cap, h->cov_cap.data(), h->cov_cap.size() * sizeof(double));
     if (cov_tag && !h->cov_tag.empty()) std::memcpy(cov_tag, h->cov_tag.data(), h->cov_tag.size() * sizeof(double));
@@ -340,7 +318,7 @@ int arslam_lm_covariance(arslam_lm *h, double *cov_cap, double *cov_tag, double 
 
 int arslam_lm_covariance_block(arslam_lm *h, const double *block, double *cov, int *status) {
   if (!h || !block || !cov) return ARSLAM_E_INVALID_ARG;
-  return guarded([&] {
+  return arslam::api_guarded([&] {
     double *key = const_cast<double *>(block);
     const auto ci = h->cap_of.find(key);
     const auto ti = h->tag_of.find(key);
@@ -373,13 +351,13 @@ int arslam_lm_covariance_block(arslam_lm *h, const double *block, double *cov, i
 int arslam_lm_covariance_pairs(arslam_lm *h, const arslam_lm_cov_pair *pairs, int n_pairs, double *cov, int *status,
                                arslam_lm_cov_info *info) {
   if (!h || n_pairs < 0 || (n_pairs > 0 && (!pairs || !cov))) return ARSLAM_E_INVALID_ARG;
-  return guarded([&] { h->covariance_pairs(pairs, n_pairs, cov, status, info); });
+  return arslam::api_guarded([&] { h->covariance_pairs(pairs, n_pairs, cov, status, info); });
 }
 
 int arslam_lm_covariance_block_pair(arslam_lm *h, const double *block_a, const double *block_b, double *cov,
                                     int *status) {
   if (!h || !block_a || !block_b || !cov) return ARSLAM_E_INVALID_ARG;
-  return guarded([&] {
+  return arslam::api_guarded([&] {
     arslam_lm_cov_pair pr{};
     int size[2] = {6, 6};
     const double *blocks[2] = {block_a, block_b};
@@ -417,7 +395,7 @@ int arslam_lm_covariance_block_pair(arslam_lm *h, const double *block_a, const d
 
 int arslam_lm_debug_reduced_rows(arslam_lm *h, int *cap_row, int *tag_row, int *cam_row) {
   if (!h) return ARSLAM_E_INVALID_ARG;
-  return guarded([&] {
+  return arslam::api_guarded([&] {
     fail_if(!h->loaded || h->multi() || h->elim_used == ARSLAM_ELIM_MIXED, ARSLAM_E_STATE,
             "reduced_rows: a one-rank problem loaded with capture or tag elimination");
     const bool swapped = h->elim_used == ARSLAM_ELIM_TAGS;
@@ -431,7 +409,7 @@ int arslam_lm_debug_reduced_rows(arslam_lm *h, int *cap_row, int *tag_row, int *
 
 int arslam_comm_unique_id(unsigned char id[ARSLAM_COMM_ID_BYTES]) {
   if (!id) return ARSLAM_E_INVALID_ARG;
-  return guarded([&] {
+  return arslam::api_guarded([&] {
     static_assert(sizeof(ncclUniqueId) <= ARSLAM_COMM_ID_BYTES, "id size");
     ncclUniqueId u;
     NCCL_CHECK(ncclGetUniqueId(&u));
@@ -443,7 +421,7 @@ int arslam_comm_unique_id(unsigned char id[ARSLAM_COMM_ID_BYTES]) {
 int arslam_lm_set_comm_callback(arslam_lm *h, int rank, int nranks, arslam_allreduce_fn fn, void *ctx) {
   if (!h || nranks < 1 || rank < 0 || rank >= nranks || ((nranks > 1 || h->force_multi) && !fn))
     return ARSLAM_E_INVALID_ARG;
-  return guarded([&] {
+  return arslam::api_guarded([&] {
     if (h->comm) { (void)ncclCommDestroy(h->comm); h->comm = nullptr; }
     h->rank = rank;
     h->nranks = nranks;
@@ -456,7 +434,7 @@ int arslam_lm_set_comm_callback(arslam_lm *h, int rank, int nranks, arslam_allre
 
 int arslam_lm_set_comm(arslam_lm *h, int rank, int nranks, const unsigned char id[ARSLAM_COMM_ID_BYTES]) {
   if (!h || !id || nranks < 1 || rank < 0 || rank >= nranks) return ARSLAM_E_INVALID_ARG;
-  return guarded([&] {
+  return arslam::api_guarded([&] {
     h->ensure_stream();
     if (h->comm) { (void)ncclCommDestroy(h->comm); h->comm = nullptr; }
     h->comm_cb = nullptr;
@@ -502,7 +480,7 @@ int arslam_lm_debug_force_indefinite(arslam_lm *h, unsigned long long step_mask)
 
 int arslam_lm_debug_force_multirank(arslam_lm *h, int on) {
   if (!h || (on != 0 && on != 1)) return ARSLAM_E_INVALID_ARG;
-  return guarded([&] {
+  return arslam::api_guarded([&] {
     if (h->comm) { (void)ncclCommDestroy(h->comm); h->comm = nullptr; }
     h->comm_cb = nullptr;
     h->rank = 0;
@@ -515,7 +493,7 @@ int arslam_lm_debug_force_multirank(arslam_lm *h, int on) {
 
 int arslam_lm_debug_break_dependency(arslam_lm *h, long ticket, long *broken) {
   if (!h || ticket < 0) return ARSLAM_E_INVALID_ARG;
-  return guarded([&] {
+  return arslam::api_guarded([&] {
     fail_if(!h->loaded || !h->has_f || h->opt.factor_executor != 1, ARSLAM_E_STATE,
             "break_dependency needs a loaded problem on the persistent executor");
     arslam::LltPlan &pl = h->plan;
@@ -535,7 +513,7 @@ int arslam_lm_debug_break_dependency(arslam_lm *h, long ticket, long *broken) {
 
 int arslam_lm_debug_tag_pair_tile(arslam_lm *h, const double *tag_a, const double *tag_b, int *status) {
   if (!h || !tag_a || !tag_b || !status) return ARSLAM_E_INVALID_ARG;
-  return guarded([&] {
+  return arslam::api_guarded([&] {
     fail_if(!h->loaded || h->multi() || h->elim_used != ARSLAM_ELIM_CAPTURES || !h->has_f, ARSLAM_E_STATE,
             "tag_pair_tile needs a pointer-keyed problem loaded with capture elimination on one rank");
     const auto ia = h->tag_of.find(const_cast<double *>(tag_a)), ib = h->tag_of.find(const_cast<double *>(tag_b));

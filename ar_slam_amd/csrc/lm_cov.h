@@ -1,7 +1,8 @@
 // lm_cov.h -- the covariance of the LM solver on the device: the selected
 // inverse of the factored reduced system and the marginal blocks (selinv.hip),
 // and the multi-right-hand-side tile solve and the cross-covariance blocks
-// (cov_pairs.hip).  Called by lm_covariance.hip.
+// (cov_pairs.hip).  Called by lm_covariance.hip, and by debug_tiles.hip for
+// the component tests.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>

@@ -1,9 +1,11 @@
 // lm_handle.h -- the handle behind the C-ABI of include/arslam_lm.h: its
-// buffers and timers, and `struct arslam_lm` with every member.  The methods'
+// own buffers and timers (HIP_CHECK and DevBuf are hip_host.h's), and
+// `struct arslam_lm` with every member.  The methods'
 // bodies live in lm_load.hip (load, upload, append, value reload), lm_solve.hip
 // (the trust-region loop, its stages, the linearization), lm_covariance.hip and
 // lm_capi.hip (the extern "C" entry points); only those include this header.
 #pragma once
+#include "hip_host.h"
 #include "host_threads.h"
 #include "llt_plan.h"
 #include "lm_cov.h"
@@ -36,14 +38,7 @@ namespace arslam {
 namespace lmh {   // the LM handle's host helpers
 
 using Error = arslam::ApiError;
-
-#define HIP_CHECK(expr)                                                                      \
-  do {                                                                                       \
-    hipError_t _e = (expr);                                                                  \
-    if (_e != hipSuccess)                                                                    \
-      throw Error(_e == hipErrorOutOfMemory ? ARSLAM_E_OUT_OF_MEMORY : ARSLAM_E_HIP,         \
-                  std::string(#expr) + ": " + hipGetErrorString(_e));                       \
-  } while (0)
+using arslam::DevBuf;
 
 #define NCCL_CHECK(expr)                                                                     \
   do {                                                                                       \
@@ -76,33 +71,6 @@ inline const DebugEnv &debug_env() {
 // decode the persistent executors' negative flags (lm_solve.hip); for a
 // timed-out wait of k_factor_dag also what its fault record says
 std::string executor_fault_message(int code, int rank, int iteration, const arslam::LltPlan &plan, hipStream_t s);
-
-// Device buffer; grow-only, so reloading a problem of the same or a smaller
-// size (every optimize() of an incremental solve) does no hipMalloc/hipFree.
-template <class T>
-struct DevBuf {
-  T *p = nullptr;
-  size_t n = 0, cap = 0;
-  void alloc(size_t count) {   // grows by half again (a growing incremental problem reallocates rarely)
-    n = count;
-    if (count <= cap) return;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = cap == 0 && count <= 16 ? count : count + count / 2;
-    HIP_CHECK(hipMalloc(&p, want * sizeof(T)));
-    cap = want;
-  }
-  void upload(const T *h, size_t count, hipStream_t s) {
-    if (count) HIP_CHECK(hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, s));
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = cap = 0;
-  }
-  ~DevBuf() { release(); }
-};
 
 // page-locked host words: a D2H copy into them stays asynchronous
 struct PinnedBuf {

@@ -1,5 +1,5 @@
 // lm_rows.h -- the device helpers that the LM stages' kernels share
-// (lm_linearize.hip, lm_schur.hip, lm_step.hip, lm_reduce.hip; debug_api.hip
+// (lm_linearize.hip, lm_schur.hip, lm_step.hip, lm_reduce.hip; debug_rows.hip
 // for the corrector): the slots and kinds of a capture, its Jacobian rows and
 // their stored copy (DevProblem::jrows), the two instances of a per-capture
 // kernel, and the wave levels of a block's tree reduction.

@@ -468,8 +468,10 @@ void selinv_plan_build(const LltPlan &P, SelinvPlan &sp, hipStream_t s) {
   }
   if (hipMalloc(&sp.gcol, gcol.size() * sizeof(int)) != hipSuccess) throw std::runtime_error("selinv: hipMalloc");
   if (hipMemcpyAsync(sp.gcol, gcol.data(), gcol.size() * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess)
+      hipStreamSynchronize(s) != hipSuccess) {
+    selinv_plan_free(sp);
     throw std::runtime_error("selinv: hipMemcpy");
+  }
 }
 
 void selinv_plan_free(SelinvPlan &sp) {

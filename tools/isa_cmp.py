@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the gfx950 machine code of every kernel of two builds.
 
-    tools/isa_cmp.py <tree or dir of .s> <tree or dir of .s> [--keep DIR] [-j N]
+    tools/isa_cmp.py <tree or dir of .s> <tree or dir of .s> [--keep DIR] [-j N] [--rename OLD=NEW ...]
 
 A tree is a checkout of this repository: every .hip / .cpp in its build.py's
 SOURCES is compiled device-only to assembly (-S) with build.py's flags.  A
@@ -10,8 +10,11 @@ way.  For every kernel (.amdhsa_kernel) the text between `<symbol>:` and the
 following `.Lfunc_end<n>:` is normalized -- comment and directive lines
 dropped, the function index taken out of `.LBB<n>_` labels -- and hashed;
 kernels are matched across the two sides by mangled name, whichever file they
-live in.  Printed per kernel: line count, hash, and the resource lines of the
-code object's metadata (VGPRs, SGPRs, spills, scratch and LDS bytes).
+live in.  --rename OLD=NEW replaces OLD by NEW in the first side's names before
+the match, for a change that moves a type of a kernel's signature to another
+namespace: the mangled name spells the type, the code does not.  Printed per
+kernel: line count, hash, and the resource lines of the code object's metadata
+(VGPRs, SGPRs, spills, scratch and LDS bytes).
 
 Exit status 0: every kernel is present on both sides with identical code and
 resources.  A diff of two builds; needs hipcc, no GPU.
@@ -138,11 +141,15 @@ def main():
     ap.add_argument("b")
     ap.add_argument("--keep", help="keep the assembly files under DIR/a and DIR/b")
     ap.add_argument("-j", type=int, default=min(8, os.cpu_count() or 1))
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW",
+                    help="replace OLD by NEW in the first side's kernel names before matching")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         base = args.keep or tmp
         a = load_side(args.a, os.path.join(base, "a"), args.j)
         b = load_side(args.b, os.path.join(base, "b"), args.j)
+    for old, new in (r.split("=", 1) for r in args.rename):
+        a = {name.replace(old, new): k for name, k in a.items()}
     return 1 if compare(a, b) else 0
 
 
