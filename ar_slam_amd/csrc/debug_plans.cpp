@@ -10,6 +10,7 @@
 #include "arslam_lm.h"
 #include "arslam_lm_debug.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -26,9 +27,8 @@ struct HostPlan {
   HostProblem h;
   ReducedLayout L;
   LltPlan plan;   // (symbolic())
-  explicit HostPlan(HostProblem hp, int ordering = 2, bool sparse = true)
-      : h(std::move(hp)), L(reduced_layout(h, ordering, sparse, nullptr, nullptr)) {}
-  explicit HostPlan(const arslam_soa_problem *p) : HostPlan(host_problem(p, nullptr)) {}
+  explicit HostPlan(HostProblem hp, const LayoutRequest &rq = {}) : h(std::move(hp)), L(reduced_layout(h, rq)) {}
+  explicit HostPlan(const arslam_soa_problem *p) : HostPlan(host_problem(p)) {}
   bool reduced() const { return L.nR > 0; }
   // cls: a rank's column classes (RankSplit::col_class), null = the one-phase plan
   HostPlan &symbolic(const std::vector<int> *cls = nullptr) {
@@ -104,9 +104,12 @@ extern "C" int arslam_debug_reduced_plan(const arslam_soa_problem *p, int orderi
     std::memset(info, 0, sizeof(*info));
     static const bool prof = std::getenv("ARSLAM_SETUP_PROFILE") != nullptr;   // debug: setup phases
     const double t0 = now_ms();
-    HostProblem h = host_problem(p, nullptr);
+    HostProblem h = host_problem(p);
     const double t1 = now_ms();
-    HostPlan hp(std::move(h), ordering, skip_zero_tiles != 0);
+    LayoutRequest rq;
+    rq.ordering = ordering;
+    rq.sparse = skip_zero_tiles != 0;
+    HostPlan hp(std::move(h), rq);
     const double t2 = now_ms();
     if (tag_row)
       for (int t = 0; t < hp.h.nt; ++t) tag_row[t] = hp.L.tag_row[t];
@@ -121,6 +124,16 @@ extern "C" int arslam_debug_reduced_plan(const arslam_soa_problem *p, int orderi
   });
 }
 
+// The side a one-rank load eliminates when asked for `elimination` (CAPTURES, TAGS or MIXED: Ceres' set e_cap /
+// e_tag, or a whole side where the set holds one kind only -- arslam_lm::choose_side's rule).
+static int debug_side(const arslam_soa_problem *p, int elimination, std::vector<uint8_t> &e_cap,
+                      std::vector<uint8_t> &e_tag) {
+  if (elimination != ARSLAM_ELIM_MIXED) return elimination;
+  const SchurSide cs = ceres_schur_side(p, &e_cap, &e_tag);
+  if (cs.e_cam || cs.e_tag == 0) return ARSLAM_ELIM_CAPTURES;
+  return cs.e_cap == 0 ? ARSLAM_ELIM_TAGS : ARSLAM_ELIM_MIXED;
+}
+
 extern "C" int arslam_debug_reduced_plan_side(const arslam_soa_problem *p, int elimination, arslam_plan_info *info) {
   if (!p || !info || elimination < ARSLAM_ELIM_CAPTURES || elimination > ARSLAM_ELIM_MIXED) return ARSLAM_E_INVALID_ARG;
   int side = elimination;
@@ -129,22 +142,54 @@ extern "C" int arslam_debug_reduced_plan_side(const arslam_soa_problem *p, int e
     // the device problem of that side, as arslam_lm's load builds it (one rank)
     std::vector<uint8_t> e_cap, e_tag;
     MixedProblem mx;
-    const arslam_soa_problem swapped = swap_roles(*p);
-    const arslam_soa_problem *q = p;
-    if (side == ARSLAM_ELIM_MIXED) {
-      const SchurSide cs = ceres_schur_side(p, &e_cap, &e_tag);
-      if (cs.e_cam || cs.e_tag == 0) side = ARSLAM_ELIM_CAPTURES;
-      else if (cs.e_cap == 0) side = ARSLAM_ELIM_TAGS;
-      else mx = mixed_problem(*p, e_cap, e_tag), q = &mx.soa;
-    }
-    if (side == ARSLAM_ELIM_TAGS) q = &swapped;
-    HostProblem h = host_problem(q, nullptr);
-    if (side == ARSLAM_ELIM_MIXED) mixed_patch(h, mx, *p);
-    HostPlan hp(std::move(h));
+    arslam_soa_problem swapped;
+    side = debug_side(p, elimination, e_cap, e_tag);
+    const arslam_soa_problem *q = device_problem(*p, side, e_cap, e_tag, swapped, mx);
+    HostPlan hp(device_host_problem(q, side == ARSLAM_ELIM_MIXED ? &mx : nullptr, *p));
     if (hp.reduced()) hp.symbolic();
     fill_plan_info(hp, info);
   });
   return rc ? rc : side;
+}
+
+extern "C" int arslam_debug_order_memory(const arslam_soa_problem *problems, int n_problems, int elimination,
+                                         int ordering, const unsigned char *forget_before, arslam_order_step *steps,
+                                         int *const *tag_row, int *const *cap_row) {
+  if (!problems || !steps || n_problems < 1 || elimination < ARSLAM_ELIM_CAPTURES || elimination > ARSLAM_ELIM_MIXED ||
+      ordering < 0 || ordering > 2)
+    return ARSLAM_E_INVALID_ARG;
+  return api_guarded([&] {
+    OrderMemory order;
+    for (int i = 0; i < n_problems; ++i) {
+      const arslam_soa_problem &p = problems[i];
+      if (forget_before && forget_before[i]) order.forget();
+      // load()'s one-rank stages up to the remembered order, the first as a
+      // first load, the later ones as the pointer-keyed path's reloads
+      const bool reuse = i > 0;
+      std::vector<uint8_t> e_cap, e_tag;
+      MixedProblem mx;
+      arslam_soa_problem swapped;
+      const int side = debug_side(&p, elimination, e_cap, e_tag);
+      const arslam_soa_problem *q = device_problem(p, side, e_cap, e_tag, swapped, mx);
+      const MixedProblem *mixed = side == ARSLAM_ELIM_MIXED ? &mx : nullptr;
+      LayoutRequest rq = order.request(reuse, side, mixed, ordering, true, q->n_cap);
+      const HostProblem h = device_host_problem(q, mixed, p);
+      rq.fast_order = reuse;
+      bool recomputed = false;
+      const ReducedLayout L = order.layout(h, rq, &recomputed);
+      order.remember(L, h, rq, mixed);
+      steps[i] = {side, L.order_reused ? 1 : 0, recomputed ? 1 : 0, L.nR > 0 ? etree_height(L) : 0, L.pad_rows};
+      // the rows by the caller's blocks
+      int *tr = tag_row ? tag_row[i] : nullptr, *cr = cap_row ? cap_row[i] : nullptr;
+      if (tr) std::fill(tr, tr + p.n_tag, -1);
+      if (cr) std::fill(cr, cr + p.n_cap, -1);
+      for (int f = 0; f < h.nt; ++f) {
+        const bool is_cap = mixed ? mx.f_is_cap[f] != 0 : side == ARSLAM_ELIM_TAGS;
+        int *out = is_cap ? cr : tr;
+        if (out) out[mixed ? mx.f_src[f] : f] = L.tag_row[f];
+      }
+    }
+  });
 }
 
 extern "C" int arslam_debug_dag_simulate(const arslam_soa_problem *p, int n_workers, unsigned seed, int policy,
@@ -248,8 +293,7 @@ extern "C" int arslam_debug_mixed_groups(const arslam_soa_problem *p, int out[4]
     if (e_cap) std::copy(ec.begin(), ec.end(), e_cap);
     if (e_tag) std::copy(et.begin(), et.end(), e_tag);
     const MixedProblem m = mixed_problem(*p, ec, et);
-    HostProblem h = host_problem(&m.soa, nullptr);
-    mixed_patch(h, m, *p);
+    const HostProblem h = device_host_problem(&m.soa, &m, *p);
     out[0] = h.nc;
     out[1] = h.nt;
     out[2] = m.n_direct;
@@ -299,7 +343,7 @@ extern "C" int arslam_debug_gather_extend(const arslam_soa_problem *p, int c0, i
     q.corners = cr.data();
     const HostPlan hs(&q);
     SchurGather G = schur_gather_plan(hs.h, hs.L);
-    const HostProblem hf = host_problem(p, nullptr);
+    const HostProblem hf = host_problem(p);
     schur_gather_extend(G, hf, hs.L, c0);
     const SchurGather F = schur_gather_plan(hf, hs.L);
     bool same = G.cap_off == F.cap_off && G.dest_row == F.dest_row && G.dest_start == F.dest_start &&

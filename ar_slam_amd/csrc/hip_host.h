@@ -4,7 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "host_structure.h"
+#include "api_error.h"
 
 #include <string>
 #include <utility>

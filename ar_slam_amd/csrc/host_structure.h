@@ -1,16 +1,17 @@
 // host_structure.h -- host-only structure of a loaded problem (no HIP):
 // capture-major observation CSR, parameter freedom, and the layout + tile
 // pattern of the reduced (tag + camera) system.  Used by the solver's load
-// and by arslam_debug_reduced_plan (CPU-testable).
+// and by the host-only debug entries (CPU-testable).  One source file per
+// subsystem: host_eblocks.cpp (which blocks are eliminated, the device
+// problem of a side), host_problem.cpp, host_ordering.cpp (RCM, nested
+// dissection), host_layout.cpp (rows, tile pattern, OrderMemory) and
+// host_gather.cpp (the Schur gather plan).
 #pragma once
 
+#include "api_error.h"
 #include "arslam_lm.h"
 
 #include <cstdint>
-#include <functional>
-#include <new>
-#include <stdexcept>
-#include <string>
 #include <vector>
 
 namespace arslam {
@@ -22,49 +23,12 @@ constexpr int kTileRows = 64;
 // supports has at most 250 ids, aruco_detector.cpp:146-150)
 constexpr int kMaxSchurBlocks = 256;
 
-// An error with the C-ABI code it maps to.
-struct ApiError : std::runtime_error {
-  int code;
-  ApiError(int c, const std::string &m) : std::runtime_error(m), code(c) {}
-};
-
-// message returned by arslam_lm_last_error() on the calling thread
-void set_last_error(const std::string &msg);
-
-inline void api_check(bool ok, int code, const char *msg) {
-  if (!ok) throw ApiError(code, msg);
-}
-
-// The C boundary of the HIP library's entry points: runs f and turns what it
-// throws into the C-ABI code, leaving the text for arslam_lm_last_error().
-template <class F>
-int api_guarded(F &&f) {
-  try {
-    f();
-    return ARSLAM_OK;
-  } catch (const ApiError &e) {
-    set_last_error(e.what());
-    return e.code;
-  } catch (const std::bad_alloc &) {
-    set_last_error("host out of memory");
-    return ARSLAM_E_OUT_OF_MEMORY;
-  } catch (const std::exception &e) {
-    set_last_error(e.what());
-    return ARSLAM_E_HIP;
-  } catch (...) {
-    set_last_error("unknown error");
-    return ARSLAM_E_HIP;
-  }
-}
-
-// In-place all-reduce hooks of the capture-sharded path (null: one rank).
-using ReduceSumF64 = std::function<void(std::vector<double> &)>;
-using ReduceMaxU8 = std::function<void(std::vector<uint8_t> &)>;
+inline long round_up(long v, long m) { return (v + m - 1) / m * m; }
 
 // Capture-major observation order and parameter freedom.  A block is a
 // parameter iff some residual uses it and it is not held constant (Ceres
 // removes unused and constant blocks; ar_slam_util.cpp:965,972).  Tag use and
-// the observation count are global over ranks (tag_deg_sum).
+// the observation count are the whole problem's (host_problem's `whole`).
 struct HostProblem {
   int nc = 0, nt = 0, nb = 0;
   long n = 0;                       // 3 + 6 nc + 6 nt parameter slots
@@ -110,8 +74,9 @@ struct ObsLoss {
   const unsigned char *kind = nullptr;
   const double *a = nullptr;
 };
-HostProblem host_problem(const arslam_soa_problem *p, const ReduceSumF64 &tag_deg_sum,
-                         const ObsLoss *loss = nullptr);
+// (whole: p holds one rank's captures of this problem, with every tag)
+HostProblem host_problem(const arslam_soa_problem *p, const ObsLoss *loss = nullptr,
+                         const arslam_soa_problem *whole = nullptr);
 
 // Ceres 2.0's e-block set for DENSE_SCHUR with no user ordering
 // (ReorderProgramForSchurTypeLinearSolver -> ComputeStableSchurOrdering ->
@@ -165,6 +130,16 @@ MixedProblem mixed_problem(const arslam_soa_problem &p, const std::vector<uint8_
 void mixed_patch(HostProblem &h, const MixedProblem &m, const arslam_soa_problem &p);
 // the parameter vector of the mixed device problem from the original blocks
 void mixed_values(const MixedProblem &m, const arslam_soa_problem &p, double *x);
+// The device problem of p under side (ARSLAM_ELIM_*): p itself, `swapped`
+// (tags eliminated) or mx.soa (MIXED: regrouped by the e-set; mx is emptied
+// otherwise).  The result points into p, swapped or mx.
+const arslam_soa_problem *device_problem(const arslam_soa_problem &p, int side, const std::vector<uint8_t> &e_cap,
+                                         const std::vector<uint8_t> &e_tag, arslam_soa_problem &swapped,
+                                         MixedProblem &mx);
+// host_problem of a device problem of p; mx (its mixed regrouping, else null): patched (mixed_patch).
+// (the role-swapped and the mixed problem keep p's observation order: its losses apply as they are)
+HostProblem device_host_problem(const arslam_soa_problem *dev, const MixedProblem *mx, const arslam_soa_problem &p,
+                                const ObsLoss *loss = nullptr);
 
 // Row layout of the reduced system and its tile pattern (before fill).
 //   ordering 0 natural, 1 reverse Cuthill-McKee, 2 nested dissection (parts
@@ -191,20 +166,97 @@ struct ReducedLayout {
 double scalar_cholesky_flops(const std::vector<std::vector<int>> &adj, const std::vector<int> &tag_row,
                              bool camera);
 
-// reuse_tag_row: the tag rows of an earlier layout of the same problem family,
-// made when the co-visibility graph had reuse_edges edges; used as is (no new
-// ordering) when the set of free tags is unchanged and the graph has grown by
-// at most a tenth since -- an incremental solve that only added captures
-// keeps its elimination order until the fill it was made for is outdated.
-// reuse_by_identity: reuse_tag_row has one entry per tag of h (the earlier
-// row of the same block, -1 for a block new to the reduced side) -- a mixed
-// set re-chosen on a grown graph (ARSLAM_ELIM_MIXED), whose reduced blocks are
-// renumbered; earlier rows of blocks gone from the reduced side stay padding,
-// the new blocks go to the end of the last part.
-ReducedLayout reduced_layout(const HostProblem &h, int ordering, bool sparse, const ReduceMaxU8 &adj_max,
-                             const ReduceMaxU8 &pattern_max,
-                             const std::vector<int> *reuse_tag_row = nullptr, long reuse_edges = 0,
-                             bool fast_order = false, bool reuse_by_identity = false);
+// What a layout is asked for.  reuse_rows: the f-blocks' rows of an earlier
+// layout of the same problem family, made when the co-visibility graph had
+// reuse_edges edges; used as they are (no new ordering) when the set of free
+// blocks is unchanged and the graph has not outgrown them
+// (OrderMemory::graph_outgrown) -- an incremental solve that only added
+// captures keeps its elimination order until the fill it was made for is
+// outdated.  Blocks past the earlier rows' (new parameter blocks are appended)
+// go to the end of the last part.
+// by_identity: reuse_rows has one entry per block of h (the earlier row of the
+// same block, -1 for a block new to the reduced side) -- a mixed set re-chosen
+// on a grown graph (ARSLAM_ELIM_MIXED), whose reduced blocks are renumbered;
+// earlier rows of blocks gone from the reduced side stay padding.
+struct LayoutRequest {
+  int ordering = 2;           // 0 natural, 1 reverse Cuthill-McKee, 2 nested dissection
+  bool sparse = true;         // skip structurally zero tiles (else every lower tile)
+  bool fast_order = false;    // nested dissection's faster separator search (nd_parts)
+  const std::vector<int> *reuse_rows = nullptr;
+  long reuse_edges = 0;
+  bool by_identity = false;
+};
+ReducedLayout reduced_layout(const HostProblem &h, const LayoutRequest &rq = {});
+
+// The tiles that group c's local system touches in the reduced system with
+// these rows: the camera's and each of its free blocks' (unsorted, repeated).
+void group_tiles(const HostProblem &h, const std::vector<int> &tag_row, int cam_row, int c, std::vector<int> &out);
+
+// symbolic tile-level Cholesky fill of a lower tile pattern (T*T bytes, in
+// place, diagonal set) and the tile elimination tree (parent[k]: the first
+// row below the diagonal)
+void tile_fill(int T, std::vector<uint8_t> &pattern, std::vector<int> &parent);
+// height of the tile elimination tree of a layout's filled pattern
+int etree_height(const ReducedLayout &L);
+
+// The elimination order a handle remembers from one load to the next, and the
+// rules by which a later load (or an appended problem) keeps it.  An
+// incremental re-load (pointer-keyed path, same options) whose free blocks are
+// unchanged keeps the previous order: the ordering (nested dissection) is the
+// largest part of the host setup.
+struct OrderMemory {
+  // The co-visibility graph the order was computed for, outgrown by a tenth
+  // (a stale order on the incremental cfg2 flow: 18 elimination-tree levels
+  // and 358 us per factorization against 10 and 217 us fresh).
+  static bool graph_outgrown(long edges, long order_edges) { return 10 * edges > 11 * order_edges; }
+  // A quarter more groups than the order was computed at: nested dissection
+  // cuts along the tags' positions, which the first solves of an incremental
+  // flow only roughly know, so a grown problem gets a fresh order even if its
+  // co-visibility graph barely changed.
+  static bool groups_outgrown(long groups, long order_groups) { return 4 * groups > 5 * order_groups; }
+  // A kept order whose tile elimination tree grew taller than the fresh
+  // order's by more than a level (new co-visibility across its separators:
+  // 10 -> 14 -> 20 levels within a few loads of the incremental cfg2 flow) is
+  // recomputed: the factorization is chain-bound, the order ~3 ms.
+  static constexpr int kHeightSlack = 1;
+
+  bool last_reused = false;   // the last remembered layout kept an earlier order (summary.order_reused)
+
+  // a bulk load, a reset: nothing to reuse
+  void forget();
+  // What a load of `side` (ARSLAM_ELIM_*) with n_groups eliminated groups asks
+  // of reduced_layout: the remembered rows if `reuse` is wanted and the options
+  // and the group count allow it.  A changed side forgets; a mixed set (mx: its
+  // regrouping, else null) has no order to reuse by index, and after a mixed
+  // set maps the earlier rows by original block (by_identity).
+  LayoutRequest request(bool reuse, int side, const MixedProblem *mx, int ordering, bool sparse, int n_groups);
+  // One rank's layout of h for that request; a kept order that made the tile
+  // tree too tall (kHeightSlack) is replaced by a fresh one (*recomputed).
+  ReducedLayout layout(const HostProblem &h, const LayoutRequest &rq, bool *recomputed = nullptr) const;
+  // after a load: L's rows (mx: also by original block), the request's options
+  // and, for a fresh order, the group count and tile-tree height it was made at
+  void remember(const ReducedLayout &L, const HostProblem &h, const LayoutRequest &rq, const MixedProblem *mx);
+  // The co-visibility of the free blocks (a bit matrix; directed edge count as
+  // ReducedLayout::n_edges) of the loaded problem, kept up to date through
+  // appends: add_groups, then outgrown() -- the appended problem reloads with
+  // a fresh order.  (A reload rebuilds the graph.)
+  void graph_build(const HostProblem &h, const ReducedLayout &L);
+  void add_groups(const HostProblem &h, const ReducedLayout &L, const std::vector<int> &groups);
+  bool outgrown(int n_groups) const;
+
+ private:
+  std::vector<int> rows_;                  // by f-block of the last layout
+  std::vector<int> tag_rows_, cap_rows_;   // a mixed set's: by original tag / capture, -1 off the reduced side
+  int side_ = ARSLAM_ELIM_CAPTURES;
+  int ordering_ = -1;
+  bool sparse_ = false;
+  long order_edges_ = 0;    // what the order was computed at: directed edges,
+  int order_groups_ = 0;    // groups,
+  int order_height_ = 0;    // and the tile elimination tree's height
+  std::vector<uint64_t> covis_;
+  long covis_nt_ = 0, covis_edges_ = 0;
+  void graph_add(const HostProblem &h, const ReducedLayout &L, int c);
+};
 
 // Deterministic Schur assembly.  k_schur stores capture c's local reduced
 // system at slab + cap_off[c] block-packed: local blocks U = 0 (f, 1 row),

@@ -524,24 +524,6 @@ void dag_build(LltPlan &plan) {
   plan.total_factor_flops = plan.total_upd_flops + n_potrf * (t3 / 3.0 + t3 / 3.0) + n_trsm * 2.0 * t3;
 }
 
-// Symbolic Cholesky fill of a lower tile pattern (in place, diagonal set) and
-// the tile elimination tree (parent[k]: the first row below the diagonal).
-void tile_fill(int T, std::vector<uint8_t> &P, std::vector<int> &parent) {
-  std::vector<int> rows;
-  for (int k = 0; k < T; ++k) {
-    P[(long)k * T + k] = 1;
-    rows.clear();
-    for (int i = k + 1; i < T; ++i)
-      if (P[(long)i * T + k]) rows.push_back(i);
-    for (size_t a = 0; a < rows.size(); ++a)
-      for (size_t b = 0; b <= a; ++b) P[(long)rows[a] * T + rows[b]] = 1;
-  }
-  parent.assign(T, -1);
-  for (int k = 0; k < T; ++k)
-    for (int i = k + 1; i < T; ++i)
-      if (P[(long)i * T + k]) { parent[k] = i; break; }
-}
-
 void llt_plan_symbolic(LltPlan &plan, int T, long lda, std::vector<uint8_t> &P, const std::vector<int> *col_class) {
   llt_plan_reset(plan);
   plan.T = T;

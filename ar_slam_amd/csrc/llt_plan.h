@@ -191,8 +191,6 @@ struct LltPlan {
 // 1 the replicated top, 2 another rank's -- a two-phase plan, see LltPlan)
 void llt_plan_symbolic(LltPlan &plan, int T, long lda, std::vector<uint8_t> &pattern,
                        const std::vector<int> *col_class = nullptr);
-// symbolic tile-level Cholesky fill (in place) and the tile elimination tree
-void tile_fill(int T, std::vector<uint8_t> &pattern, std::vector<int> &parent);
 // Subtree-to-rank split of the tile elimination tree (multi-GPU): the top of
 // the tree (the upper nested-dissection separators, the camera and the rhs)
 // is replicated, the subtrees below it are dealt to the ranks, and every

@@ -250,9 +250,7 @@ int arslam_lm_reset(arslam_lm *h) {
     h->loaded = false;
     h->pk_dirty = true;
     h->pk_loaded = false;
-    h->prev_tag_row.clear();
-    h->prev_mx_tag_row.clear();
-    h->prev_mx_cap_row.clear();
+    h->order.forget();
   });
 }
 
@@ -272,7 +270,7 @@ int arslam_lm_load_soa_loss(arslam_lm *h, const arslam_soa_problem *p, const uns
     h->pk_loaded = false;
     h->pk_dirty = true;
     h->reuse_order = false;   // a bulk load never reuses a pointer-keyed problem's order
-    h->prev_tag_row.clear();
+    h->order.forget();
     // (the caller's arrays are read during the load only)
     h->load(p, obs_loss_kind ? arslam::ObsLoss{obs_loss_kind, obs_loss_a} : h->default_obs_loss(p->n_obs));
   });

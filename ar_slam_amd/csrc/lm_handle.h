@@ -343,11 +343,17 @@ struct arslam_lm {
   // order, null arrays for none; they go beside the corners into every
   // host_problem call of the load)
   void load(const arslam_soa_problem *p, const arslam::ObsLoss &in_loss);
-  // load()'s parts: the e-block side for Ceres' set cs; several ranks: this
-  // rank's problem h, the whole problem's layout L, this rank's column classes
+  // load()'s stages: the e-block side for Ceres' set cs and the device problem
+  // of that side; several ranks: this rank's problem h, the whole problem's
+  // layout L (for the order memory's request rq), this rank's column classes;
+  // the tile plan (+ one rank: the gather plan and the order's graph); the timings
   int choose_side(const arslam::SchurSide &cs);
-  void local_rank_problem(const arslam_soa_problem *p, const arslam::ObsLoss &in_loss, bool can_reuse,
+  const arslam_soa_problem *choose_device_problem(const arslam_soa_problem *p_in, arslam_soa_problem &swapped);
+  void local_rank_problem(const arslam_soa_problem *p, const arslam::ObsLoss &in_loss, const arslam::LayoutRequest &rq,
                           arslam::HostProblem &h, arslam::ReducedLayout &L, std::vector<int> &col_class);
+  void build_plans(const arslam::HostProblem &h, arslam::ReducedLayout &L, const std::vector<int> &col_class);
+  void record_load_times(double t_load, double t_side, double t_host, double t_layout, double t_book, double t_plan,
+                         double t_upload);
   // (extend_from >= 0: captures [extend_from, nc) were appended to the loaded
   // problem, the others unchanged: the gather plan is extended, not rebuilt)
   void upload_problem(const arslam::HostProblem &h, const arslam::ReducedLayout &L, int extend_from = -1);
@@ -360,7 +366,6 @@ struct arslam_lm {
   bool append_as_mixed(const arslam_soa_problem *p, arslam::MixedProblem &m);
   bool same_reduced_rows(const arslam::HostProblem &h) const;
   bool groups_fit_plan(const arslam::HostProblem &h, const std::vector<int> &groups) const;
-  bool order_outgrown(const arslam::HostProblem &h, const std::vector<int> &groups);
   arslam::ReducedLayout lay;      // the loaded layout (one rank), kept for try_append
   bool pk_appended_only = false;  // since the last load only residual blocks of known tags were added
   int setup_kind = ARSLAM_SETUP_LOAD;
@@ -381,33 +386,10 @@ struct arslam_lm {
   std::vector<double> loc_loss_a;
   double split_top_work = 0.0, split_max_rank_work = 0.0, split_total_work = 0.0;
   int split_active = 1;   // ranks owning subtrees (RankSplit::n_active)
-  // co-visibility of the free tags (a bit matrix, directed edge count as
-  // ReducedLayout::n_edges), kept up to date through appends: an appended
-  // problem whose graph outgrew the one its elimination order was computed
-  // for by more than a tenth reloads with a fresh order (a stale order on the
-  // incremental cfg2 flow: 18 elimination-tree levels and 358 us per
-  // factorization against 10 and 217 us fresh)
-  std::vector<uint64_t> covis;
-  long covis_nt = 0, covis_edges = 0;
-  void covis_build(const arslam::HostProblem &h, const arslam::ReducedLayout &L);
-  void covis_add(const arslam::HostProblem &h, const arslam::ReducedLayout &L, int c);
-  bool reuse_order = false;  // load(): keep the previous tag order when the free tags are unchanged
-  std::vector<int> prev_tag_row;
-  // ARSLAM_ELIM_MIXED: the rows of the last layout by original block (tag /
-  // capture id, -1 off the reduced side), for a reload whose re-chosen set
-  // renumbers the reduced blocks (reduced_layout by identity)
-  std::vector<int> prev_mx_tag_row, prev_mx_cap_row;
-  int prev_ordering = -1, prev_skip = -1;
-  long prev_order_edges = 0;
-  // the capture count the order was computed at: nested dissection cuts along
-  // the tags' positions, which the first solves of an incremental flow only
-  // roughly know, so a grown problem (by a quarter) gets a fresh order even if
-  // its co-visibility graph barely changed (incremental cfg2: an order kept
-  // from the first load gave 18 elimination-tree levels, a fresh one 10)
-  int prev_order_nc = 0;
-  bool last_order_reused = false;   // summary.order_reused
-  int prev_order_height = 0;   // tile elimination-tree height of the layout the order was computed for
-  static int etree_height(const arslam::ReducedLayout &L);
+  // the elimination order kept between loads, and the pointer-keyed path's
+  // request to keep it (set around its load() of a grown problem)
+  arslam::OrderMemory order;
+  bool reuse_order = false;
   void linearize(double *x_cost, double *fixed_cost, double *gmax, double *gnorm, double *xnorm);
   // linearize split at the host read: enqueue (results copied to h_lin), collect after a sync
   void linearize_launch();

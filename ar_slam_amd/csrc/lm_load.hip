@@ -55,46 +55,6 @@ void arslam_lm::ensure_stream() {
   ready_opt_device = opt.device;
 }
 
-void arslam_lm::covis_build(const arslam::HostProblem &h, const arslam::ReducedLayout &L) {
-  covis_nt = h.nt <= 16384 ? h.nt : 0;
-  covis_edges = 0;
-  covis.assign(((size_t)covis_nt * covis_nt + 63) / 64, 0);
-  for (int c = 0; c < h.nc && covis_nt; ++c) covis_add(h, L, c);
-}
-
-void arslam_lm::covis_add(const arslam::HostProblem &h, const arslam::ReducedLayout &L, int c) {
-  if (!covis_nt) return;
-  for (int a = h.cap_blk_start[c]; a < h.cap_blk_start[c + 1]; ++a)
-    for (int b = h.cap_blk_start[c]; b < h.cap_blk_start[c + 1]; ++b) {
-      const int ta = h.blk_tag[a], tb = h.blk_tag[b];
-      if (ta == tb || L.tag_row[ta] < 0 || L.tag_row[tb] < 0) continue;
-      const size_t bit = (size_t)ta * covis_nt + tb;
-      if (!(covis[bit >> 6] >> (bit & 63) & 1)) {
-        covis[bit >> 6] |= 1ull << (bit & 63);
-        ++covis_edges;
-      }
-    }
-}
-
-int arslam_lm::etree_height(const arslam::ReducedLayout &L) {
-  std::vector<uint8_t> P = L.pattern;
-  std::vector<int> parent;
-  arslam::tile_fill(L.T, P, parent);
-  std::vector<int> lev(L.T, 1);
-  int h = 0;
-  for (int k = 0; k < L.T; ++k) {   // (parents have larger indices)
-    if (parent[k] >= 0) lev[parent[k]] = std::max(lev[parent[k]], lev[k] + 1);
-    h = std::max(h, lev[k]);
-  }
-  return h;
-}
-
-namespace {
-
-long round_up(long v, long m) { return (v + m - 1) / m * m; }
-
-}  // namespace
-
 // The e-block side (ARSLAM_ELIM_*) for Ceres' set cs of the problem: Ceres' own
 // independent set decides AUTO; tag elimination runs the same kernels on the
 // role-swapped problem.
@@ -127,6 +87,43 @@ int arslam_lm::choose_side(const arslam::SchurSide &cs) {
   return side;
 }
 
+// load()'s first stage: the side, and the device problem of that side (p_in
+// itself, `swapped`, or the handle's mx).
+const arslam_soa_problem *arslam_lm::choose_device_problem(const arslam_soa_problem *p_in, arslam_soa_problem &swapped) {
+  std::vector<uint8_t> e_cap, e_tag;
+  const bool want_set = opt.elimination == ARSLAM_ELIM_MIXED;
+  elim_used = choose_side(arslam::ceres_schur_side(p_in, want_set ? &e_cap : nullptr, want_set ? &e_tag : nullptr));
+  return arslam::device_problem(*p_in, elim_used, e_cap, e_tag, swapped, mx);
+}
+
+// The tile plan, and on one rank beside it the Schur gather plan (host only,
+// from h and L) on a second thread while this one builds and uploads the tile
+// plan (its HIP calls stay on the thread whose device is current) and does the
+// co-visibility bookkeeping.
+void arslam_lm::build_plans(const arslam::HostProblem &h, arslam::ReducedLayout &L, const std::vector<int> &col_class) {
+  scalar_flops = L.scalar_flops;
+  nR = L.nR;
+  has_f = nR > 0;
+  sg_ready = false;
+  N = has_f ? L.N : 0;
+  if (has_f && !multi()) {
+    arslam::SchurGather sg_new;
+    arslam::host_fork2(
+        true, [&] { sg_new = arslam::schur_gather_plan(h, L); },
+        [&] {
+          arslam::llt_plan_build(plan, L.T, N, L.pattern, stream, nullptr);
+          order.graph_build(h, L);
+        });
+    sg = std::move(sg_new);
+    sg_ready = true;
+  } else if (has_f) {
+    arslam::llt_plan_build(plan, L.T, N, L.pattern, stream, &col_class);
+  } else {
+    if (!multi()) order.graph_build(h, L);
+    arslam::llt_plan_free(plan);
+  }
+}
+
 void arslam_lm::load(const arslam_soa_problem *p_in, const arslam::ObsLoss &in_loss) {
   const double t_load = now_s();
   loaded = false;
@@ -137,35 +134,13 @@ void arslam_lm::load(const arslam_soa_problem *p_in, const arslam::ObsLoss &in_l
   // load of a process pays it here, in summary.setup_phase_s[0] -- round 4's
   // "1.2 ms per full load" was that one start averaged over 179 loads)
   ensure_stream();
-  std::vector<uint8_t> e_cap, e_tag;
-  const bool want_set = opt.elimination == ARSLAM_ELIM_MIXED;
-  const int side = choose_side(arslam::ceres_schur_side(p_in, want_set ? &e_cap : nullptr, want_set ? &e_tag : nullptr));
-  // (the f-side changed, or is a mixed set of its own: no order to reuse by
-  // index; a mixed set after a mixed set maps the earlier rows by block)
-  const bool was_mixed = elim_used == ARSLAM_ELIM_MIXED;
-  if (side != elim_used || side == ARSLAM_ELIM_MIXED) prev_tag_row.clear();
-  elim_used = side;
-  const arslam_soa_problem swapped = arslam::swap_roles(*p_in);
-  if (side == ARSLAM_ELIM_MIXED) mx = arslam::mixed_problem(*p_in, e_cap, e_tag);
-  else mx = arslam::MixedProblem{};
-  static const bool mx_fresh = std::getenv("ARSLAM_MIXED_FRESH_ORDER") != nullptr;   // debug A/B: round 6's first cut
-  const bool by_identity = side == ARSLAM_ELIM_MIXED && was_mixed && reuse_order && !mx_fresh && !mx.f_src.empty() &&
-                           (!prev_mx_tag_row.empty() || !prev_mx_cap_row.empty());
-  if (by_identity) {
-    prev_tag_row.assign(mx.f_src.size(), -1);
-    for (size_t f = 0; f < mx.f_src.size(); ++f) {
-      const std::vector<int> &m = mx.f_is_cap[f] ? prev_mx_cap_row : prev_mx_tag_row;
-      if (mx.f_src[f] < (int)m.size()) prev_tag_row[f] = m[mx.f_src[f]];
-    }
-  }
-  const arslam_soa_problem *p = side == ARSLAM_ELIM_TAGS ? &swapped : side == ARSLAM_ELIM_MIXED ? &mx.soa : p_in;
+  arslam_soa_problem swapped;
+  const arslam_soa_problem *p = choose_device_problem(p_in, swapped);
+  const arslam::MixedProblem *mixed = elim_used == ARSLAM_ELIM_MIXED ? &mx : nullptr;
+  arslam::LayoutRequest rq = order.request(reuse_order, elim_used, mixed, opt.reduced_ordering,
+                                           opt.cholesky_skip_zero_tiles != 0, p->n_cap);
   const double t_side = now_s();
-  double t_host = t_side;   // (one rank: after host_problem)
-  // an incremental re-load (pointer-keyed path, same options) whose free tags
-  // are unchanged keeps the previous elimination order: the ordering (nested
-  // dissection) is the largest part of the host setup
-  const bool can_reuse = reuse_order && !prev_tag_row.empty() && prev_ordering == opt.reduced_ordering &&
-                         prev_skip == opt.cholesky_skip_zero_tiles && 4L * p->n_cap <= 5L * prev_order_nc;
+  double t_host = t_side;   // (one rank: after the host problem)
   arslam::HostProblem h;
   arslam::ReducedLayout L;
   std::vector<int> col_class;
@@ -173,22 +148,12 @@ void arslam_lm::load(const arslam_soa_problem *p_in, const arslam::ObsLoss &in_l
   nc_full = p->n_cap;
   nc_user = p_in->n_cap;
   if (multi()) {
-    local_rank_problem(p, in_loss, can_reuse, h, L, col_class);
+    local_rank_problem(p, in_loss, rq, h, L, col_class);
   } else {
-    // (the role-swapped and the mixed problem keep p_in's observation order: its losses apply as they are)
-    h = arslam::host_problem(p, nullptr, &in_loss);   // validates p
-    if (side == ARSLAM_ELIM_MIXED) arslam::mixed_patch(h, mx, *p_in);
+    h = arslam::device_host_problem(p, mixed, *p_in, &in_loss);
     t_host = now_s();
-    // (a grown pointer-keyed problem: a fresh order takes the faster separator search)
-    L = arslam::reduced_layout(h, opt.reduced_ordering, opt.cholesky_skip_zero_tiles != 0, nullptr, nullptr,
-                               can_reuse ? &prev_tag_row : nullptr, prev_order_edges, reuse_order, by_identity);
-    // A kept order whose tile elimination tree grew taller than the fresh
-    // order's by more than a level (new co-visibility across its separators:
-    // 10 -> 14 -> 20 levels within a few loads of the incremental cfg2 flow)
-    // is recomputed: the factorization is chain-bound, the order ~3 ms.
-    if (L.order_reused && L.nR > 0 && etree_height(L) > prev_order_height + 1)
-      L = arslam::reduced_layout(h, opt.reduced_ordering, opt.cholesky_skip_zero_tiles != 0, nullptr, nullptr,
-                                 nullptr, 0, true);
+    rq.fast_order = reuse_order;   // (a grown pointer-keyed problem: a fresh order takes the faster separator search)
+    L = order.layout(h, rq);
   }
   const double t_layout = now_s();
   soa = *p;   // (several ranks: the whole problem; write_back maps this rank's captures)
@@ -199,63 +164,27 @@ void arslam_lm::load(const arslam_soa_problem *p_in, const arslam::ObsLoss &in_l
   nb_global = h.nb_global;
   slot_free = h.slot_free;
   x0 = h.x0;
-  last_order_reused = L.order_reused;
-  if (!L.order_reused) {
-    prev_order_nc = h.nc;
-    prev_order_height = L.nR > 0 ? etree_height(L) : 0;
-  }
-  prev_tag_row = L.tag_row;
-  prev_order_edges = L.order_edges;
-  prev_mx_tag_row.clear();
-  prev_mx_cap_row.clear();
-  if (side == ARSLAM_ELIM_MIXED) {
-    prev_mx_tag_row.assign(p_in->n_tag, -1);
-    prev_mx_cap_row.assign(p_in->n_cap, -1);
-    for (size_t f = 0; f < mx.f_src.size(); ++f)
-      (mx.f_is_cap[f] ? prev_mx_cap_row : prev_mx_tag_row)[mx.f_src[f]] = L.tag_row[f];
-  }
-  prev_ordering = opt.reduced_ordering;
-  prev_skip = opt.cholesky_skip_zero_tiles;
+  order.remember(L, h, rq, mixed);
   const double t_book = now_s();
-  scalar_flops = L.scalar_flops;
-  nR = L.nR;
-  has_f = nR > 0;
-  sg_ready = false;
-  if (has_f && !multi()) {
-    // the Schur gather plan (host only, from h and L) on a second thread while
-    // this one builds and uploads the tile plan (its HIP calls stay on the
-    // thread whose device is current) and does the co-visibility bookkeeping
-    N = L.N;
-    arslam::SchurGather sg_new;
-    arslam::host_fork2(
-        true, [&] { sg_new = arslam::schur_gather_plan(h, L); },
-        [&] {
-          arslam::llt_plan_build(plan, L.T, N, L.pattern, stream, nullptr);
-          covis_build(h, L);
-        });
-    sg = std::move(sg_new);
-    sg_ready = true;
-  } else if (has_f) {
-    N = L.N;
-    arslam::llt_plan_build(plan, L.T, N, L.pattern, stream, multi() ? &col_class : nullptr);
-  } else {
-    if (!multi()) covis_build(h, L);
-    N = 0;
-    arslam::llt_plan_free(plan);
-  }
+  build_plans(h, L, col_class);
   const double t_plan = now_s();
   upload_problem(h, L);
   const double t_upload = now_s();
   if (!multi()) lay = std::move(L);   // (try_append: an appended problem keeps this layout and plan)
   setup_kind = ARSLAM_SETUP_LOAD;
-  soa = side == ARSLAM_ELIM_MIXED ? *p_in : *p;   // (mixed: write_back maps the device slots to p_in's blocks)
+  soa = mixed ? *p_in : *p;   // (mixed: write_back maps the device slots to p_in's blocks)
   loaded = true;
   pk_appended_only = true;
+  record_load_times(t_load, t_side, t_host, t_layout, t_book, t_plan, t_upload);
+}
+
+// summary.setup_phase_s: structure (side rule + host problem), elimination
+// order (reduced layout; several ranks: + the split), tile plan + task graph,
+// gather plan + upload, the rest
+void arslam_lm::record_load_times(double t_load, double t_side, double t_host, double t_layout, double t_book,
+                                  double t_plan, double t_upload) {
   const double t_end = now_s();
   setup_s = t_end - t_load;
-  // summary.setup_phase_s: structure (side rule + host problem), elimination
-  // order (reduced layout; several ranks: + the split), tile plan + task graph,
-  // gather plan + upload, the rest
   setup_phase[0] = t_host - t_load;
   setup_phase[1] = t_layout - t_host;
   setup_phase[2] = t_plan - t_book;
@@ -265,7 +194,7 @@ void arslam_lm::load(const arslam_soa_problem *p_in, const arslam::ObsLoss &in_l
     std::fprintf(stderr, "arslam setup: nc %d nt %d side %.3f host+layout %.3f covis %.3f plan %.3f gather+upload %.3f tail %.3f total %.3f ms (order %s, %d levels, %ld tiles)\n",
                  nc, nt, 1e3 * (t_side - t_load), 1e3 * (t_layout - t_side), 1e3 * (t_book - t_layout), 1e3 * (t_plan - t_book),
                  1e3 * (t_upload - t_plan), 1e3 * (t_end - t_upload), 1e3 * setup_s,
-                 prev_order_nc == nc ? "fresh" : "kept", plan.nlev, (long)plan.n_tiles);
+                 order.last_reused ? "kept" : "fresh", plan.nlev, (long)plan.n_tiles);
 }
 
 // Several ranks: every rank holds the whole problem p and computes the same
@@ -273,11 +202,11 @@ void arslam_lm::load(const arslam_soa_problem *p_in, const arslam::ObsLoss &in_l
 // the subtree-to-rank split of the tile elimination tree, which gives this
 // rank its captures and tile columns (arslam::rank_split).  h: this rank's
 // problem; L: the whole problem's layout, its slots renumbered for this rank.
-void arslam_lm::local_rank_problem(const arslam_soa_problem *p, const arslam::ObsLoss &in_loss, bool can_reuse,
-                                   arslam::HostProblem &h, arslam::ReducedLayout &L, std::vector<int> &col_class) {
-  const arslam::HostProblem hf = arslam::host_problem(p, nullptr);   // validates p
-  L = arslam::reduced_layout(hf, opt.reduced_ordering, opt.cholesky_skip_zero_tiles != 0, nullptr, nullptr,
-                             can_reuse ? &prev_tag_row : nullptr, prev_order_edges);
+void arslam_lm::local_rank_problem(const arslam_soa_problem *p, const arslam::ObsLoss &in_loss,
+                                   const arslam::LayoutRequest &rq, arslam::HostProblem &h, arslam::ReducedLayout &L,
+                                   std::vector<int> &col_class) {
+  const arslam::HostProblem hf = arslam::host_problem(p);   // validates p
+  L = arslam::reduced_layout(hf, rq);   // (the plain separator search; no recompute for height)
   arslam::RankSplit split = arslam::rank_split(hf, L, std::max(nranks, 2));
   if (nranks == 1) {
     // (forced multi-rank path on one rank: the two-rank split's replicated
@@ -327,13 +256,7 @@ void arslam_lm::local_rank_problem(const arslam_soa_problem *p, const arslam::Ob
   pl.obs_tag = loc_obs_tag.data();
   pl.corners = loc_corners.data();
   pl.cap_const = p->cap_const ? loc_cap_const.data() : nullptr;
-  // the tags' use (freedom) and the observation count are the whole problem's
-  const arslam::ReduceSumF64 global_deg = [&](std::vector<double> &deg) {
-    std::fill(deg.begin(), deg.end(), 0.0);
-    for (int b = 0; b < p->n_obs; ++b) deg[p->obs_tag[b]] += 1.0;
-    deg[p->n_tag] = p->n_obs;
-  };
-  h = arslam::host_problem(&pl, global_deg, &loc_loss);
+  h = arslam::host_problem(&pl, &loc_loss, p);   // (the tags' use and the observation count: the whole problem's)
   // the layout's tag slots are the whole problem's (3 + 6 nc_full + 6 t + a):
   // renumber them for this rank's parameter vector (3 + 6 nc_own + 6 t + a)
   const long shift = 6L * (p->n_cap - (long)own_caps.size());
@@ -511,7 +434,7 @@ void arslam_lm::alloc_solve_buffers() {
   if (has_f) {
     d_slab.alloc(std::max(sg.cap_off[nc], 1L));
     d_gather_part.alloc(36L * std::max(sg.n_pslots, 1));
-    s_pre = multi() ? round_up(top_tail_len(), 512) : 0;
+    s_pre = multi() ? arslam::round_up(top_tail_len(), 512) : 0;
     d_S.alloc((size_t)s_pre + (size_t)plan.n_tiles * 4096);   // (cleared by k_schur's extra blocks every step)
     Sp = d_S.p + s_pre;
     d_z.alloc(N);
@@ -635,30 +558,12 @@ bool arslam_lm::groups_fit_plan(const arslam::HostProblem &h, const std::vector<
   std::vector<int> ts;
   for (int c : groups) {
     ts.clear();
-    if (lay.cam_row >= 0) {
-      ts.push_back(lay.cam_row / 64);
-      ts.push_back((lay.cam_row + 2) / 64);
-    }
-    for (int a = h.cap_blk_start[c]; a < h.cap_blk_start[c + 1]; ++a) {
-      const int r0 = lay.tag_row[h.blk_tag[a]];
-      if (r0 < 0) continue;
-      ts.push_back(r0 / 64);
-      ts.push_back((r0 + 5) / 64);
-    }
+    arslam::group_tiles(h, lay.tag_row, lay.cam_row, c, ts);
     for (size_t a = 0; a < ts.size(); ++a)
       for (size_t b = 0; b < ts.size(); ++b)
         if (ts[a] >= ts[b] && plan.h_tile_id[(size_t)ts[a] * T + ts[b]] < 0) return false;
   }
   return true;
-}
-
-// the co-visibility graph the order was computed for, outgrown by a tenth, or
-// a quarter more groups: reload with a fresh order.  (Adds the groups' edges
-// to covis; a reload rebuilds it.)
-bool arslam_lm::order_outgrown(const arslam::HostProblem &h, const std::vector<int> &groups) {
-  for (int c : groups) covis_add(h, lay, c);
-  if (covis_nt && 10 * covis_edges > 11 * prev_order_edges) return true;
-  return 4L * h.nc > 5L * prev_order_nc;
 }
 
 // arslam_lm_solve's one append entry: the capture form first, then the mixed
@@ -674,8 +579,7 @@ bool arslam_lm::try_append(const arslam_soa_problem *p, const arslam::ObsLoss &i
   else return false;
   const bool mixed = dev != p;
   const double t1 = now_s();
-  arslam::HostProblem h = arslam::host_problem(dev, nullptr, &in_loss);   // (m.soa: p's observation order)
-  if (mixed) arslam::mixed_patch(h, m, *p);
+  const arslam::HostProblem h = arslam::device_host_problem(dev, mixed ? &m : nullptr, *p, &in_loss);
   const double t2 = now_s();
   // the groups to check, ascending: the captures of the appended residual
   // blocks (the others' tile pairs were in the pattern already); mixed: the
@@ -685,7 +589,10 @@ bool arslam_lm::try_append(const arslam_soa_problem *p, const arslam::ObsLoss &i
   std::vector<int> groups;
   for (int c = 0; c < h.nc; ++c)
     if (touched[c]) groups.push_back(c);
-  if (!same_reduced_rows(h) || !groups_fit_plan(h, groups) || order_outgrown(h, groups)) return false;
+  if (!same_reduced_rows(h) || !groups_fit_plan(h, groups)) return false;
+  // the order's graph outgrown, or a quarter more groups: reload with a fresh order
+  order.add_groups(h, lay, groups);
+  if (order.outgrown(h.nc)) return false;
   // only new groups got residual blocks: their contributions extend the gather plan
   const int extend_from = groups.empty() || groups.front() >= nc ? nc : -1;
   // the f-side slots move with the group count

@@ -525,7 +525,7 @@ void arslam_lm::fill_summary(arslam_lm_summary *s) {
   s->split_max_rank_work = split_max_rank_work;
   s->split_total_work = split_total_work;
   s->n_active_ranks = multi() ? split_active : 1;
-  s->order_reused = last_order_reused ? 1 : 0;
+  s->order_reused = order.last_reused ? 1 : 0;
 }
 
 namespace {

@@ -53,6 +53,7 @@ EXPORTS = ["arslam_lm_options_init", "arslam_lm_create", "arslam_lm_destroy",
            "arslam_lm_covariance_pairs", "arslam_lm_covariance_block_pair", "arslam_debug_tile_solve",
            "arslam_lm_debug_force_multirank", "arslam_lm_debug_break_dependency", "arslam_lm_debug_tag_pair_tile",
            "arslam_debug_reduced_plan", "arslam_debug_reduced_plan_side", "arslam_debug_schur_stamps", "arslam_debug_ceres_e_blocks",
+           "arslam_debug_order_memory",
            "arslam_debug_mixed_groups",
            "arslam_debug_dag_simulate", "arslam_debug_dag_simulate_started", "arslam_debug_dag_workgroup_limit",
            "arslam_debug_dag_fault_detail", "arslam_debug_box_fingerprint",
@@ -835,6 +836,47 @@ def debug_reduced_plan_side(camera, cap, tag, obs_cap, obs_tag, corners=None, el
     side = lib().arslam_debug_reduced_plan_side(C.byref(A.s), elimination, C.byref(info))
     _check(min(side, 0))
     return side, {f: getattr(info, f) for f, _ in PlanInfo._fields_}
+
+
+class OrderStep(C.Structure):
+    _fields_ = [("side", C.c_int), ("order_reused", C.c_int), ("recomputed", C.c_int), ("etree_height", C.c_int),
+                ("pad_rows", C.c_long)]
+
+
+def debug_order_memory(problems, elimination=ELIM_CAPTURES, ordering=2, forget_before=None):
+    """Host-only: the problems in turn through one elimination-order memory, the first as a first
+    one-rank load, each later one as a pointer-keyed reload that may keep the remembered order
+    (forget_before[i]: drop the memory before problem i, as a reset does).  problems: dicts with
+    camera, cap, tag, obs_cap, obs_tag and optionally corners, camera_const, cap_const, tag_const.
+    Returns one dict per problem: side, order_reused, recomputed (a kept order replaced because its
+    tile elimination tree grew too tall), etree_height, pad_rows, and tag_row / cap_row: the first
+    reduced row of each original tag / capture, -1 for none."""
+    soas = [_Soa(q["camera"], q["cap"], q["tag"], q["obs_cap"], q["obs_tag"],
+                 q["corners"] if q.get("corners") is not None else np.zeros((len(q["obs_cap"]), 8)),
+                 q.get("camera_const", False), q.get("cap_const"), q.get("tag_const")) for q in problems]
+    n = len(soas)
+    arr = (SoaProblem * n)(*[A.s for A in soas])
+    steps = (OrderStep * n)()
+    tag_rows = [np.zeros(max(A.tag.shape[0], 1), np.int32) for A in soas]
+    cap_rows = [np.zeros(max(A.cap.shape[0], 1), np.int32) for A in soas]
+    tr = (_ip * n)(*[r.ctypes.data_as(_ip) for r in tag_rows])
+    cr = (_ip * n)(*[r.ctypes.data_as(_ip) for r in cap_rows])
+    fb = None
+    if forget_before is not None:
+        fb = np.ascontiguousarray(forget_before, np.uint8)
+        assert fb.shape == (n,)
+    L = lib()
+    L.arslam_debug_order_memory.argtypes = [C.POINTER(SoaProblem), C.c_int, C.c_int, C.c_int, _up,
+                                            C.POINTER(OrderStep), C.POINTER(_ip), C.POINTER(_ip)]
+    _check(L.arslam_debug_order_memory(arr, n, int(elimination), int(ordering),
+                                       fb.ctypes.data_as(_up) if fb is not None else None, steps, tr, cr))
+    out = []
+    for i, A in enumerate(soas):
+        d = {f: getattr(steps[i], f) for f, _ in OrderStep._fields_}
+        d["tag_row"] = tag_rows[i][:A.tag.shape[0]]
+        d["cap_row"] = cap_rows[i][:A.cap.shape[0]]
+        out.append(d)
+    return out
 
 
 def box_fingerprint(device=0):

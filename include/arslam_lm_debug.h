@@ -201,6 +201,26 @@ int arslam_debug_reduced_plan(const arslam_soa_problem *p, int ordering, int ski
  * side used (MIXED falls back to a whole side as the load does) or an error. */
 int arslam_debug_reduced_plan_side(const arslam_soa_problem *p, int elimination, arslam_plan_info *info);
 
+/* Host only: the elimination-order memory of a handle over a sequence of
+ * loads.  problems[0] is laid out as a first one-rank load lays it out under
+ * elimination (as above) and ordering (sparse tiles); each later one as a
+ * pointer-keyed reload of a grown problem, which may keep the remembered
+ * order.  forget_before (nullable) [n_problems]: non-zero drops the memory
+ * before that load, as arslam_lm_reset does.  Per problem: steps[i], and the
+ * first reduced row of each of the caller's blocks, -1 where the block has
+ * none: tag_row[i] [n_tag], cap_row[i] [n_cap] (captures have rows under tag
+ * elimination and in a mixed set); the arrays and their entries are nullable. */
+typedef struct {
+  int side;           /* the side used (MIXED falls back to a whole side as the load does) */
+  int order_reused;   /* as arslam_lm_summary.order_reused */
+  int recomputed;     /* 1: a kept order made the tile elimination tree too tall and was replaced */
+  int etree_height;   /* levels of the tile elimination tree */
+  long pad_rows;      /* as arslam_plan_info.pad_rows */
+} arslam_order_step;
+int arslam_debug_order_memory(const arslam_soa_problem *problems, int n_problems, int elimination, int ordering,
+                              const unsigned char *forget_before, arslam_order_step *steps, int *const *tag_row,
+                              int *const *cap_row);
+
 /* Host only: one simulated interleaving of n_workers workgroups running the
  * persistent executor's protocol on the one-rank plan of p (policy 0 random,
  * 1-3 adversarial orders; + 16 drops the cap on claimed continuations in

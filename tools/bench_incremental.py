@@ -65,7 +65,7 @@ if os.environ.get("ARSLAM_INC_DUMP"):   # debug: one line per Solve
             d = s.solve_summary(i)
             f.write(json.dumps({k: d[k] for k in ("elimination_used", "setup_kind", "setup_time_s", "minimizer_time_s",
                                                   "num_linear_solves", "n_factor_tiles", "n_levels", "n_reduced",
-                                                  "order_reused", "t_cholesky_ms")}) + "\n")
+                                                  "order_reused", "t_cholesky_ms", "final_cost")}) + "\n")
 print(json.dumps({"flow": f"solveIncremental, {name}: {g.n_cap} captures / {g.n_tag} tags, one message per capture",
                   "wall_s": wall, "solves": n, "lm_iterations": iters,
                   "setup_ms_per_solve": 1e3 * setup / n, "minimizer_ms_per_solve": 1e3 * mini / n,
