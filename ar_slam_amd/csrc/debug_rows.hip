@@ -15,16 +15,18 @@ namespace arslam {
 namespace {
 
 // one thread per (observation, row): residual and 15-column Jacobian row
+// (kSized: of a tag of side size[o]; else of the default side, size unused)
+template <bool kSized>
 __global__ void k_debug_rj(int n, const double *__restrict__ cam, const double *__restrict__ cap,
                            const double *__restrict__ tag, const double *__restrict__ corners,
-                           double *__restrict__ r, double *__restrict__ J) {
+                           const double *__restrict__ size, double *__restrict__ r, double *__restrict__ J) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= 8L * n) return;
   const long o = e / 8;
   const int row = (int)(e % 8), corner = row >> 1, comp = row & 1;
   double j13[13];
-  r[e] = residual_jacobian_row(cam + 3 * o, cap + 6 * o, tag + 6 * o, corner, comp,
-                               corners[8 * o + row], j13);
+  r[e] = residual_jacobian_row(cam + 3 * o, cap + 6 * o, tag + 6 * o, kSized ? 0.5 * size[o] : kArucoHalf, corner,
+                               comp, corners[8 * o + row], j13);
   double *out = J + e * 15;
   out[0] = j13[0];
   out[1] = 0.0;
@@ -44,7 +46,7 @@ __global__ void k_debug_rj_loss(int n, const double *__restrict__ cam, const dou
   const long o = e / 8;
   const int row = (int)(e % 8), corner = row >> 1, comp = row & 1;
   double j13[13];
-  double rv = residual_jacobian_row(cam + 3 * o, cap + 6 * o, tag + 6 * o, corner, comp,
+  double rv = residual_jacobian_row(cam + 3 * o, cap + 6 * o, tag + 6 * o, kArucoHalf, corner, comp,
                                     corners[8 * o + row], j13);
   const double rh = robustify_row(kind[o], a[o], rv, j13);
   r[e] = rv;
@@ -94,23 +96,40 @@ dim3 blocks_of_128(long threads) { return dim3((unsigned)((threads + 127) / 128)
 
 using arslam::DevBuf;
 
-extern "C" int arslam_debug_residual_jacobian(int n, const double *cam, const double *cap,
-                                              const double *tag, const double *corners, double *r,
-                                              double *J) {
+// the body of the two row entries (size: null = every tag of the default side)
+static int debug_rows(int n, const double *cam, const double *cap, const double *tag, const double *corners,
+                      const double *size, double *r, double *J) {
   if (n < 0 || (n && (!cam || !cap || !tag || !corners || !r || !J))) return ARSLAM_E_INVALID_ARG;
+  for (int i = 0; size && i < n; ++i)
+    if (!arslam::tag_size_valid(size[i])) return ARSLAM_E_INVALID_ARG;
   if (n == 0) return ARSLAM_OK;
   return arslam::api_guarded([&] {
-    DevBuf<double> d_in, d_out;   // d_out: r [8 n] | J [120 n]
-    arslam::upload_rows(d_in, n, cam, cap, tag, corners, nullptr);
+    DevBuf<double> d_in, d_out;   // d_in: ... (| size [n]); d_out: r [8 n] | J [120 n]
+    arslam::upload_rows(d_in, n, cam, cap, tag, corners, size);
     d_out.alloc(128L * n);
     double *d_r = d_out.p, *d_J = d_r + 8L * n;
-    hipLaunchKernelGGL(arslam::k_debug_rj, arslam::blocks_of_128(8L * n), dim3(128), 0, 0, n, d_in.p, d_in.p + 3L * n,
-                       d_in.p + 9L * n, d_in.p + 15L * n, d_r, d_J);
+    const double *d_size = size ? d_in.p + 23L * n : nullptr;
+    auto kernel = size ? arslam::k_debug_rj<true> : arslam::k_debug_rj<false>;
+    hipLaunchKernelGGL(kernel, arslam::blocks_of_128(8L * n), dim3(128), 0, 0, n, d_in.p, d_in.p + 3L * n,
+                       d_in.p + 9L * n, d_in.p + 15L * n, d_size, d_r, d_J);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipDeviceSynchronize());
     arslam::download(r, d_r, 8L * n);
     arslam::download(J, d_J, 120L * n);
   });
+}
+
+extern "C" int arslam_debug_residual_jacobian(int n, const double *cam, const double *cap,
+                                              const double *tag, const double *corners, double *r,
+                                              double *J) {
+  return debug_rows(n, cam, cap, tag, corners, nullptr, r, J);
+}
+
+extern "C" int arslam_debug_residual_jacobian_sized(int n, const double *cam, const double *cap,
+                                                    const double *tag, const double *corners,
+                                                    const double *size, double *r, double *J) {
+  if (n > 0 && !size) return ARSLAM_E_INVALID_ARG;
+  return debug_rows(n, cam, cap, tag, corners, size, r, J);
 }
 
 extern "C" int arslam_debug_residual_jacobian_loss(int n, const double *cam, const double *cap,

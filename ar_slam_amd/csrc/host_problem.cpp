@@ -69,6 +69,14 @@ HostProblem host_problem(const arslam_soa_problem *p, const ObsLoss *loss, const
       h.loss_a[q] = loss->a[order[q]];
     }
   }
+  // the tag sides in the same order (kept only when some side is not the default)
+  bool any_size = false;
+  if (loss && loss->size)
+    for (int b = 0; b < nb && !any_size; ++b) any_size = loss->size[b] != ARSLAM_DEFAULT_TAG_SIZE;
+  if (any_size) {
+    h.obs_size.resize(nb);
+    for (int q = 0; q < nb; ++q) h.obs_size[q] = loss->size[order[q]];
+  }
   api_check(h.maxblk <= kMaxSchurBlocks, ARSLAM_E_UNSUPPORTED,
             "an eliminated block (capture, or tag under tag elimination) couples more than 256 distinct blocks");
   // tag CSR over the capture-major order

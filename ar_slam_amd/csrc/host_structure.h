@@ -47,6 +47,9 @@ struct HostProblem {
   // both empty when no observation has one
   std::vector<unsigned char> loss_kind;   // [nb] ARSLAM_LOSS_*
   std::vector<double> loss_a;             // [nb]
+  // the side of each observation's tag (ObsLoss::size), capture-major like
+  // corners; empty when every one is ARSLAM_DEFAULT_TAG_SIZE
+  std::vector<double> obs_size;           // [nb] metres
   std::vector<unsigned char> slot_free, obs_active;
   std::vector<double> x0;           // [n] initial slots
   long nb_global = 0;
@@ -70,10 +73,15 @@ std::vector<std::vector<int>> nd_parts(int n, const std::vector<std::vector<int>
 // observation order (kind ARSLAM_LOSS_*, scale a); both null: none.  It stays
 // beside the problem through swap_roles and mixed_problem, which keep the
 // observation order.
+// size: the side length of each observation's tag, in the same order and
+// carried the same way (the functor's other constant); null: the default.
 struct ObsLoss {
   const unsigned char *kind = nullptr;
   const double *a = nullptr;
+  const double *size = nullptr;
 };
+// a tag side length the API accepts (arslam_lm.h)
+inline bool tag_size_valid(double s) { return ARSLAM_TAG_SIZE_VALID(s); }
 // (whole: p holds one rank's captures of this problem, with every tag)
 HostProblem host_problem(const arslam_soa_problem *p, const ObsLoss *loss = nullptr,
                          const arslam_soa_problem *whole = nullptr);

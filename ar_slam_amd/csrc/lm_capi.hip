@@ -120,18 +120,44 @@ int arslam_lm_get_loss(const arslam_lm *h, int *kind, double *a) {
   return ARSLAM_OK;
 }
 
+int arslam_lm_set_tag_size(arslam_lm *h, double size) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return arslam::api_guarded([&] {
+    fail_if(!arslam::tag_size_valid(size), ARSLAM_E_INVALID_ARG, "tag size: finite and > 0 (metres)");
+    h->def_tag_size = size;
+    // (as arslam_lm_set_loss: the blocks keep the sides they were added with,
+    // the resident problem is dropped)
+    h->loaded = false;
+    h->pk_dirty = true;
+  });
+}
+
+int arslam_lm_get_tag_size(const arslam_lm *h, double *size) {
+  if (!h || !size) return ARSLAM_E_INVALID_ARG;
+  *size = h->def_tag_size;
+  return ARSLAM_OK;
+}
+
 int arslam_lm_add_residual_block(arslam_lm *h, const double corners[8], double *camera,
                                  double *capture, double *tag) {
   if (!h) return ARSLAM_E_INVALID_ARG;
-  return arslam_lm_add_residual_block_loss(h, corners, camera, capture, tag, h->def_loss_kind, h->def_loss_a);
+  return arslam_lm_add_residual_block_sized(h, corners, camera, capture, tag, h->def_tag_size, h->def_loss_kind,
+                                            h->def_loss_a);
 }
 
 int arslam_lm_add_residual_block_loss(arslam_lm *h, const double corners[8], double *camera,
                                       double *capture, double *tag, int kind, double a) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return arslam_lm_add_residual_block_sized(h, corners, camera, capture, tag, h->def_tag_size, kind, a);
+}
+
+int arslam_lm_add_residual_block_sized(arslam_lm *h, const double corners[8], double *camera,
+                                       double *capture, double *tag, double size, int kind, double a) {
   if (!h || !corners || !camera || !capture || !tag) return ARSLAM_E_INVALID_ARG;
   return arslam::api_guarded([&] {
     fail_if(!arslam::loss_valid(kind, a), ARSLAM_E_INVALID_ARG,
             "loss: kind must be ARSLAM_LOSS_NONE, _HUBER, _SOFT_L_ONE or _CAUCHY, its scale finite and > 0");
+    fail_if(!arslam::tag_size_valid(size), ARSLAM_E_INVALID_ARG, "tag size: finite and > 0 (metres)");
     fail_if(h->camera_ptr && h->camera_ptr != camera, ARSLAM_E_UNSUPPORTED,
             "one shared camera block per problem (ArSlamSolver::camera_)");
     fail_if(capture == camera || tag == camera || capture == tag, ARSLAM_E_INVALID_ARG,
@@ -164,6 +190,7 @@ int arslam_lm_add_residual_block_loss(arslam_lm *h, const double corners[8], dou
     h->pk_corners.insert(h->pk_corners.end(), corners, corners + 8);
     h->pk_loss_kind.push_back((unsigned char)kind);
     h->pk_loss_a.push_back(kind == ARSLAM_LOSS_NONE ? 0.0 : a);
+    h->pk_size.push_back(size);
   });
 }
 
@@ -212,7 +239,8 @@ int arslam_lm_solve(arslam_lm *h, arslam_lm_summary *summary) {
     p.camera = cam.data(); p.cap = cap.data(); p.tag = tag.data();
     p.obs_cap = h->pk_obs_cap.data(); p.obs_tag = h->pk_obs_tag.data();
     p.corners = h->pk_corners.data();
-    const arslam::ObsLoss pk_loss{h->pk_loss_kind.data(), h->pk_loss_a.data()};   // (one per block, beside pk_corners)
+    // (one loss and one tag side per block, beside pk_corners)
+    const arslam::ObsLoss pk_loss{h->pk_loss_kind.data(), h->pk_loss_a.data(), h->pk_size.data()};
     p.camera_const = h->constant.count(h->camera_ptr) ? 1 : 0;
     p.cap_const = cc.data(); p.tag_const = tc.data();
     struct StageGuard {   // (the staging arrays go out of scope; the device problem stays)
@@ -246,6 +274,7 @@ int arslam_lm_reset(arslam_lm *h) {
     h->cap_ptrs.clear(); h->tag_ptrs.clear();
     h->pk_obs_cap.clear(); h->pk_obs_tag.clear(); h->pk_corners.clear();
     h->pk_loss_kind.clear(); h->pk_loss_a.clear();   // (the default loss stays: it is the handle's, not the problem's)
+    h->pk_size.clear();                              // (and so does the default tag side)
     h->constant.clear();
     h->loaded = false;
     h->pk_dirty = true;
@@ -260,9 +289,21 @@ int arslam_lm_load_soa(arslam_lm *h, const arslam_soa_problem *p) {
 
 int arslam_lm_load_soa_loss(arslam_lm *h, const arslam_soa_problem *p, const unsigned char *obs_loss_kind,
                             const double *obs_loss_a) {
+  return arslam_lm_load_soa_sized(h, p, nullptr, obs_loss_kind, obs_loss_a);
+}
+
+int arslam_lm_load_soa_sized(arslam_lm *h, const arslam_soa_problem *p, const double *tag_size,
+                             const unsigned char *obs_loss_kind, const double *obs_loss_a) {
   if (!h || !p || (obs_loss_kind == nullptr) != (obs_loss_a == nullptr)) return ARSLAM_E_INVALID_ARG;
   return arslam::api_guarded([&] {
-    fail_if(p->n_obs < 0, ARSLAM_E_INVALID_ARG, "negative sizes");   // (before n_obs sizes anything here)
+    fail_if(p->n_obs < 0 || p->n_tag < 0, ARSLAM_E_INVALID_ARG, "negative sizes");   // (before they size anything here)
+    if (tag_size) {
+      for (int t = 0; t < p->n_tag; ++t)
+        fail_if(!arslam::tag_size_valid(tag_size[t]), ARSLAM_E_INVALID_ARG, "tag_size: finite and > 0 (metres)");
+      fail_if(p->n_obs > 0 && !p->obs_tag, ARSLAM_E_INVALID_ARG, "null observation arrays");
+      for (int b = 0; b < p->n_obs; ++b)
+        fail_if(p->obs_tag[b] < 0 || p->obs_tag[b] >= p->n_tag, ARSLAM_E_INVALID_ARG, "obs_tag out of range");
+    }
     if (obs_loss_kind)
       for (int b = 0; b < p->n_obs; ++b)
         fail_if(!arslam::loss_valid(obs_loss_kind[b], obs_loss_a[b]), ARSLAM_E_INVALID_ARG,
@@ -272,7 +313,9 @@ int arslam_lm_load_soa_loss(arslam_lm *h, const arslam_soa_problem *p, const uns
     h->reuse_order = false;   // a bulk load never reuses a pointer-keyed problem's order
     h->order.forget();
     // (the caller's arrays are read during the load only)
-    h->load(p, obs_loss_kind ? arslam::ObsLoss{obs_loss_kind, obs_loss_a} : h->default_obs_loss(p->n_obs));
+    arslam::ObsLoss ol = obs_loss_kind ? arslam::ObsLoss{obs_loss_kind, obs_loss_a} : h->default_obs_loss(p->n_obs);
+    ol.size = h->obs_sizes(p, tag_size);
+    h->load(p, ol);
   });
 }
 

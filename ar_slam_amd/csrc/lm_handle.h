@@ -215,6 +215,20 @@ struct arslam_lm {
     soa_loss_a.assign(n_obs, def_loss_a);
     return arslam::ObsLoss{soa_loss_kind.data(), soa_loss_a.data()};
   }
+  // each residual block's tag side (arslam_lm_add_residual_block_sized; the
+  // handle's default side for the other two), beside pk_loss_* and under the
+  // same rules: bound when the block is added, never changed afterwards
+  std::vector<double> pk_size;
+  double def_tag_size = ARSLAM_DEFAULT_TAG_SIZE;   // arslam_lm_set_tag_size
+  std::vector<double> soa_size;   // arslam_lm_load_soa*'s tag sides, per observation
+  // the side of each observation's tag from the per-tag sides (null: the
+  // handle's default for every tag); null when every side is the default
+  const double *obs_sizes(const arslam_soa_problem *p, const double *tag_size) {
+    if (!tag_size && def_tag_size == ARSLAM_DEFAULT_TAG_SIZE) return nullptr;
+    soa_size.resize(p->n_obs > 0 ? p->n_obs : 0);
+    for (int b = 0; b < p->n_obs; ++b) soa_size[b] = tag_size ? tag_size[p->obs_tag[b]] : def_tag_size;
+    return soa_size.data();
+  }
   std::unordered_set<double *> constant;
   // The pointer-keyed structure (blocks, residuals, constants) changed since
   // the last load: arslam_lm_solve reloads; otherwise it reuses the resident
@@ -254,6 +268,7 @@ struct arslam_lm {
   double *u_corners = nullptr, *u_x0 = nullptr;
   unsigned char *u_loss_kind = nullptr;   // DevProblem::obs_loss_kind, obs_loss_a (a problem with losses)
   double *u_loss_a = nullptr;
+  double *u_obs_size = nullptr;           // DevProblem::obs_size (a problem with a tag side other than the default)
   long *u_cap_off = nullptr;
   int2 *u_dest_row = nullptr;
   int4 *u_gather_items = nullptr, *u_gather_splits = nullptr;
@@ -384,6 +399,7 @@ struct arslam_lm {
   std::vector<unsigned char> loc_cap_const;
   std::vector<unsigned char> loc_loss_kind;   // this rank's observations' losses
   std::vector<double> loc_loss_a;
+  std::vector<double> loc_size;               // ... and their tags' sides
   double split_top_work = 0.0, split_max_rank_work = 0.0, split_total_work = 0.0;
   int split_active = 1;   // ranks owning subtrees (RankSplit::n_active)
   // the elimination order kept between loads, and the pointer-keyed path's

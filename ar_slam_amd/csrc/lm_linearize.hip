@@ -36,8 +36,11 @@ __device__ __forceinline__ double row_prod(const double *rr, int ca, int cb) {
 // Linearize at x: per-observation tag gradient/column norms, per-capture
 // gradient/column norms, cost and camera partials.  Unscaled Jacobian (with
 // kLoss: corrected by sqrt(rho') per observation).
-template <bool kChunked, bool kLoss>
-__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_linearize(DevProblem P, const double *__restrict__ x,
+// (kSized: the same attribute for the one-chunk instances, 96 / 98 VGPRs as
+// without; the chunked ones ask for 2 waves instead of 4 and so take the
+// registers the others spill for: no scratch, profiles/tag_size/resource_usage.txt)
+template <bool kChunked, bool kLoss, bool kSized>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu((kChunked && kSized) ? 2 : 4, 8))) void k_linearize(DevProblem P, const double *__restrict__ x,
                                                      double *__restrict__ g,
                                                      double *__restrict__ colnorm,
                                                      double *__restrict__ obs_tg,
@@ -60,7 +63,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(4, 8))) v
   // around the projection cost the single-chunk code spills)
   auto chunk = [&](int q0) __attribute__((always_inline)) {
     const int kc = min(kObsChunk, k - q0), nr = 8 * kc;
-    fill_rows<kLoss>(P, x, nullptr, c, o0, 8 * q0, nr, nrows, rows, P.jrows, kLoss ? ocost : nullptr);
+    fill_rows<kLoss, kSized>(P, x, nullptr, c, o0, 8 * q0, nr, nrows, rows, P.jrows, kLoss ? ocost : nullptr);
     __syncthreads();
     // Every sum below is over rows of one product of two LDS columns (ca, cb),
     // picked per lane up front: one code path for the whole wave (a divergent
@@ -129,12 +132,13 @@ void launch_linearize(const DevProblem &P, const double *x, double *g, double *c
                       double *obs_tg, double *parts, hipStream_t s) {
   if (P.nc == 0) return;
   const size_t lds = lds_rows(kObsChunk) + sizeof(double) * (kObsChunk + 16);
-  // (the instance per loaded problem: kLoss iff it has robust losses)
-  const bool loss = P.obs_loss_kind != nullptr;
-  hipLaunchKernelGGL((loss ? k_linearize<false, true> : k_linearize<false, false>), dim3(P.nc), dim3(kWave), lds, s, P,
+  // (the instance per loaded problem: kLoss iff it has robust losses, kSized
+  // iff some tag's side is not the default)
+  const bool loss = P.obs_loss_kind != nullptr, sized = P.obs_size != nullptr;
+  hipLaunchKernelGGL(ARSLAM_PICK_INSTANCE(k_linearize, false, loss, sized), dim3(P.nc), dim3(kWave), lds, s, P,
                      x, g, colnorm, obs_tg, parts);
   if (P.n_chunk_caps)
-    hipLaunchKernelGGL((loss ? k_linearize<true, true> : k_linearize<true, false>), dim3(P.n_chunk_caps), dim3(kWave),
+    hipLaunchKernelGGL(ARSLAM_PICK_INSTANCE(k_linearize, true, loss, sized), dim3(P.n_chunk_caps), dim3(kWave),
                        lds, s, P, x, g, colnorm, obs_tg, parts);
 }
 

@@ -234,7 +234,7 @@ void arslam_lm::local_rank_problem(const arslam_soa_problem *p, const arslam::Ob
     if (p->cap_const) loc_cap_const[c] = p->cap_const[own_caps[c]];
   }
   loc_obs_cap.clear(); loc_obs_tag.clear(); loc_corners.clear();
-  loc_loss_kind.clear(); loc_loss_a.clear();
+  loc_loss_kind.clear(); loc_loss_a.clear(); loc_size.clear();
   const bool with_loss = in_loss.kind && in_loss.a;   // (the loss goes with its capture's observations)
   for (int b = 0; b < p->n_obs; ++b) {
     const int lc = loc_of[p->obs_cap[b]];
@@ -246,8 +246,10 @@ void arslam_lm::local_rank_problem(const arslam_soa_problem *p, const arslam::Ob
       loc_loss_kind.push_back(in_loss.kind[b]);
       loc_loss_a.push_back(in_loss.a[b]);
     }
+    if (in_loss.size) loc_size.push_back(in_loss.size[b]);   // (and so does its tag's side)
   }
-  const arslam::ObsLoss loc_loss{with_loss ? loc_loss_kind.data() : nullptr, with_loss ? loc_loss_a.data() : nullptr};
+  const arslam::ObsLoss loc_loss{with_loss ? loc_loss_kind.data() : nullptr, with_loss ? loc_loss_a.data() : nullptr,
+                                 in_loss.size ? loc_size.data() : nullptr};
   arslam_soa_problem pl = *p;
   pl.n_cap = (int)own_caps.size();
   pl.n_obs = (int)loc_obs_cap.size();
@@ -304,6 +306,8 @@ void arslam_lm::upload_problem(const arslam::HostProblem &h, const arslam::Reduc
     upload.add(&u_loss_kind, h.loss_kind.data(), nb);
     upload.add(&u_loss_a, h.loss_a.data(), nb);
   }
+  const bool has_size = !h.obs_size.empty();
+  if (has_size) upload.add(&u_obs_size, h.obs_size.data(), nb);
   upload.add(&u_x0, x0.data(), n);
   upload.add(&u_tag_row, L.tag_row.data(), L.tag_row.size());
   upload.add(&u_row_slot, row_slot.data(), row_slot.size());
@@ -392,6 +396,7 @@ void arslam_lm::upload_problem(const arslam::HostProblem &h, const arslam::Reduc
   P.tag_start = u_tag_start; P.obs_tpos = u_obs_tpos; P.corners = u_corners;
   P.obs_loss_kind = has_loss ? u_loss_kind : nullptr;
   P.obs_loss_a = has_loss ? u_loss_a : nullptr;
+  P.obs_size = has_size ? u_obs_size : nullptr;
   P.tag_row = u_tag_row; P.row_slot = u_row_slot;
   P.tile_id = plan.tile_id; P.T = plan.T;
   P.tile_class = multi() && has_f ? plan.tile_class : nullptr;

@@ -159,6 +159,11 @@ struct DevProblem {
   // (last in the struct: no other field's kernel-argument offset moves)
   const unsigned char *obs_loss_kind = nullptr;   // [nb] ARSLAM_LOSS_*
   const double *obs_loss_a = nullptr;             // [nb] scale a
+  // the side length of each observation's tag, in the order of corners; null
+  // when every tag of the loaded problem has the default side -- the host then
+  // launches the kSized = false instances (per observation, not per tag: the
+  // groups of swap_roles and the mixed e-set need no tag lookup)
+  const double *obs_size = nullptr;               // [nb] metres
 };
 
 // element (r, c), r >= c, of the compact-tiled reduced system

@@ -68,7 +68,9 @@ __device__ __forceinline__ double robustify_row(int kind, double a, double &r, d
 // (robustify_row), in LDS and in gout alike; with ocost, observation q of the
 // chunk also leaves its cost rho(s) / 2 in ocost[q] (from the corrected
 // residuals it would be rho' s / 2).
-template <bool kLoss = false>
+// kSized: the observation's tag side comes from DevProblem::obs_size; else
+// every tag has the default side, a constant of the code.
+template <bool kLoss = false, bool kSized = false>
 __device__ __forceinline__ void fill_rows(const DevProblem &P, const double *x, const double *scale, int c,
                           int o0, int row0, int nr, int nrows, double *rows, double *gout = nullptr,
                           double *ocost = nullptr) {
@@ -84,7 +86,8 @@ __device__ __forceinline__ void fill_rows(const DevProblem &P, const double *x, 
     // (tag elimination: the e-block is the problem's tag -- projectCorner
     // still takes the capture first; the Jacobian halves come back as e|f)
     const bool sw = group_swapped(P, c);
-    double r = residual_jacobian_row(cam, sw ? tag : cap, sw ? cap : tag, corner, comp,
+    const double half = kSized ? 0.5 * P.obs_size[obs] : kArucoHalf;
+    double r = residual_jacobian_row(cam, sw ? tag : cap, sw ? cap : tag, half, corner, comp,
                                      P.corners[8L * obs + 2 * corner + comp], J);
     if (kLoss) {
       // (nr is a multiple of 8: an observation's 8 lanes are in the loop together)
@@ -135,6 +138,14 @@ __device__ __forceinline__ void fill_rows(const DevProblem &P, const double *x, 
 // false is the code without them, instruction for instruction.  k_backsub
 // reads the corrected rows k_linearize stored, so its kLoss reaches only the
 // fused candidate cost.
+// kSized = true: the loaded problem has a tag side other than the default
+// (DevProblem::obs_size); false is the code with the constant side,
+// instruction for instruction.  The two flags are independent: four instances
+// of each form, and a problem of default-size tags launches the two it always
+// has.  k_backsub's kSized, like its kLoss, reaches only the candidate cost.
+#define ARSLAM_PICK_INSTANCE(K, chunked, loss, sized)                                       \
+  ((sized) ? ((loss) ? K<chunked, true, true> : K<chunked, false, true>)                    \
+           : ((loss) ? K<chunked, true, false> : K<chunked, false, false>))
 template <bool kChunked>
 __device__ __forceinline__ int chunk_capture(const DevProblem &P, int &k) {
   const int c = kChunked ? P.chunk_caps[blockIdx.x] : (int)blockIdx.x;

@@ -28,6 +28,9 @@ struct LocParams {
   // instances only; null when no observation of the batch has one
   const unsigned char *lk;     // [nb]
   const double *la;            // [nb]
+  // the map tags' sides in metres; null when every tag has the default side
+  // (last in the struct: no other field's kernel-argument offset moves)
+  const double *tsize;         // [nt]
 };
 
 // k_localize_cov's: k_localize's arguments (the batch, the last solve's poses, results, losses

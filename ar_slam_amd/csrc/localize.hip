@@ -70,9 +70,10 @@ __device__ double normalize_angle(double a) {   // ar_slam_util.hpp:348-351
   return fmod(fmod(a, 2 * M_PI) + 3 * M_PI, 2 * M_PI) - M_PI;
 }
 
-// calcInitValues :52-95 + initCapturePose :98-115
+// calcInitValues :52-95 + initCapturePose :98-115, from a tag of side `size`
+// (the reference's aruco_size; the depth local_z is proportional to it)
 __device__ void init_capture_pose(const double *corners, const double *camera, const double *ar_pose,
-                                  double *inv) {
+                                  double size, double *inv) {
   const double focal = camera[0];
   double max_dist_sq = 0.0, avg_x = 0.0, avg_y = 0.0;
   for (int i = 0; i < 4; ++i) {
@@ -92,7 +93,7 @@ __device__ void init_capture_pose(const double *corners, const double *camera, c
     const double delta = normalize_angle(actual - expected);
     avg_angle += normalize_angle(delta - avg_angle) / (i + 1);
   }
-  const double local_z = focal * kArucoSize / sqrt(max_dist_sq);
+  const double local_z = focal * size / sqrt(max_dist_sq);
   const double local_position[3] = {avg_x * local_z / focal, avg_y * local_z / focal, local_z};
   const double local_rot[3] = {0.0, 0.0, avg_angle};
   const double inv_ar_rot[3] = {-ar_pose[3], -ar_pose[4], -ar_pose[5]};
@@ -109,12 +110,17 @@ __device__ void init_capture_pose(const double *corners, const double *camera, c
 // localizeOne holds every tag and the camera constant (ar_slam_util.cpp:965,
 // 972), so the first half of projectCorner, a = R(w_t) c_i + t_t (:144-148),
 // is the same for every query and iteration: computed once per batch solve.
-__global__ void k_tag_corners(int nt, const double *__restrict__ tag, double *__restrict__ aw) {
+// size: the tags' sides [nt], null = every tag of the default side.  The
+// gathered points carry the size into k_localize, k_localize_terms and
+// k_localize_cov, which need nothing else of it.
+__global__ void k_tag_corners(int nt, const double *__restrict__ tag, const double *__restrict__ size,
+                              double *__restrict__ aw) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;   // 4 t + corner
   if (e >= 4 * nt) return;
   const double *tg = tag + 6L * (e >> 2);
   const AngleAxis at = aa_prepare(tg + 3);
-  const double cpt[3] = {0.5 * kArucoSize * corner_dx(e & 3), 0.5 * kArucoSize * corner_dy(e & 3), 0.0};
+  const double half = size ? 0.5 * size[e >> 2] : kArucoHalf;
+  const double cpt[3] = {half * corner_dx(e & 3), half * corner_dy(e & 3), 0.0};
   double a[3];
   aa_rotate(at, cpt, a);
   aw[4L * e] = a[0] + tg[0];
@@ -371,8 +377,10 @@ __global__ __launch_bounds__(64, 2) void k_localize(LocParams p) {
     }
     return;
   }
-  if (p.init_from_map)
-    init_capture_pose(p.corners + 8L * res.init_obs, p.cam, p.tag + 6L * p.ot[res.init_obs], x);
+  if (p.init_from_map) {
+    const int t0 = p.ot[res.init_obs];
+    init_capture_pose(p.corners + 8L * res.init_obs, p.cam, p.tag + 6L * t0, p.tsize ? p.tsize[t0] : kArucoSize, x);
+  }
   const int nrow = 8 * k;
 #pragma unroll
   for (int ch = 0; ch < NCH; ++ch) {
@@ -770,7 +778,7 @@ void launch_localize(const LocParams &p, hipStream_t s) {
   if (p.nq == 0) return;
   if (p.nt > 0)   // the map's corner points (inside the timed region: one launch per batch solve)
     hipLaunchKernelGGL(k_tag_corners, dim3((unsigned)((4 * p.nt + 255) / 256)), dim3(256), 0, s, p.nt, p.tag,
-                       const_cast<double *>(p.aw));
+                       p.tsize, const_cast<double *>(p.aw));
   const dim3 block(64);
   if (!p.lk) {   // no observation has a robust loss: the code without one
     if (p.max_k <= 8)   // (cfg5: k = 8) two queries per wave

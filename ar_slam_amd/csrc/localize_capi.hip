@@ -17,6 +17,13 @@ struct arslam_localizer {
   arslam::DevBuf<double> cam, tag, corners, pose_in, pose_out, aw;
   arslam::DevBuf<int> qs, ot;
   arslam::DevBuf<unsigned char> tim;
+  // The map tags' sides.  The default (set_tag_size) holds for every tag of a
+  // batch loaded without an array; they are bound at the load.  has_size: some
+  // tag of the loaded batch has a side other than ARSLAM_DEFAULT_TAG_SIZE
+  // (else nothing is uploaded and the kernels run as without sizes).
+  double def_tag_size = ARSLAM_DEFAULT_TAG_SIZE;
+  bool has_size = false;
+  arslam::DevBuf<double> tsize;
   arslam::DevBuf<arslam_localize_result> res;
   // Robust losses.  The default (set_loss) holds for every observation of a
   // batch loaded without arrays; a batch's own arrays (load_loss) override it.
@@ -60,11 +67,16 @@ struct arslam_localizer {
                       "loss: unknown kind, or a scale that is not finite and > 0");
   }
 
-  // kinds / scales [n_obs]: the batch's own losses, both null = the handle's default
-  void load(const arslam_localize_batch *b, const unsigned char *kinds = nullptr, const double *scales = nullptr) {
+  // kinds / scales [n_obs]: the batch's own losses, both null = the handle's default;
+  // tag_size [n_tag]: the map tags' sides, null = the handle's default for every tag
+  void load(const arslam_localize_batch *b, const unsigned char *kinds = nullptr, const double *scales = nullptr,
+            const double *tag_size = nullptr) {
     using arslam::api_check;
     api_check(b != nullptr, ARSLAM_E_INVALID_ARG, "null batch");
     api_check(b->n_query >= 0 && b->n_tag >= 0 && b->n_obs >= 0, ARSLAM_E_INVALID_ARG, "negative sizes");
+    if (tag_size)
+      for (int t = 0; t < b->n_tag; ++t)
+        api_check(ARSLAM_TAG_SIZE_VALID(tag_size[t]), ARSLAM_E_INVALID_ARG, "tag_size: finite and > 0 (metres)");
     api_check((kinds == nullptr) == (scales == nullptr), ARSLAM_E_INVALID_ARG,
               "obs_loss_kind and obs_loss_a: both or neither");
     if (kinds)
@@ -102,6 +114,10 @@ struct arslam_localizer {
     up(pose_in, b->pose, 6L * nq);
     has_tim = b->tag_in_map != nullptr;
     if (has_tim) up(tim, b->tag_in_map, nt);
+    const std::vector<double> sizes = tag_size ? std::vector<double>(tag_size, tag_size + nt)
+                                               : std::vector<double>((size_t)nt, def_tag_size);
+    has_size = std::any_of(sizes.begin(), sizes.end(), [](double v) { return v != ARSLAM_DEFAULT_TAG_SIZE; });
+    if (has_size) up(tsize, sizes.data(), (size_t)nt);   // (the sync below: sizes is a local)
     pose_out.alloc(std::max(6L * nq, 1L));
     aw.alloc(std::max(16L * nt, 1L));
     res.alloc(std::max(nq, 1));
@@ -157,6 +173,7 @@ struct arslam_localizer {
     p.qs = qs.p; p.ot = ot.p; p.corners = corners.p; p.pose_in = pose_in.p; p.pose_out = pose_out.p;
     p.res = res.p; p.init_from_map = init_from_map; p.max_k = max_k;
     p.aw = aw.p; p.nt = nt;
+    p.tsize = has_size ? tsize.p : nullptr;
     p.max_iters = opt.max_num_iterations; p.max_invalid = opt.max_num_consecutive_invalid_steps;
     p.jacobi = opt.jacobi_scaling;
     p.ftol = opt.function_tolerance; p.gtol = opt.gradient_tolerance; p.ptol = opt.parameter_tolerance;
@@ -263,6 +280,26 @@ int arslam_localizer_load_loss(arslam_localizer *h, const arslam_localize_batch 
   return arslam::api_guarded([&] { h->load(b, obs_loss_kind, obs_loss_a); });
 }
 
+int arslam_localizer_set_tag_size(arslam_localizer *h, double size) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return arslam::api_guarded([&] {
+    arslam::api_check(ARSLAM_TAG_SIZE_VALID(size), ARSLAM_E_INVALID_ARG, "tag size: finite and > 0 (metres)");
+    h->def_tag_size = size;
+  });
+}
+
+int arslam_localizer_get_tag_size(const arslam_localizer *h, double *size) {
+  if (!h || !size) return ARSLAM_E_INVALID_ARG;
+  *size = h->def_tag_size;
+  return ARSLAM_OK;
+}
+
+int arslam_localizer_load_sized(arslam_localizer *h, const arslam_localize_batch *b, const double *tag_size,
+                                const unsigned char *obs_loss_kind, const double *obs_loss_a) {
+  if (!h || !b) return ARSLAM_E_INVALID_ARG;
+  return arslam::api_guarded([&] { h->load(b, obs_loss_kind, obs_loss_a, tag_size); });
+}
+
 int arslam_localizer_observation_terms(arslam_localizer *h, double *sq_residual, double *weight) {
   if (!h) return ARSLAM_E_INVALID_ARG;
   return arslam::api_guarded([&] { h->observation_terms(sq_residual, weight); });
@@ -281,12 +318,17 @@ int arslam_localizer_covariance_timed(arslam_localizer *h, double *cov, int *cov
 
 int arslam_localize_many_cov(const arslam_localize_batch *b, const arslam_lm_options *opt, int kind, double a,
                              arslam_localize_result *res, double *cov, int *cov_status) {
+  return arslam_localize_many_sized(b, opt, nullptr, kind, a, res, cov, cov_status);
+}
+
+int arslam_localize_many_sized(const arslam_localize_batch *b, const arslam_lm_options *opt, const double *tag_size,
+                               int kind, double a, arslam_localize_result *res, double *cov, int *cov_status) {
   if (!b) return ARSLAM_E_INVALID_ARG;
   arslam_localizer *h = nullptr;
   int rc = arslam_localizer_create(&h, opt);
   if (rc) return rc;
   rc = arslam_localizer_set_loss(h, kind, a);
-  if (!rc) rc = arslam_localizer_load(h, b);
+  if (!rc) rc = arslam_localizer_load_sized(h, b, tag_size, nullptr, nullptr);
   if (!rc) rc = arslam_localizer_solve(h, b->pose, res, nullptr);
   if (!rc && (cov || cov_status)) rc = arslam_localizer_covariance(h, cov, cov_status, nullptr);
   arslam_localizer_destroy(h);

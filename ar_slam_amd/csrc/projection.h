@@ -16,6 +16,11 @@ namespace arslam {
 namespace {
 
 constexpr double kArucoSize = 0.0635;  // ar_slam_util.hpp:319
+// Half the side of a tag of the default size.  The functions below take the
+// half-side of the observed tag: the corner is half * (+-1, +-1, 0), and
+// 0.5 * s and +-1 * half are exact, so kArucoHalf gives the bits of the
+// constant-size code.
+constexpr double kArucoHalf = 0.5 * kArucoSize;
 
 __device__ __forceinline__ double corner_dx(int i) { return (i == 1 || i == 2) ? 1.0 : -1.0; }
 __device__ __forceinline__ double corner_dy(int i) { return (i >= 2) ? 1.0 : -1.0; }
@@ -132,12 +137,13 @@ __device__ __forceinline__ void vecmat3(const double *v, const double *M, double
   o[2] = v[0] * M[2] + v[1] * M[5] + v[2] * M[8];
 }
 
-// Residual of one row (corner, comp) of ArucoReprojectionError.
+// Residual of one row (corner, comp) of ArucoReprojectionError, for a tag of
+// side 2 half.
 __device__ __forceinline__ double residual_row(const AngleAxis &ac, const double *cap,
                                                const AngleAxis &at, const double *tag, double f,
-                                               int corner, int comp, double obs, double *a_out,
-                                               double *p_out) {
-  const double cpt[3] = {0.5 * kArucoSize * corner_dx(corner), 0.5 * kArucoSize * corner_dy(corner), 0.0};
+                                               double half, int corner, int comp, double obs,
+                                               double *a_out, double *p_out) {
+  const double cpt[3] = {half * corner_dx(corner), half * corner_dy(corner), 0.0};
   double a[3], p[3];
   aa_rotate(at, cpt, a);
   a[0] += tag[0]; a[1] += tag[1]; a[2] += tag[2];   // ar_slam_util.cpp:146-148
@@ -151,13 +157,13 @@ __device__ __forceinline__ double residual_row(const AngleAxis &ac, const double
 
 // Residual row and its 13 non-zero Jacobian entries: [f, t_c(3), w_c(3), t_t(3), w_t(3)].
 __device__ __forceinline__ double residual_jacobian_row(const double *cam, const double *cap,
-                                                        const double *tag, int corner, int comp,
-                                                        double obs, double J[13]) {
+                                                        const double *tag, double half, int corner,
+                                                        int comp, double obs, double J[13]) {
   const AngleAxis ac = aa_prepare(cap + 3);
   const AngleAxis at = aa_prepare(tag + 3);
   double a[3], p[3];
   const double f = cam[0];
-  const double r = residual_row(ac, cap, at, tag, f, corner, comp, obs, a, p);
+  const double r = residual_row(ac, cap, at, tag, f, half, corner, comp, obs, a, p);
   const double x = p[0] / p[2], y = p[1] / p[2];
   const double fz = f / p[2];
   const double P[3] = {comp == 0 ? fz : 0.0, comp == 0 ? 0.0 : fz, comp == 0 ? -fz * x : -fz * y};
@@ -181,7 +187,7 @@ __device__ __forceinline__ double residual_jacobian_row(const double *cam, const
     J[4] = -v[0]; J[5] = -v[1]; J[6] = -v[2];
   }
   // d/dw_t = -((P Mc Mt) x c) Jr_t   (small branch: -((P Mc) x c))
-  const double cpt[3] = {0.5 * kArucoSize * corner_dx(corner), 0.5 * kArucoSize * corner_dy(corner), 0.0};
+  const double cpt[3] = {half * corner_dx(corner), half * corner_dy(corner), 0.0};
   if (at.big) {
     double Mt[9], PMM[3], o[3], Jr[9];
     aa_matrix(at, Mt);

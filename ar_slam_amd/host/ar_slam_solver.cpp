@@ -17,7 +17,6 @@ namespace arslam {
 
 namespace {
 
-constexpr double kArucoSize = 0.0635;   // ar_slam_util.hpp:319
 constexpr double kDirections[4][2] = {{-1.0, -1.0}, {1.0, -1.0}, {1.0, 1.0}, {-1.0, 1.0}};   // :340-345
 
 void check(int rc) {
@@ -81,7 +80,7 @@ void composeAxisAngle(const double *rot1, const double *rot2, double *out) {   /
   quat_to_aa(q3, out);
 }
 
-void calcInitValues(const ArucoRect &rect, double focal, double out[4]) {   // :52-95
+void calcInitValues(const ArucoRect &rect, double focal, double out[4], double aruco_size) {   // :52-95
   double max_dist_sq = 0.0, avg_x = 0.0, avg_y = 0.0;
   for (unsigned i = 0; i < 4; ++i) {
     const Point &p1 = rect.corners[i], &p2 = rect.corners[(i + 1) & 3];
@@ -100,7 +99,7 @@ void calcInitValues(const ArucoRect &rect, double focal, double out[4]) {   // :
     const double delta = normalize_angle(actual - expected);
     avg_angle += normalize_angle(delta - avg_angle) / (i + 1);
   }
-  const double local_z = focal * kArucoSize / std::sqrt(max_dist_sq);
+  const double local_z = focal * aruco_size / std::sqrt(max_dist_sq);
   out[0] = avg_x * local_z / focal;
   out[1] = avg_y * local_z / focal;
   out[2] = local_z;
@@ -108,9 +107,9 @@ void calcInitValues(const ArucoRect &rect, double focal, double out[4]) {   // :
 }
 
 void initCapturePose(const ArucoRect &rect, const double *camera, const double *ar_pose,
-                     double *inv) {   // :98-115
+                     double *inv, double aruco_size) {   // :98-115
   double v[4];
-  calcInitValues(rect, camera[0], v);
+  calcInitValues(rect, camera[0], v, aruco_size);
   const double local_position[3] = {v[0], v[1], v[2]};
   const double local_rot[3] = {0.0, 0.0, v[3]};
   const double inv_ar_rot[3] = {-ar_pose[3], -ar_pose[4], -ar_pose[5]};
@@ -123,9 +122,9 @@ void initCapturePose(const ArucoRect &rect, const double *camera, const double *
 }
 
 void initArPose(const ArucoRect &rect, const double *camera, const double *inv,
-                double *ar_pose) {   // :118-128
+                double *ar_pose, double aruco_size) {   // :118-128
   double v[4];
-  calcInitValues(rect, camera[0], v);
+  calcInitValues(rect, camera[0], v, aruco_size);
   const double local_position[3] = {v[0], v[1], v[2]};
   const double cap_rotation[3] = {-inv[3], -inv[4], -inv[5]};
   angle_axis_rotate(cap_rotation, local_position, ar_pose);
@@ -168,6 +167,8 @@ Aruco &ArSlamSolver::addAruco(const std::string &ar_id) {   // :430-436
   Aruco &a = arucos_.back();
   a.id = ar_id;
   a.handle = ArucoHandle{idx};
+  const auto sz = aruco_size_by_id_.find(ar_id);
+  a.size = sz != aruco_size_by_id_.end() ? sz->second : default_aruco_size_;
   return a;
 }
 
@@ -231,6 +232,14 @@ void ArSlamSolver::loadYamlString(const std::string &text) {   // :304-384
       Aruco &aruco = addAruco(kv.first);
       const yaml::Node &pd = kv.second["pose"];
       for (size_t i = 0; i < aruco.pose.params.size(); ++i) aruco.pose.params[i] = pd[i].as_double();
+      // (optional: saveYaml leaves it out for a tag of the default side, so a
+      // missing key means that side, not this solver's default or by-id side)
+      aruco.size = ARSLAM_DEFAULT_TAG_SIZE;
+      if (const yaml::Node *sz = kv.second.find("size")) {
+        const double v = sz->as_double();
+        if (!ARSLAM_TAG_SIZE_VALID(v)) throw std::runtime_error("aruco " + kv.first + ": size must be finite and > 0");
+        aruco.size = v;
+      }
     }
   }
   if (const yaml::Node *blocks = doc.find("blocks")) {
@@ -291,6 +300,7 @@ void ArSlamSolver::saveYaml(std::ostream &y) const {   // :387-465 (yaml-cpp emi
     y << "  " << quote_if_needed(a.id) << ":\n    pose: ";
     flow(a.pose.params.data(), 6);
     y << "\n";
+    if (a.size != ARSLAM_DEFAULT_TAG_SIZE) y << "    size: " << format_double(a.size) << "\n";
   }
   y << "camera:\n  params: ";
   flow(camera_.params.data(), 3);
@@ -355,21 +365,27 @@ void ArSlamSolver::addCaptureBlocks(Capture &capture) {   // block loop of :704-
     Aruco &aruco = at(block.aruco);
     if (!aruco.initialized) {
       aruco.initialized = true;
-      initArPose(block.aruco_rect, camera_.params.data(), capture.data(), aruco.data());
+      initArPose(block.aruco_rect, camera_.params.data(), capture.data(), aruco.data(), aruco.size);
     }
     if (block.added) throw std::runtime_error("block for capture was somehow already added?");
     block.added = true;
     double xy[8];
     for (int i = 0; i < 4; ++i) { xy[2 * i] = block.aruco_rect.corners[i].x; xy[2 * i + 1] = block.aruco_rect.corners[i].y; }
     // was: problem_.AddResidualBlock(AutoDiffCostFunction<ArucoReprojectionError,8,3,6,6>, nullptr, ...)
-    check(arslam_lm_add_residual_block(problem_, xy, camera_.params.data(), capture.data(), aruco.data()));
+    // (the handle's default loss, as arslam_lm_add_residual_block gives it; the tag's own side)
+    int loss_kind = ARSLAM_LOSS_NONE;
+    double loss_a = 0.0;
+    check(arslam_lm_get_loss(problem_, &loss_kind, &loss_a));
+    check(arslam_lm_add_residual_block_sized(problem_, xy, camera_.params.data(), capture.data(), aruco.data(),
+                                             aruco.size, loss_kind, loss_a));
   }
 }
 
 void ArSlamSolver::solveCapture(Capture &capture, std::optional<BlockHandle> init_block) {   // :680-742
   if (init_block) {
     const Block &block = at(*init_block);
-    initCapturePose(block.aruco_rect, camera_.params.data(), at(block.aruco).data(), capture.data());
+    initCapturePose(block.aruco_rect, camera_.params.data(), at(block.aruco).data(), capture.data(),
+                    at(block.aruco).size);
   }
   addCaptureBlocks(capture);
   optimize(capture);
@@ -393,7 +409,8 @@ void ArSlamSolver::solve() {   // :744-866
     Capture &capture = at(ch);
     if (ch.idx != best_cap_idx) {
       const Block &block = at(*capture.init_block);
-      initCapturePose(block.aruco_rect, camera_.params.data(), at(block.aruco).data(), at(block.capture).data());
+      initCapturePose(block.aruco_rect, camera_.params.data(), at(block.aruco).data(), at(block.capture).data(),
+                      at(block.aruco).size);
     }
     addCaptureBlocks(capture);
     optimize(capture);
@@ -425,7 +442,11 @@ void ArSlamSolver::localizeMany(unsigned first_loc_cap_idx) {   // :888-901, eac
     for (BlockHandle bh : a.blocks)
       if (at(bh).capture.idx < first_loc_cap_idx) { in_map[a.handle.idx] = 1; break; }
   std::vector<double> tags(6 * std::max<size_t>(arucos_.size(), 1));
-  for (const Aruco &a : arucos_) std::copy(a.pose.params.begin(), a.pose.params.end(), tags.begin() + 6 * a.handle.idx);
+  std::vector<double> sizes(std::max<size_t>(arucos_.size(), 1), ARSLAM_DEFAULT_TAG_SIZE);
+  for (const Aruco &a : arucos_) {
+    std::copy(a.pose.params.begin(), a.pose.params.end(), tags.begin() + 6 * a.handle.idx);
+    sizes[a.handle.idx] = a.size;
+  }
   std::vector<int> q_start{0}, obs_tag;
   std::vector<double> corners, pose;
   std::vector<unsigned> qcap;
@@ -459,7 +480,7 @@ void ArSlamSolver::localizeMany(unsigned first_loc_cap_idx) {   // :888-901, eac
   // evaluate there on the first request (nothing more runs when nobody asks)
   check(arslam_localizer_create(&localizer_, &options_));
   check(arslam_localizer_set_loss(localizer_, localize_loss_kind_, localize_loss_a_));
-  check(arslam_localizer_load(localizer_, &b));
+  check(arslam_localizer_load_sized(localizer_, &b, sizes.data(), nullptr, nullptr));
   check(arslam_localizer_solve(localizer_, pose.data(), res.data(), nullptr));
   loc_first_ = first_loc_cap_idx;
   loc_count_ = (unsigned)qcap.size();
@@ -522,6 +543,26 @@ int ArSlamSolver::setLocalizeLoss(int kind, double a) {
   if (!loss_valid(kind, a)) return ARSLAM_E_INVALID_ARG;
   localize_loss_kind_ = kind;
   localize_loss_a_ = a;
+  return ARSLAM_OK;
+}
+
+int ArSlamSolver::setDefaultArucoSize(double size) {
+  if (!ARSLAM_TAG_SIZE_VALID(size)) return ARSLAM_E_INVALID_ARG;
+  default_aruco_size_ = size;
+  return ARSLAM_OK;
+}
+
+int ArSlamSolver::setArucoSize(const std::string &id, double size) {
+  if (!ARSLAM_TAG_SIZE_VALID(size)) return ARSLAM_E_INVALID_ARG;
+  const auto it = aruco_map_.find(id);
+  if (it != aruco_map_.end()) {
+    Aruco &a = arucos_[it->second];
+    bool bound = a.initialized;
+    for (BlockHandle bh : a.blocks) bound = bound || at(bh).added;
+    if (bound) return ARSLAM_E_STATE;   // its pose or a residual block was made with the side it has
+    a.size = size;
+  }
+  aruco_size_by_id_[id] = size;
   return ARSLAM_OK;
 }
 

@@ -81,6 +81,9 @@ struct Aruco {   // :229-240
   PoseParams pose;
   double *data() { return pose.params.data(); }
   const double *data() const { return pose.params.data(); }
+  // the tag's side in metres (the reference's one aruco_size, ar_slam_util.hpp:319,
+  // per tag): setArucoSize / setDefaultArucoSize, the map file's optional key
+  double size = ARSLAM_DEFAULT_TAG_SIZE;
 };
 
 struct Block {   // :296-315
@@ -176,6 +179,15 @@ class ArSlamSolver {
   // reference passes nullptr, ar_slam_util.cpp:956-963): localizeMany then
   // runs through arslam_localize_many_loss.  Same return values as setLoss.
   int setLocalizeLoss(int kind, double a);
+  // Tag sides in metres.  The default holds for the tags created afterwards
+  // (by addDetections or loadYaml without the key).  setArucoSize names a tag
+  // by its id string and may precede the tag's first detection; once the tag
+  // is initialised or a residual block of it has been added its side is bound:
+  // ARSLAM_E_STATE.  A side that is not finite or not > 0: ARSLAM_E_INVALID_ARG.
+  // The sides reach the residual blocks (arslam_lm_add_residual_block_sized),
+  // the initialisers and localizeMany's batch.
+  int setDefaultArucoSize(double size);
+  int setArucoSize(const std::string &id, double size);
   // The 6x6 covariance (arslam_localizer_covariance: row-major, [t_c, w_c],
   // unit-variance residuals) and its ARSLAM_COV_* status of a capture the last
   // localizeMany localized, at the pose it was given -- ceres::Covariance on
@@ -215,6 +227,8 @@ class ArSlamSolver {
   bool verbose_ = false;
   int localize_loss_kind_ = ARSLAM_LOSS_NONE;   // setLocalizeLoss
   double localize_loss_a_ = 0.0;
+  double default_aruco_size_ = ARSLAM_DEFAULT_TAG_SIZE;
+  std::unordered_map<std::string, double> aruco_size_by_id_;   // setArucoSize before the tag exists
   // the last localizeMany: its resident batch, the captures it covered
   // (loc_first_ + q is query q) and their covariances once asked for
   void dropLocalizer();
@@ -226,8 +240,11 @@ class ArSlamSolver {
 
 // initialisers (ar_slam_util.cpp:41-128)
 void composeAxisAngle(const double *rot1, const double *rot2, double *out);
-void calcInitValues(const ArucoRect &rect, double focal, double out[4]);
-void initCapturePose(const ArucoRect &rect, const double *camera, const double *ar_pose, double *inv_cap_pose);
-void initArPose(const ArucoRect &rect, const double *camera, const double *inv_cap_pose, double *ar_pose);
+// (aruco_size: the side of the tag the rectangle shows; the depth is proportional to it)
+void calcInitValues(const ArucoRect &rect, double focal, double out[4], double aruco_size = ARSLAM_DEFAULT_TAG_SIZE);
+void initCapturePose(const ArucoRect &rect, const double *camera, const double *ar_pose, double *inv_cap_pose,
+                     double aruco_size = ARSLAM_DEFAULT_TAG_SIZE);
+void initArPose(const ArucoRect &rect, const double *camera, const double *inv_cap_pose, double *ar_pose,
+                double aruco_size = ARSLAM_DEFAULT_TAG_SIZE);
 
 }  // namespace arslam

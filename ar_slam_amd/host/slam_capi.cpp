@@ -72,6 +72,42 @@ int arslam_slam_set_localize_loss(arslam_slam *h, int kind, double a) {
   return h->s.setLocalizeLoss(kind, a);
 }
 
+int arslam_slam_set_default_aruco_size(arslam_slam *h, double size) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return h->s.setDefaultArucoSize(size);
+}
+
+int arslam_slam_set_aruco_size(arslam_slam *h, const char *id, double size) {
+  if (!h || !id) return ARSLAM_E_INVALID_ARG;
+  int rc = ARSLAM_OK;
+  const int g = slam_guarded([&] { rc = h->s.setArucoSize(id, size); });
+  if (!g && rc == ARSLAM_E_STATE)
+    arslam::set_last_error("set_aruco_size: the tag is initialised or has residual blocks; its side is bound");
+  return g ? g : rc;
+}
+
+int arslam_slam_aruco_size(const arslam_slam *h, int a, double *size) {
+  if (!h || !size || a < 0 || a >= (int)h->s.numArucos()) return ARSLAM_E_INVALID_ARG;
+  *size = h->s.at(arslam::ArucoHandle{(unsigned)a}).size;
+  return ARSLAM_OK;
+}
+
+int arslam_slam_debug_init_pose(int which, const double rect[8], const double camera[3], const double pose_in[6],
+                                double size, double pose_out[6]) {
+  if ((which != 0 && which != 1) || !rect || !camera || !pose_in || !pose_out) return ARSLAM_E_INVALID_ARG;
+  if (size != 0.0 && !ARSLAM_TAG_SIZE_VALID(size)) return ARSLAM_E_INVALID_ARG;
+  arslam::ArucoRect r;
+  for (int i = 0; i < 4; ++i) r.corners[i] = arslam::Point{rect[2 * i], rect[2 * i + 1]};
+  if (which == 0) {
+    if (size == 0.0) arslam::initArPose(r, camera, pose_in, pose_out);
+    else arslam::initArPose(r, camera, pose_in, pose_out, size);
+  } else {
+    if (size == 0.0) arslam::initCapturePose(r, camera, pose_in, pose_out);
+    else arslam::initCapturePose(r, camera, pose_in, pose_out, size);
+  }
+  return ARSLAM_OK;
+}
+
 int arslam_slam_load_yaml(arslam_slam *h, const char *path) {
   if (!h || !path) return ARSLAM_E_INVALID_ARG;
   return slam_guarded([&] { h->s.loadYaml(path); });

@@ -46,6 +46,11 @@ EXPORTS = ["arslam_lm_options_init", "arslam_lm_create", "arslam_lm_destroy",
            "arslam_lm_set_iteration_callback", "arslam_lm_owned_captures",
            "arslam_lm_set_loss", "arslam_lm_get_loss", "arslam_lm_add_residual_block_loss",
            "arslam_lm_load_soa_loss", "arslam_debug_residual_jacobian_loss", "arslam_slam_set_loss",
+           "arslam_lm_set_tag_size", "arslam_lm_get_tag_size", "arslam_lm_add_residual_block_sized",
+           "arslam_lm_load_soa_sized", "arslam_debug_residual_jacobian_sized",
+           "arslam_localizer_set_tag_size", "arslam_localizer_get_tag_size", "arslam_localizer_load_sized",
+           "arslam_localize_many_sized",
+           "arslam_slam_debug_init_pose", "arslam_slam_set_default_aruco_size", "arslam_slam_set_aruco_size", "arslam_slam_aruco_size",
            "arslam_debug_residual_jacobian", "arslam_debug_dense_llt", "arslam_debug_dense_llt_ex",
            "arslam_debug_tile_llt", "arslam_debug_tile_plan",
            "arslam_debug_angle_axis_rotate", "arslam_debug_selinv", "arslam_lm_debug_force_indefinite",
@@ -81,6 +86,7 @@ ELIM_AUTO, ELIM_CAPTURES, ELIM_TAGS, ELIM_MIXED = 0, 1, 2, 3   # arslam_lm_optio
 SETUP_LOAD, SETUP_VALUES, SETUP_APPEND = 0, 1, 2   # arslam_lm_summary.setup_kind
 # ceres::LossFunction of a residual block (arslam_lm.h ARSLAM_LOSS_*); a loss is (kind, a)
 LOSS_NONE, LOSS_HUBER, LOSS_SOFT_L_ONE, LOSS_CAUCHY = 0, 1, 2, 3
+DEFAULT_TAG_SIZE = 0.0635   # arslam_lm.h ARSLAM_DEFAULT_TAG_SIZE: the side of a tag, metres
 _ip = C.POINTER(C.c_int)
 _up = C.POINTER(C.c_ubyte)
 
@@ -257,6 +263,22 @@ def lib():
         L.arslam_localize_many_cov.argtypes = [C.POINTER(LocalizeBatchC), C.POINTER(Options), C.c_int, C.c_double,
                                                C.POINTER(LocalizeResult), _dp, _ip]
         L.arslam_slam_localize_covariance.argtypes = [C.c_void_p, C.c_int, _dp, _ip]
+    if hasattr(L, "arslam_lm_set_tag_size"):
+        L.arslam_lm_set_tag_size.argtypes = [C.c_void_p, C.c_double]
+        L.arslam_lm_get_tag_size.argtypes = [C.c_void_p, _dp]
+        L.arslam_lm_add_residual_block_sized.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, C.c_double, C.c_int,
+                                                         C.c_double]
+        L.arslam_lm_load_soa_sized.argtypes = [C.c_void_p, C.POINTER(SoaProblem), _dp, _up, _dp]
+        L.arslam_debug_residual_jacobian_sized.argtypes = [C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
+        L.arslam_localizer_set_tag_size.argtypes = [C.c_void_p, C.c_double]
+        L.arslam_localizer_get_tag_size.argtypes = [C.c_void_p, _dp]
+        L.arslam_localizer_load_sized.argtypes = [C.c_void_p, C.POINTER(LocalizeBatchC), _dp, _up, _dp]
+        L.arslam_localize_many_sized.argtypes = [C.POINTER(LocalizeBatchC), C.POINTER(Options), _dp, C.c_int,
+                                                 C.c_double, C.POINTER(LocalizeResult), _dp, _ip]
+        L.arslam_slam_set_default_aruco_size.argtypes = [C.c_void_p, C.c_double]
+        L.arslam_slam_set_aruco_size.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
+        L.arslam_slam_aruco_size.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.arslam_slam_debug_init_pose.argtypes = [C.c_int, _dp, _dp, _dp, C.c_double, _dp]
     L.arslam_lm_set_parameter_block_constant.argtypes = [C.c_void_p, _dp]
     L.arslam_lm_set_parameter_block_variable.argtypes = [C.c_void_p, _dp]
     L.arslam_lm_solve.argtypes = [C.c_void_p, C.POINTER(Summary)]
@@ -416,6 +438,17 @@ class _Handle:
         _check(lib().arslam_lm_get_loss(self._h, C.byref(k), C.byref(a)))
         return k.value, a.value
 
+    def set_tag_size(self, size):
+        """The handle's default tag side in metres (DEFAULT_TAG_SIZE on creation): what
+        add_residual_block gives the blocks added afterwards and a bulk load gives every tag.
+        Drops a loaded SoA problem."""
+        _check(lib().arslam_lm_set_tag_size(self._h, float(size)))
+
+    def get_tag_size(self):
+        s = C.c_double(0.0)
+        _check(lib().arslam_lm_get_tag_size(self._h, C.byref(s)))
+        return s.value
+
     def set_iteration_callback(self, fn):
         """ceres::IterationCallback: fn(iteration dict) -> SOLVER_CONTINUE / SOLVER_ABORT /
         SOLVER_TERMINATE_SUCCESSFULLY (None = continue); fn=None removes it."""
@@ -476,9 +509,10 @@ class ResidentProblem(_Handle):
 
     def __init__(self, camera, cap, tag, obs_cap, obs_tag, corners, camera_const=False,
                  cap_const=None, tag_const=None, comm=None, force_multirank=False, loss=None, obs_loss=None,
-                 **opts):
+                 tag_size=None, **opts):
         """loss = (kind, a): the robust loss of every observation (the handle's default loss);
-        obs_loss = (kinds[n_obs], a[n_obs]): one loss per observation, in observation order."""
+        obs_loss = (kinds[n_obs], a[n_obs]): one loss per observation, in observation order;
+        tag_size = [n_tag] the tags' sides in metres (a scalar: every tag's); None: DEFAULT_TAG_SIZE."""
         super().__init__(**opts)
         if force_multirank:
             self.debug_force_multirank(True)
@@ -487,13 +521,20 @@ class ResidentProblem(_Handle):
         if loss is not None:
             self.set_loss(*loss)
         self.A = _Soa(camera, cap, tag, obs_cap, obs_tag, corners, camera_const, cap_const, tag_const)
-        if obs_loss is None:
-            _check(lib().arslam_lm_load_soa(self._h, C.byref(self.A.s)))
-        else:
+        kinds = scales = None
+        if obs_loss is not None:
             kinds = np.ascontiguousarray(obs_loss[0], np.uint8).reshape(-1)
             scales = _f64(obs_loss[1]).reshape(-1)
             if kinds.shape[0] != self.A.s.n_obs or scales.shape[0] != self.A.s.n_obs:
                 raise ValueError("obs_loss: one kind and one scale per observation")
+        if tag_size is not None:
+            sizes = _f64(np.broadcast_to(np.asarray(tag_size, np.float64), (self.A.s.n_tag,)))
+            _check(lib().arslam_lm_load_soa_sized(self._h, C.byref(self.A.s), sizes.ctypes.data_as(_dp),
+                                                  kinds.ctypes.data_as(_up) if kinds is not None else None,
+                                                  scales.ctypes.data_as(_dp) if scales is not None else None))
+        elif obs_loss is None:
+            _check(lib().arslam_lm_load_soa(self._h, C.byref(self.A.s)))
+        else:
             _check(lib().arslam_lm_load_soa_loss(self._h, C.byref(self.A.s), kinds.ctypes.data_as(_up),
                                                  scales.ctypes.data_as(_dp)))
 
@@ -585,10 +626,17 @@ class Problem(_Handle):
             raise TypeError(f"parameter block must be a C-contiguous float64 array of size {n}")
         return a.ctypes.data_as(_dp)
 
-    def add_residual_block(self, corners, camera, capture, tag, loss=None):
-        """loss = (kind, a): this block's own robust loss; None: the handle's default (set_loss)."""
+    def add_residual_block(self, corners, camera, capture, tag, loss=None, size=None):
+        """loss = (kind, a): this block's own robust loss; None: the handle's default (set_loss).
+        size: the side of this block's tag in metres; None: the handle's default (set_tag_size)."""
         c = _f64(corners).reshape(8)
         self._keep += [camera, capture, tag]
+        if size is not None:
+            kind, a = self.get_loss() if loss is None else loss
+            _check(lib().arslam_lm_add_residual_block_sized(self._h, c.ctypes.data_as(_dp),
+                                                            self._block(camera, 3), self._block(capture, 6),
+                                                            self._block(tag, 6), float(size), int(kind), float(a)))
+            return
         if loss is not None:
             _check(lib().arslam_lm_add_residual_block_loss(self._h, c.ctypes.data_as(_dp),
                                                            self._block(camera, 3), self._block(capture, 6),
@@ -652,6 +700,17 @@ class Problem(_Handle):
 
 # ---- component entry points (include/arslam_lm_debug.h) ----
 
+def debug_slam_init_pose(which, rect, camera, pose_in, size=None):
+    """The host mirror's initialisers alone (no device): which = "ar": initArPose from the capture's
+    inv_pose, "capture": initCapturePose from the tag's pose; for a tag of side `size` (None: the
+    call with the default argument).  arslam_slam_debug_init_pose."""
+    rect, camera, pose_in = _f64(rect).reshape(8), _f64(camera).reshape(3), _f64(pose_in).reshape(6)
+    out = np.zeros(6)
+    _check(lib().arslam_slam_debug_init_pose({"ar": 0, "capture": 1}[which], rect.ctypes.data_as(_dp),
+                                             camera.ctypes.data_as(_dp), pose_in.ctypes.data_as(_dp),
+                                             0.0 if size is None else float(size), out.ctypes.data_as(_dp)))
+    return out
+
 def debug_residual_jacobian(cam, cap, tag, corners):
     """Device residuals (n,8) and Jacobians (n,8,15) of n independent observations."""
     cap = _f64(cap, (-1, 6))
@@ -664,6 +723,23 @@ def debug_residual_jacobian(cam, cap, tag, corners):
     _check(lib().arslam_debug_residual_jacobian(n, cam.ctypes.data_as(_dp), cap.ctypes.data_as(_dp),
                                                 tag.ctypes.data_as(_dp), corners.ctypes.data_as(_dp),
                                                 r.ctypes.data_as(_dp), J.ctypes.data_as(_dp)))
+    return r, J
+
+
+def debug_residual_jacobian_sized(cam, cap, tag, corners, size):
+    """debug_residual_jacobian for tags of side size[n] (metres; a scalar: every tag's)."""
+    cap = _f64(cap, (-1, 6))
+    n = cap.shape[0]
+    cam = _f64(np.broadcast_to(np.asarray(cam, np.float64), (n, 3)))
+    tag = _f64(tag, (-1, 6))
+    corners = _f64(corners, (-1, 8))
+    size = _f64(np.broadcast_to(np.asarray(size, np.float64), (n,)))
+    r = np.zeros((n, 8))
+    J = np.zeros((n, 8, 15))
+    _check(lib().arslam_debug_residual_jacobian_sized(n, cam.ctypes.data_as(_dp), cap.ctypes.data_as(_dp),
+                                                      tag.ctypes.data_as(_dp), corners.ctypes.data_as(_dp),
+                                                      size.ctypes.data_as(_dp), r.ctypes.data_as(_dp),
+                                                      J.ctypes.data_as(_dp)))
     return r, J
 
 
@@ -1045,14 +1121,26 @@ class _LocArrays:
                                 int(bool(init_from_map)))
 
 
-def localize_many(batch, init_from_map=True, pose=None, loss=None, covariance=False, **opts):
+def localize_many(batch, init_from_map=True, pose=None, loss=None, covariance=False, tag_size=None, **opts):
     """localizeMany on the device (one-shot).  ``batch`` has camera, tag, q_start, obs_tag,
     corners, tag_in_map (synth.LocalizeBatch).  loss = (kind, a): every observation's robust loss
-    (LOSS_*, scale); the results' costs are then the robust cost.  Returns (pose (Nq,6), results
+    (LOSS_*, scale); the results' costs are then the robust cost.  tag_size: the map tags' sides in
+    metres, [n_tag] or a scalar (None: DEFAULT_TAG_SIZE).  Returns (pose (Nq,6), results
     dict of arrays); with covariance=True also cov (Nq, 6, 6) and its status (Nq,), COV_*
     (Localizer.covariance)."""
     A = _LocArrays(batch, init_from_map, pose)
     res = (LocalizeResult * max(A.s.n_query, 1))()
+    if tag_size is not None:
+        nq = A.s.n_query
+        sizes = _f64(np.broadcast_to(np.asarray(tag_size, np.float64), (A.s.n_tag,)))
+        cov, st = np.zeros((max(nq, 1), 6, 6)), np.zeros(max(nq, 1), np.int32)
+        kind, a = (LOSS_NONE, 0.0) if loss is None else loss
+        _check(lib().arslam_localize_many_sized(C.byref(A.s), C.byref(make_options(**opts)), sizes.ctypes.data_as(_dp),
+                                                int(kind), float(a), res,
+                                                cov.ctypes.data_as(_dp) if covariance else None,
+                                                st.ctypes.data_as(_ip) if covariance else None))
+        out = (A.pose, _loc_results(res[:nq]))
+        return out + (cov[:nq], st[:nq]) if covariance else out
     if covariance:
         nq = A.s.n_query
         cov, st = np.zeros((max(nq, 1), 6, 6)), np.zeros(max(nq, 1), np.int32)
@@ -1071,10 +1159,11 @@ def localize_many(batch, init_from_map=True, pose=None, loss=None, covariance=Fa
 class Localizer:
     """Resident batched localizer: load a batch once, solve it many times."""
 
-    def __init__(self, batch, init_from_map=True, pose=None, loss=None, obs_loss=None, **opts):
+    def __init__(self, batch, init_from_map=True, pose=None, loss=None, obs_loss=None, tag_size=None, **opts):
         """loss = (kind, a): the robust loss of every observation (the handle's default loss);
         obs_loss = (kinds[n_obs], a[n_obs]): one loss per observation of this batch, in observation
-        order, overriding the default."""
+        order, overriding the default; tag_size: the map tags' sides in metres, [n_tag] or a scalar
+        (None: DEFAULT_TAG_SIZE)."""
         self._h = C.c_void_p()
         _check(lib().arslam_localizer_create(C.byref(self._h), C.byref(make_options(**opts))))
         self.A = _LocArrays(batch, init_from_map, pose)
@@ -1082,15 +1171,31 @@ class Localizer:
         self.n_obs = self.A.s.n_obs
         if loss is not None:
             self.set_loss(*loss)
-        if obs_loss is None:
-            _check(lib().arslam_localizer_load(self._h, C.byref(self.A.s)))
-        else:
+        kinds = scales = None
+        if obs_loss is not None:
             kinds = np.ascontiguousarray(obs_loss[0], np.uint8).reshape(-1)
             scales = _f64(obs_loss[1]).reshape(-1)
             if kinds.shape[0] != self.n_obs or scales.shape[0] != self.n_obs:
                 raise ValueError("obs_loss: one kind and one scale per observation")
+        if tag_size is not None:
+            sizes = _f64(np.broadcast_to(np.asarray(tag_size, np.float64), (self.A.s.n_tag,)))
+            _check(lib().arslam_localizer_load_sized(self._h, C.byref(self.A.s), sizes.ctypes.data_as(_dp),
+                                                     kinds.ctypes.data_as(_up) if kinds is not None else None,
+                                                     scales.ctypes.data_as(_dp) if scales is not None else None))
+        elif obs_loss is None:
+            _check(lib().arslam_localizer_load(self._h, C.byref(self.A.s)))
+        else:
             _check(lib().arslam_localizer_load_loss(self._h, C.byref(self.A.s), kinds.ctypes.data_as(_up),
                                                     scales.ctypes.data_as(_dp)))
+
+    def set_tag_size(self, size):
+        """The default side (metres) of every map tag of a batch loaded afterwards."""
+        _check(lib().arslam_localizer_set_tag_size(self._h, float(size)))
+
+    def get_tag_size(self):
+        s = C.c_double(0.0)
+        _check(lib().arslam_localizer_get_tag_size(self._h, C.byref(s)))
+        return s.value
 
     def set_loss(self, kind, a=0.0):
         """The default loss (LOSS_*, scale a) of every observation, from the next solve() on; the
@@ -1185,6 +1290,20 @@ class SlamSolver:
     def set_localize_loss(self, kind, a=0.0):
         """The robust loss (LOSS_*, scale a) of every residual block localize_many adds."""
         _check(lib().arslam_slam_set_localize_loss(self._h, int(kind), C.c_double(float(a))))
+
+    def set_default_aruco_size(self, size):
+        """The side (metres) of the tags created from now on (DEFAULT_TAG_SIZE initially)."""
+        _check(lib().arslam_slam_set_default_aruco_size(self._h, float(size)))
+
+    def set_aruco_size(self, tag_id, size):
+        """The side (metres) of the tag with this id string; may precede its first detection.
+        STATE once the tag is initialised or has residual blocks."""
+        _check(lib().arslam_slam_set_aruco_size(self._h, str(tag_id).encode(), float(size)))
+
+    def aruco_size(self, a):
+        s = C.c_double(0.0)
+        _check(lib().arslam_slam_aruco_size(self._h, int(a), C.byref(s)))
+        return s.value
 
     def load_yaml(self, path):
         _check(lib().arslam_slam_load_yaml(self._h, str(path).encode()))

@@ -147,12 +147,20 @@ def angle_axis_rotate(w, x):
     return np.where(big[:, None], rot_big, rot_small)
 
 
-def project_corners(camera, cap, tag):
-    """Project all 4 corners of each (cap row, tag row) pair -> (N,8)."""
+def _tag_corner(d, n, size=None):
+    """Corner of direction d of n tags in their own frames (n,3); size: their sides (n,), None: ARUCO_SIZE."""
+    if size is None:
+        return np.tile([0.5 * ARUCO_SIZE * d[0], 0.5 * ARUCO_SIZE * d[1], 0.0], (n, 1))
+    half = 0.5 * np.broadcast_to(np.asarray(size, np.float64), (n,))
+    return np.stack([half * d[0], half * d[1], np.zeros(n)], 1)
+
+
+def project_corners(camera, cap, tag, size=None):
+    """Project all 4 corners of each (cap row, tag row) pair -> (N,8); size: each row's tag side."""
     n = cap.shape[0]
     out = np.empty((n, 8))
     for i, d in enumerate(ARUCO_DIRECTIONS):
-        corner = np.tile([0.5 * ARUCO_SIZE * d[0], 0.5 * ARUCO_SIZE * d[1], 0.0], (n, 1))
+        corner = _tag_corner(d, n, size)
         a = angle_axis_rotate(tag[:, 3:], corner) + tag[:, :3]
         b = a + cap[:, :3]
         p = angle_axis_rotate(cap[:, 3:], b)
@@ -204,13 +212,16 @@ def _visible_nearest(R_cw, pos, corners_w, centres, cand, k):
 
 def make_graph(n_captures, grid_x, grid_y, seed, k=8, noise_px=0.5,
                init_trans_sigma=0.02, init_rot_sigma=0.02, f_init=1.1 * F_TRUE,
-               max_tilt=np.deg2rad(20.0), name="", full_rotation=False, depth=(0.6, 1.2)):
+               max_tilt=np.deg2rad(20.0), name="", full_rotation=False, depth=(0.6, 1.2), tag_size=None):
     """Generate a connected capture/tag graph with exactly ``k`` tags per capture (``k`` an int,
-    or a sequence: capture c sees ``k[c % len(k)]`` tags; cameras ``depth`` metres from the plane)."""
+    or a sequence: capture c sees ``k[c % len(k)]`` tags; cameras ``depth`` metres from the plane).
+    ``tag_size``: the tags' sides in metres, a scalar or one per tag (None: ARUCO_SIZE, and the
+    graph of a seed is the one it has always been)."""
     ks = np.resize(np.asarray(k, np.int64), n_captures) if np.ndim(k) else np.full(n_captures, int(k))
     kmax = int(ks.max())
     rng = np.random.Generator(np.random.PCG64(seed))
     n_tag = grid_x * grid_y
+    sizes = None if tag_size is None else np.broadcast_to(np.asarray(tag_size, np.float64), (n_tag,))
     gx, gy = np.meshgrid(np.arange(grid_x) * TAG_SPACING, np.arange(grid_y) * TAG_SPACING)
     tag_true = np.zeros((n_tag, 6))
     tag_true[:, 0] = gx.ravel()
@@ -225,7 +236,7 @@ def make_graph(n_captures, grid_x, grid_y, seed, k=8, noise_px=0.5,
     # tag corner world points (Nt,4,3)
     corners_w = np.empty((n_tag, 4, 3))
     for i, d in enumerate(ARUCO_DIRECTIONS):
-        c = np.tile([0.5 * ARUCO_SIZE * d[0], 0.5 * ARUCO_SIZE * d[1], 0.0], (n_tag, 1))
+        c = _tag_corner(d, n_tag, sizes)
         corners_w[:, i] = angle_axis_rotate(tag_true[:, 3:], c) + tag_true[:, :3]
     centres = tag_true[:, :3]
 
@@ -276,7 +287,8 @@ def make_graph(n_captures, grid_x, grid_y, seed, k=8, noise_px=0.5,
 
     obs_cap = np.repeat(np.arange(n_captures), ks).astype(np.int32)
     obs_tag = np.concatenate(obs_tags).astype(np.int32)
-    corners = project_corners(camera_true, cap_true[obs_cap], tag_true[obs_tag])
+    corners = project_corners(camera_true, cap_true[obs_cap], tag_true[obs_tag],
+                              None if sizes is None else sizes[obs_tag])
     corners += rng.normal(0.0, noise_px, corners.shape)
 
     cap0 = cap_true.copy()
@@ -317,16 +329,19 @@ class LocalizeBatch:
 
 
 def make_localize_batch(map_name="cfg3", n_query=4096, seed=3, k=8, noise_px=0.5,
-                        max_tilt=np.deg2rad(20.0)):
-    """cfg5: ``n_query`` captures of the ``map_name`` tag grid (truth), k tags each."""
+                        max_tilt=np.deg2rad(20.0), tag_size=None):
+    """cfg5: ``n_query`` captures of the ``map_name`` tag grid (truth), k tags each.
+    ``tag_size``: the map tags' sides, a scalar or one per tag (None: ARUCO_SIZE, the batch of a
+    seed as it has always been)."""
     _, grid_x, grid_y, _ = CONFIGS[map_name]
     g = config_graph(map_name)
     tag = g.tag_true.copy()
     n_tag = tag.shape[0]
+    sizes = None if tag_size is None else np.broadcast_to(np.asarray(tag_size, np.float64), (n_tag,))
     rng = np.random.Generator(np.random.PCG64(seed))
     corners_w = np.empty((n_tag, 4, 3))
     for i, d in enumerate(ARUCO_DIRECTIONS):
-        c = np.tile([0.5 * ARUCO_SIZE * d[0], 0.5 * ARUCO_SIZE * d[1], 0.0], (n_tag, 1))
+        c = _tag_corner(d, n_tag, sizes)
         corners_w[:, i] = angle_axis_rotate(tag[:, 3:], c) + tag[:, :3]
     centres = tag[:, :3]
     x_lo, x_hi = -0.1, (grid_x - 1) * TAG_SPACING + 0.1
@@ -353,7 +368,7 @@ def make_localize_batch(map_name="cfg3", n_query=4096, seed=3, k=8, noise_px=0.5
             filled += 1
     q_of = np.repeat(np.arange(n_query), k)
     obs_tag = obs.ravel().astype(np.int32)
-    corners = project_corners(g.camera_true, pose[q_of], tag[obs_tag])
+    corners = project_corners(g.camera_true, pose[q_of], tag[obs_tag], None if sizes is None else sizes[obs_tag])
     corners += rng.normal(0.0, noise_px, corners.shape)
     return LocalizeBatch(g.camera_true.copy(), tag, (np.arange(n_query + 1) * k).astype(np.int32),
                          obs_tag, np.ascontiguousarray(corners), pose, np.ones(n_tag, np.uint8))

@@ -95,6 +95,18 @@ enum {
  * > 0 for every kind but NONE (which ignores it). */
 enum { ARSLAM_LOSS_NONE = 0, ARSLAM_LOSS_HUBER = 1, ARSLAM_LOSS_SOFT_L_ONE = 2, ARSLAM_LOSS_CAUCHY = 3 };
 
+/* The side length of a tag, in metres: the functor's other constant
+ * (ArucoReprojectionError(rect) plus a size; the reference fixes it,
+ * aruco_size, ar_slam_util.hpp:319).  Corner i of a tag of side s is
+ * 0.5 s ARUCO_DIRECTIONS[i] in the tag's frame.  The tag sides are the only
+ * thing that gives the map its metric scale: the residual is unchanged when
+ * every translation and every side are scaled together.  A residual block
+ * carries the side of its tag, bound when the block is added, like its loss;
+ * any side that is not finite or not > 0 is ARSLAM_E_INVALID_ARG. */
+#define ARSLAM_DEFAULT_TAG_SIZE 0.0635
+/* a side the API accepts: finite and > 0 (false for NaN) */
+#define ARSLAM_TAG_SIZE_VALID(s) ((s) > 0.0 && (s) <= 1.7976931348623157e308)
+
 /* ceres::Solver::Options subset used by ArSlamSolver::optimize
  * (ar_slam_util.cpp:1003-1012); defaults from arslam_lm_options_init are
  * the reference's values (max_num_iterations = 50, DENSE_SCHUR) plus Ceres
@@ -239,6 +251,20 @@ int arslam_lm_get_loss(const arslam_lm *h, int *kind, double *a);
 int arslam_lm_add_residual_block_loss(arslam_lm *h, const double corners[8], double *camera,
                                       double *capture, double *tag, int kind, double a);
 
+/* The handle's default tag side, ARSLAM_DEFAULT_TAG_SIZE on creation: what
+ * arslam_lm_add_residual_block and _loss give the blocks added afterwards and
+ * what arslam_lm_load_soa and _loss give every tag.  Like arslam_lm_set_loss
+ * it drops a problem loaded by arslam_lm_load_soa, arslam_lm_reset keeps it,
+ * and a rejected call leaves the handle as it was. */
+int arslam_lm_set_tag_size(arslam_lm *h, double size);
+int arslam_lm_get_tag_size(const arslam_lm *h, double *size);
+
+/* arslam_lm_add_residual_block_loss with this block's own tag side (every
+ * block of one tag would pass the same; the side belongs to the block, as
+ * to a Ceres functor). */
+int arslam_lm_add_residual_block_sized(arslam_lm *h, const double corners[8], double *camera,
+                                       double *capture, double *tag, double size, int kind, double a);
+
 /* problem_.SetParameterBlockConstant(block) -- ar_slam_util.cpp:965, 972 */
 int arslam_lm_set_parameter_block_constant(arslam_lm *h, double *block);
 int arslam_lm_set_parameter_block_variable(arslam_lm *h, double *block);
@@ -262,6 +288,12 @@ int arslam_lm_solve_loaded(arslam_lm *h, arslam_lm_summary *summary);
  * passes the whole problem's arrays, as it does the problem. */
 int arslam_lm_load_soa_loss(arslam_lm *h, const arslam_soa_problem *p,
                             const unsigned char *obs_loss_kind, const double *obs_loss_a);
+
+/* arslam_lm_load_soa_loss with one side per tag (tag_size[n_tag], metres);
+ * NULL: the handle's default side for every tag.  A problem whose sides are
+ * all ARSLAM_DEFAULT_TAG_SIZE runs the same kernels as one loaded without. */
+int arslam_lm_load_soa_sized(arslam_lm *h, const arslam_soa_problem *p, const double *tag_size,
+                             const unsigned char *obs_loss_kind, const double *obs_loss_a);
 
 /* One-shot bulk solve (a handle of its own, so no loss: with one, create a
  * handle, arslam_lm_set_loss or arslam_lm_load_soa_loss, arslam_lm_solve_loaded). */

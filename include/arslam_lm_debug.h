@@ -19,6 +19,12 @@ extern "C" {
 int arslam_debug_residual_jacobian(int n, const double *cam, const double *cap, const double *tag,
                                    const double *corners, double *r, double *J);
 
+/* The same rows for tags of side size[n] (metres, finite and > 0), through
+ * the device functions the sized instances of k_linearize use.  At
+ * ARSLAM_DEFAULT_TAG_SIZE r and J are arslam_debug_residual_jacobian's bits. */
+int arslam_debug_residual_jacobian_sized(int n, const double *cam, const double *cap, const double *tag,
+                                         const double *corners, const double *size, double *r, double *J);
+
 /* The same rows after each observation's robust loss (arslam_lm.h
  * ARSLAM_LOSS_*; kind [n], a [n]), through the device functions k_linearize
  * uses: r [n*8] and J [n*8*15] times sqrt(rho'(s)), s = |r|^2 over the

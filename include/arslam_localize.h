@@ -152,6 +152,24 @@ int arslam_localizer_covariance_timed(arslam_localizer *h, double *cov, int *cov
 int arslam_localize_many_cov(const arslam_localize_batch *b, const arslam_lm_options *opt, int kind, double a,
                              arslam_localize_result *res, double *cov, int *cov_status);
 
+/* ---- tag sides ----
+ * A map tag carries its side length in metres (arslam_lm.h
+ * ARSLAM_DEFAULT_TAG_SIZE and the rule for a valid side): it gives the tag's
+ * constant world corners and initCapturePose's depth, local_z = focal * side /
+ * sqrt(max_dist_sq).  The handle's default side holds for every tag of a batch
+ * loaded afterwards without an array; the sides are bound at the load.  A batch
+ * whose sides are all the default runs the code without sizes. */
+int arslam_localizer_set_tag_size(arslam_localizer *h, double size);
+int arslam_localizer_get_tag_size(const arslam_localizer *h, double *size);
+/* arslam_localizer_load_loss with one side per map tag, tag_size [n_tag]
+ * (NULL: the handle's default for every tag). */
+int arslam_localizer_load_sized(arslam_localizer *h, const arslam_localize_batch *b, const double *tag_size,
+                                const unsigned char *obs_loss_kind, const double *obs_loss_a);
+/* arslam_localize_many_cov with one side per map tag (NULL: the default side). */
+int arslam_localize_many_sized(const arslam_localize_batch *b, const arslam_lm_options *opt,
+                               const double *tag_size, int kind, double a, arslam_localize_result *res,
+                               double *cov, int *cov_status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,30 @@ int arslam_slam_set_loss(arslam_slam *h, int kind, double a);
  * arslam_localize_many_loss.  Initially NONE.  An invalid kind or scale
  * returns ARSLAM_E_INVALID_ARG and leaves the loss unchanged. */
 int arslam_slam_set_localize_loss(arslam_slam *h, int kind, double a);
+/* Tag sides in metres (arslam_lm.h ARSLAM_DEFAULT_TAG_SIZE; the reference has
+ * one aruco_size for every tag, ar_slam_util.hpp:319).  The default holds for
+ * the tags created afterwards.  arslam_slam_set_aruco_size names a tag by its id
+ * string and may precede the tag's first detection; once the tag is initialised
+ * or a residual block of it has been added, its side is bound: ARSLAM_E_STATE.
+ * A side that is not finite or not > 0 is ARSLAM_E_INVALID_ARG and changes
+ * nothing.  The sides reach the residual blocks, calcInitValues / initArPose /
+ * initCapturePose and localizeMany's batch.  The map file keeps a tag's side
+ * under the optional key `size` of its entry, written only when it differs
+ * from the default. */
+int arslam_slam_set_default_aruco_size(arslam_slam *h, double size);
+int arslam_slam_set_aruco_size(arslam_slam *h, const char *id, double size);
+/* the side of tag a (index as in arslam_slam_aruco) */
+int arslam_slam_aruco_size(const arslam_slam *h, int a, double *size);
+/* A map entry without the `size` key is a tag of ARSLAM_DEFAULT_TAG_SIZE (that
+ * is when the key is left out), whatever the loading solver's default or by-id
+ * sides are. */
+/* Component entry, host only (no device): the mirror's initialisers alone.
+ * which = 0: initArPose(rect, camera, pose_in = the capture's inv_pose) -> the
+ * tag's pose; which = 1: initCapturePose(rect, camera, pose_in = the tag's
+ * pose) -> the capture's inv_pose; for a tag of side `size`, or, with size = 0,
+ * the call with the default argument (ARSLAM_DEFAULT_TAG_SIZE). */
+int arslam_slam_debug_init_pose(int which, const double rect[8], const double camera[3], const double pose_in[6],
+                                double size, double pose_out[6]);
 
 int arslam_slam_load_yaml(arslam_slam *h, const char *path);
 int arslam_slam_load_yaml_string(arslam_slam *h, const char *text);
