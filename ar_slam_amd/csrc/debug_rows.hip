@@ -15,8 +15,9 @@ namespace arslam {
 namespace {
 
 // one thread per (observation, row): residual and 15-column Jacobian row
-// (kSized: of a tag of side size[o]; else of the default side, size unused)
-template <bool kSized>
+// (kSized: of a tag of side size[o]; else of the default side, size unused;
+// kDist: under the radial camera model, l1 and l2 from cam, else the pinhole)
+template <bool kSized, bool kDist = false>
 __global__ void k_debug_rj(int n, const double *__restrict__ cam, const double *__restrict__ cap,
                            const double *__restrict__ tag, const double *__restrict__ corners,
                            const double *__restrict__ size, double *__restrict__ r, double *__restrict__ J) {
@@ -25,8 +26,8 @@ __global__ void k_debug_rj(int n, const double *__restrict__ cam, const double *
   const long o = e / 8;
   const int row = (int)(e % 8), corner = row >> 1, comp = row & 1;
   double j13[13];
-  r[e] = residual_jacobian_row(cam + 3 * o, cap + 6 * o, tag + 6 * o, kSized ? 0.5 * size[o] : kArucoHalf, corner,
-                               comp, corners[8 * o + row], j13);
+  r[e] = residual_jacobian_row<kDist>(cam + 3 * o, cap + 6 * o, tag + 6 * o, kSized ? 0.5 * size[o] : kArucoHalf,
+                                      corner, comp, corners[8 * o + row], j13);
   double *out = J + e * 15;
   out[0] = j13[0];
   out[1] = 0.0;
@@ -96,9 +97,9 @@ dim3 blocks_of_128(long threads) { return dim3((unsigned)((threads + 127) / 128)
 
 using arslam::DevBuf;
 
-// the body of the two row entries (size: null = every tag of the default side)
+// the body of the three row entries (size: null = every tag of the default side)
 static int debug_rows(int n, const double *cam, const double *cap, const double *tag, const double *corners,
-                      const double *size, double *r, double *J) {
+                      const double *size, double *r, double *J, int model = ARSLAM_CAMERA_PINHOLE) {
   if (n < 0 || (n && (!cam || !cap || !tag || !corners || !r || !J))) return ARSLAM_E_INVALID_ARG;
   for (int i = 0; size && i < n; ++i)
     if (!arslam::tag_size_valid(size[i])) return ARSLAM_E_INVALID_ARG;
@@ -109,7 +110,9 @@ static int debug_rows(int n, const double *cam, const double *cap, const double 
     d_out.alloc(128L * n);
     double *d_r = d_out.p, *d_J = d_r + 8L * n;
     const double *d_size = size ? d_in.p + 23L * n : nullptr;
-    auto kernel = size ? arslam::k_debug_rj<true> : arslam::k_debug_rj<false>;
+    auto kernel = model == ARSLAM_CAMERA_RADIAL
+                      ? (size ? arslam::k_debug_rj<true, true> : arslam::k_debug_rj<false, true>)
+                      : (size ? arslam::k_debug_rj<true> : arslam::k_debug_rj<false>);
     hipLaunchKernelGGL(kernel, arslam::blocks_of_128(8L * n), dim3(128), 0, 0, n, d_in.p, d_in.p + 3L * n,
                        d_in.p + 9L * n, d_in.p + 15L * n, d_size, d_r, d_J);
     HIP_CHECK(hipGetLastError());
@@ -130,6 +133,13 @@ extern "C" int arslam_debug_residual_jacobian_sized(int n, const double *cam, co
                                                     const double *size, double *r, double *J) {
   if (n > 0 && !size) return ARSLAM_E_INVALID_ARG;
   return debug_rows(n, cam, cap, tag, corners, size, r, J);
+}
+
+extern "C" int arslam_debug_residual_jacobian_model(int n, int model, const double *cam, const double *cap,
+                                                    const double *tag, const double *corners,
+                                                    const double *size, double *r, double *J) {
+  if (!ARSLAM_CAMERA_MODEL_VALID(model)) return ARSLAM_E_INVALID_ARG;
+  return debug_rows(n, cam, cap, tag, corners, size, r, J, model);
 }
 
 extern "C" int arslam_debug_residual_jacobian_loss(int n, const double *cam, const double *cap,

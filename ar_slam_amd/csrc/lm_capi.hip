@@ -138,6 +138,27 @@ int arslam_lm_get_tag_size(const arslam_lm *h, double *size) {
   return ARSLAM_OK;
 }
 
+int arslam_lm_set_camera_model(arslam_lm *h, int model) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return arslam::api_guarded([&] {
+    fail_if(!ARSLAM_CAMERA_MODEL_VALID(model), ARSLAM_E_INVALID_ARG,
+            "camera model: ARSLAM_CAMERA_PINHOLE or ARSLAM_CAMERA_RADIAL");
+    if (model == h->camera_model) return;
+    h->camera_model = model;
+    // (as arslam_lm_set_tag_size: the resident problem was linearized under the
+    // other model; so was its last solve, which a kept covariance describes)
+    h->loaded = false;
+    h->pk_dirty = true;
+    h->cov_invalidate();
+  });
+}
+
+int arslam_lm_camera_model(const arslam_lm *h, int *model) {
+  if (!h || !model) return ARSLAM_E_INVALID_ARG;
+  *model = h->camera_model;
+  return ARSLAM_OK;
+}
+
 int arslam_lm_add_residual_block(arslam_lm *h, const double corners[8], double *camera,
                                  double *capture, double *tag) {
   if (!h) return ARSLAM_E_INVALID_ARG;

@@ -220,6 +220,9 @@ struct arslam_lm {
   // same rules: bound when the block is added, never changed afterwards
   std::vector<double> pk_size;
   double def_tag_size = ARSLAM_DEFAULT_TAG_SIZE;   // arslam_lm_set_tag_size
+  // the camera model of the next load (arslam_lm_set_camera_model): the loaded
+  // problem's is DevProblem::camera_radial, and a change drops that problem
+  int camera_model = ARSLAM_CAMERA_PINHOLE;
   std::vector<double> soa_size;   // arslam_lm_load_soa*'s tag sides, per observation
   // the side of each observation's tag from the per-tag sides (null: the
   // handle's default for every tag); null when every side is the default

@@ -27,6 +27,15 @@ __device__ __forceinline__ double row_prod(const double *rr, int ca, int cb) {
   return rr[ca] * rr[cb];
 }
 
+// The least waves per SIMD k_linearize asks the register allocator to keep.
+// The pinhole instances: 4, and 2 for the sized chunked ones (the comments at
+// the kernel).  The radial ones hold d, d' and the two products of P on top of
+// the pinhole row: an instance that would spill at its pinhole twin's bound
+// asks for fewer waves instead of scratch (profiles/distortion/resource_usage.txt).
+constexpr int linearize_min_waves(bool chunked, bool sized, bool dist) {
+  return (chunked && (sized || dist)) ? 2 : 4;
+}
+
 // (4 waves per SIMD instead of the 3 its 143 VGPRs allow: a 28-byte spill,
 // 84 -> 71 us on cfg3; 5 waves spills 148 bytes and is slower)
 // (those figures are the compiler's of the time.  Today's gives, under the
@@ -39,8 +48,9 @@ __device__ __forceinline__ double row_prod(const double *rr, int ca, int cb) {
 // (kSized: the same attribute for the one-chunk instances, 96 / 98 VGPRs as
 // without; the chunked ones ask for 2 waves instead of 4 and so take the
 // registers the others spill for: no scratch, profiles/tag_size/resource_usage.txt)
-template <bool kChunked, bool kLoss, bool kSized>
-__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu((kChunked && kSized) ? 2 : 4, 8))) void k_linearize(DevProblem P, const double *__restrict__ x,
+// (kDist: linearize_min_waves)
+template <bool kChunked, bool kLoss, bool kSized, bool kDist>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(linearize_min_waves(kChunked, kSized, kDist), 8))) void k_linearize(DevProblem P, const double *__restrict__ x,
                                                      double *__restrict__ g,
                                                      double *__restrict__ colnorm,
                                                      double *__restrict__ obs_tg,
@@ -63,7 +73,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu((kChunked
   // around the projection cost the single-chunk code spills)
   auto chunk = [&](int q0) __attribute__((always_inline)) {
     const int kc = min(kObsChunk, k - q0), nr = 8 * kc;
-    fill_rows<kLoss, kSized>(P, x, nullptr, c, o0, 8 * q0, nr, nrows, rows, P.jrows, kLoss ? ocost : nullptr);
+    fill_rows<kLoss, kSized, kDist>(P, x, nullptr, c, o0, 8 * q0, nr, nrows, rows, P.jrows, kLoss ? ocost : nullptr);
     __syncthreads();
     // Every sum below is over rows of one product of two LDS columns (ca, cb),
     // picked per lane up front: one code path for the whole wave (a divergent
@@ -133,12 +143,12 @@ void launch_linearize(const DevProblem &P, const double *x, double *g, double *c
   if (P.nc == 0) return;
   const size_t lds = lds_rows(kObsChunk) + sizeof(double) * (kObsChunk + 16);
   // (the instance per loaded problem: kLoss iff it has robust losses, kSized
-  // iff some tag's side is not the default)
-  const bool loss = P.obs_loss_kind != nullptr, sized = P.obs_size != nullptr;
-  hipLaunchKernelGGL(ARSLAM_PICK_INSTANCE(k_linearize, false, loss, sized), dim3(P.nc), dim3(kWave), lds, s, P,
+  // iff some tag's side is not the default, kDist iff loaded under the radial model)
+  const bool loss = P.obs_loss_kind != nullptr, sized = P.obs_size != nullptr, dist = P.camera_radial != 0;
+  hipLaunchKernelGGL(ARSLAM_PICK_INSTANCE(k_linearize, false, loss, sized, dist), dim3(P.nc), dim3(kWave), lds, s, P,
                      x, g, colnorm, obs_tg, parts);
   if (P.n_chunk_caps)
-    hipLaunchKernelGGL(ARSLAM_PICK_INSTANCE(k_linearize, true, loss, sized), dim3(P.n_chunk_caps), dim3(kWave),
+    hipLaunchKernelGGL(ARSLAM_PICK_INSTANCE(k_linearize, true, loss, sized, dist), dim3(P.n_chunk_caps), dim3(kWave),
                        lds, s, P, x, g, colnorm, obs_tg, parts);
 }
 

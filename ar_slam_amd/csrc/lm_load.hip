@@ -397,6 +397,7 @@ void arslam_lm::upload_problem(const arslam::HostProblem &h, const arslam::Reduc
   P.obs_loss_kind = has_loss ? u_loss_kind : nullptr;
   P.obs_loss_a = has_loss ? u_loss_a : nullptr;
   P.obs_size = has_size ? u_obs_size : nullptr;
+  P.camera_radial = camera_model == ARSLAM_CAMERA_RADIAL ? 1 : 0;   // (the handle's model, bound at the load)
   P.tag_row = u_tag_row; P.row_slot = u_row_slot;
   P.tile_id = plan.tile_id; P.T = plan.T;
   P.tile_class = multi() && has_f ? plan.tile_class : nullptr;

@@ -87,6 +87,11 @@ enum PartIdx {
 
 struct DevProblem {
   int nc, nt, nb;
+  // 1: loaded under ARSLAM_CAMERA_RADIAL -- the host then launches the kDist
+  // instances of k_linearize, k_cost and k_backsub, which read l1 and l2 from
+  // camera slots 1 and 2; no kernel reads the flag.  (In the four bytes that
+  // padded nb up to n: no field's kernel-argument offset moves.)
+  int camera_radial = 0;
   long n;              // number of parameter slots 3 + 6nc + 6nt
   long nR;             // rows of the reduced system (tags + camera + alignment padding); row nR = rhs
   long N;              // padded matrix size (multiple of kTile, > nR)

@@ -70,7 +70,10 @@ __device__ __forceinline__ double robustify_row(int kind, double a, double &r, d
 // residuals it would be rho' s / 2).
 // kSized: the observation's tag side comes from DevProblem::obs_size; else
 // every tag has the default side, a constant of the code.
-template <bool kLoss = false, bool kSized = false>
+// kDist: the rows of the radial camera model, l1 and l2 from camera slots 1
+// and 2 of x (held: they never move, so a capture's rows are consistent over a
+// solve); else the pinhole's.
+template <bool kLoss = false, bool kSized = false, bool kDist = false>
 __device__ __forceinline__ void fill_rows(const DevProblem &P, const double *x, const double *scale, int c,
                           int o0, int row0, int nr, int nrows, double *rows, double *gout = nullptr,
                           double *ocost = nullptr) {
@@ -87,8 +90,8 @@ __device__ __forceinline__ void fill_rows(const DevProblem &P, const double *x, 
     // still takes the capture first; the Jacobian halves come back as e|f)
     const bool sw = group_swapped(P, c);
     const double half = kSized ? 0.5 * P.obs_size[obs] : kArucoHalf;
-    double r = residual_jacobian_row(cam, sw ? tag : cap, sw ? cap : tag, half, corner, comp,
-                                     P.corners[8L * obs + 2 * corner + comp], J);
+    double r = residual_jacobian_row<kDist>(cam, sw ? tag : cap, sw ? cap : tag, half, corner, comp,
+                                            P.corners[8L * obs + 2 * corner + comp], J);
     if (kLoss) {
       // (nr is a multiple of 8: an observation's 8 lanes are in the loop together)
       const double rho = robustify_row(P.obs_loss_kind[obs], P.obs_loss_a[obs], r, J);
@@ -143,9 +146,16 @@ __device__ __forceinline__ void fill_rows(const DevProblem &P, const double *x, 
 // instruction for instruction.  The two flags are independent: four instances
 // of each form, and a problem of default-size tags launches the two it always
 // has.  k_backsub's kSized, like its kLoss, reaches only the candidate cost.
-#define ARSLAM_PICK_INSTANCE(K, chunked, loss, sized)                                       \
-  ((sized) ? ((loss) ? K<chunked, true, true> : K<chunked, false, true>)                    \
-           : ((loss) ? K<chunked, true, false> : K<chunked, false, false>))
+// kDist = true: the problem was loaded under ARSLAM_CAMERA_RADIAL
+// (DevProblem::camera_radial); false is the pinhole code, instruction for
+// instruction.  Independent of the other two: eight instances of each form,
+// and a pinhole problem launches one of the four it always could.
+#define ARSLAM_PICK_INSTANCE_D(K, chunked, loss, sized, dist)                               \
+  ((sized) ? ((loss) ? K<chunked, true, true, dist> : K<chunked, false, true, dist>)        \
+           : ((loss) ? K<chunked, true, false, dist> : K<chunked, false, false, dist>))
+#define ARSLAM_PICK_INSTANCE(K, chunked, loss, sized, dist)                                 \
+  ((dist) ? ARSLAM_PICK_INSTANCE_D(K, chunked, loss, sized, true)                           \
+          : ARSLAM_PICK_INSTANCE_D(K, chunked, loss, sized, false))
 template <bool kChunked>
 __device__ __forceinline__ int chunk_capture(const DevProblem &P, int &k) {
   const int c = kChunked ? P.chunk_caps[blockIdx.x] : (int)blockIdx.x;

@@ -121,7 +121,7 @@ __device__ void inv6(const double *U, double *Ui) {
 // k_backsub just formed, held in LDS); camera and tags from x.
 // (kChunked: a capture of more than kObsChunk observations, its rows 64 at a
 // time; else at most one wave of rows)
-template <bool kChunked, bool kLoss, bool kSized>
+template <bool kChunked, bool kLoss, bool kSized, bool kDist>
 __device__ __forceinline__ void capture_cost(const DevProblem &P, const double *__restrict__ x, const double *cap,
                                              int c, double *__restrict__ parts) {
   __shared__ double sq[kWave];
@@ -143,8 +143,11 @@ __device__ __forceinline__ void capture_cost(const DevProblem &P, const double *
       const double obsv = P.corners[8L * obs + 2 * corner + comp];
       const bool sw = group_swapped(P, c);   // tag e-block: the capture is the f-block
       const double half = kSized ? 0.5 * P.obs_size[obs] : kArucoHalf;
-      const double r = residual_row(sw ? at : ac, sw ? tag : cap, sw ? ac : at, sw ? cap : tag, cam[0], half,
-                                    corner, comp, obsv, nullptr, nullptr);
+      // (kDist: the radial model's l1, l2 from camera slots 1, 2)
+      const double r = kDist ? residual_row<true>(sw ? at : ac, sw ? tag : cap, sw ? ac : at, sw ? cap : tag, cam[0],
+                                                  half, corner, comp, obsv, nullptr, nullptr, cam[1], cam[2])
+                             : residual_row(sw ? at : ac, sw ? tag : cap, sw ? ac : at, sw ? cap : tag, cam[0], half,
+                                            corner, comp, obsv, nullptr, nullptr);
       if (!isfinite(r)) bad = 1.0;
       r2 = r * r;
     }
@@ -179,18 +182,18 @@ __device__ __forceinline__ void capture_cost(const DevProblem &P, const double *
   }
 }
 
-template <bool kChunked, bool kLoss, bool kSized>
+template <bool kChunked, bool kLoss, bool kSized, bool kDist>
 __global__ __launch_bounds__(kWave) void k_cost(DevProblem P, const double *__restrict__ x,
                                                 double *__restrict__ parts) {
   int k;
   const int c = chunk_capture<kChunked>(P, k);
   if (c < 0) return;
-  capture_cost<kChunked, kLoss, kSized>(P, x, x + slot_cap(P, c), c, parts);
+  capture_cost<kChunked, kLoss, kSized, kDist>(P, x, x + slot_cap(P, c), c, parts);
 }
 
 // Back substitution for capture c, candidate update of its slots and its
 // share of the model cost change.
-template <bool kChunked, bool kLoss, bool kSized>
+template <bool kChunked, bool kLoss, bool kSized, bool kDist>
 __global__ __launch_bounds__(kWave) void k_backsub(DevProblem P, const double *__restrict__ x,
                                                    const double *__restrict__ scale,
                                                    const double *__restrict__ diag, double radius,
@@ -338,7 +341,7 @@ __global__ __launch_bounds__(kWave) void k_backsub(DevProblem P, const double *_
   // by k_update_f, launched before this kernel
   if (with_cost) {
     __syncthreads();
-    capture_cost<kChunked, kLoss, kSized>(P, xc, capc, c, parts);
+    capture_cost<kChunked, kLoss, kSized, kDist>(P, xc, capc, c, parts);
   }
 }
 
@@ -395,11 +398,11 @@ void launch_backsub(const DevProblem &P, const double *x, const double *scale, c
                     bool reuse_ui, bool with_cost) {
   if (P.nc == 0) return;
   const size_t lds = lds_rows(kObsChunk) + sizeof(double) * (8L * kObsChunk + 36 + 36 + 16);
-  const bool loss = P.obs_loss_kind != nullptr, sized = P.obs_size != nullptr;
-  hipLaunchKernelGGL(ARSLAM_PICK_INSTANCE(k_backsub, false, loss, sized), dim3(P.nc), dim3(kWave), lds, s, P, x,
+  const bool loss = P.obs_loss_kind != nullptr, sized = P.obs_size != nullptr, dist = P.camera_radial != 0;
+  hipLaunchKernelGGL(ARSLAM_PICK_INSTANCE(k_backsub, false, loss, sized, dist), dim3(P.nc), dim3(kWave), lds, s, P, x,
                      scale, diag, radius, yF, xc, parts, reuse_ui ? 1 : 0, with_cost ? 1 : 0);
   if (P.n_chunk_caps)
-    hipLaunchKernelGGL(ARSLAM_PICK_INSTANCE(k_backsub, true, loss, sized), dim3(P.n_chunk_caps), dim3(kWave), lds, s,
+    hipLaunchKernelGGL(ARSLAM_PICK_INSTANCE(k_backsub, true, loss, sized, dist), dim3(P.n_chunk_caps), dim3(kWave), lds, s,
                        P, x, scale, diag, radius, yF, xc, parts, reuse_ui ? 1 : 0, with_cost ? 1 : 0);
 }
 
@@ -412,10 +415,10 @@ void launch_update_f(const DevProblem &P, const double *x, const double *scale, 
 
 void launch_cost(const DevProblem &P, const double *x, double *parts, hipStream_t s) {
   if (P.nc == 0) return;
-  const bool loss = P.obs_loss_kind != nullptr, sized = P.obs_size != nullptr;
-  hipLaunchKernelGGL(ARSLAM_PICK_INSTANCE(k_cost, false, loss, sized), dim3(P.nc), dim3(kWave), 0, s, P, x, parts);
+  const bool loss = P.obs_loss_kind != nullptr, sized = P.obs_size != nullptr, dist = P.camera_radial != 0;
+  hipLaunchKernelGGL(ARSLAM_PICK_INSTANCE(k_cost, false, loss, sized, dist), dim3(P.nc), dim3(kWave), 0, s, P, x, parts);
   if (P.n_chunk_caps)
-    hipLaunchKernelGGL(ARSLAM_PICK_INSTANCE(k_cost, true, loss, sized), dim3(P.n_chunk_caps), dim3(kWave), 0, s, P, x,
+    hipLaunchKernelGGL(ARSLAM_PICK_INSTANCE(k_cost, true, loss, sized, dist), dim3(P.n_chunk_caps), dim3(kWave), 0, s, P, x,
                        parts);
 }
 

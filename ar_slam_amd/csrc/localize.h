@@ -23,6 +23,10 @@ struct LocParams {
   const double *aw;            // [nt*4][4] world points of the (constant) tags' corners
   int init_from_map, max_k;
   int max_iters, max_invalid, jacobi;
+  // 1: ARSLAM_CAMERA_RADIAL -- the launchers pick the kDist instances, which
+  // read l1, l2 from cam[1], cam[2]; no kernel reads the flag.  (In the four
+  // bytes that padded jacobi up to ftol: no field's kernel-argument offset moves.)
+  int dist;
   double ftol, gtol, ptol, r0, rmax, rmin, min_rel, dmin, dmax;
   // per-observation robust loss (ARSLAM_LOSS_*, scale), read by the kLoss
   // instances only; null when no observation of the batch has one

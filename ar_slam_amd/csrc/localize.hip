@@ -146,14 +146,31 @@ __device__ __forceinline__ void cap_frame(const double *x, CapFrame &F, bool jac
 // Residual row of a corner whose world point is aw: b = aw + t_c, p = R(w_c) b
 // (:152-155), r = f p_xy / p_z - obs (:157-162, :198-211); with J6 != null
 // also its 6 capture-block Jacobian entries [t_c, w_c].
-__device__ __forceinline__ double loc_row(const CapFrame &F, const double *x, const double *aw, double f,
+// kDist: under the radial camera model, cam = [f, l1, l2] (projection.h
+// radial_factor and residual_jacobian_row's P); else the pinhole, cam[0] alone.
+template <bool kDist = false>
+__device__ __forceinline__ double loc_row(const CapFrame &F, const double *x, const double *aw, const double *cam,
                                           int comp, double obs, double *J6) {
+  const double f = cam[0];
   double b[3] = {aw[0] + x[0], aw[1] + x[1], aw[2] + x[2]}, p[3];
   aa_rotate(F.ac, b, p);
-  const double r = f * ((comp == 0 ? p[0] : p[1]) / p[2]) - obs;
+  double r = f * ((comp == 0 ? p[0] : p[1]) / p[2]) - obs;
+  if (kDist && !J6)
+    r = f * (radial_factor(p[0] / p[2], p[1] / p[2], cam[1], cam[2], nullptr) * ((comp == 0 ? p[0] : p[1]) / p[2])) - obs;
   if (J6) {
     const double xx = p[0] / p[2], yy = p[1] / p[2], fz = f / p[2];
-    const double P[3] = {comp == 0 ? fz : 0.0, comp == 0 ? 0.0 : fz, comp == 0 ? -fz * xx : -fz * yy};
+    double P[3] = {comp == 0 ? fz : 0.0, comp == 0 ? 0.0 : fz, comp == 0 ? -fz * xx : -fz * yy};
+    if (kDist) {
+      // (P[2] from P[0] and P[1], not from A and B: two fewer values live
+      // across the products, which k_localize<2, 32> would spill for)
+      double d1;
+      const double d = radial_factor(xx, yy, cam[1], cam[2], &d1);
+      const double w = comp == 0 ? xx : yy, c2 = 2.0 * d1 * w;
+      P[0] = fz * ((comp == 0 ? d : 0.0) + c2 * xx);
+      P[1] = fz * ((comp == 0 ? 0.0 : d) + c2 * yy);
+      P[2] = -(P[0] * xx + P[1] * yy);
+      r = f * (d * w) - obs;
+    }
     double PM[3], v[3];
     vecmat3(P, F.M, PM);
     J6[0] = PM[0]; J6[1] = PM[1]; J6[2] = PM[2];
@@ -253,7 +270,7 @@ __device__ __forceinline__ double robust_weight(const LossKA *lka, int R, double
 // kLoss: the rows are the corrected ones, sqrt(rho') (J | r) per observation,
 // and the cost is sum rho / 2; lka = the query's staged losses.  kLoss = false
 // is the code without a loss (lka unused).
-template <int NCH, int LPQ, bool kLoss>
+template <int NCH, int LPQ, bool kLoss, bool kDist>
 __device__ bool evaluate_jacobian(const LocParams &p, const double *rc, const LossKA *lka, int nrow,
                                   const double *x, int lane, double &cost, double *red,
                                   const AngleAxis *ac_pre = nullptr) {
@@ -275,7 +292,7 @@ __device__ bool evaluate_jacobian(const LocParams &p, const double *rc, const Lo
     if (R < nrow) {
       const double *rr = rc + 4 * R;   // (the row's corner world point and observation, LDS)
       double j6[6];
-      double r = loc_row(F, x, rr, p.cam[0], R & 1, rr[3], j6);
+      double r = loc_row<kDist>(F, x, rr, p.cam, R & 1, rr[3], j6);
       bad = bad || !isfinite(r);   // (the uncorrected residual)
       if (kLoss) {
         double w;
@@ -303,7 +320,7 @@ __device__ bool evaluate_jacobian(const LocParams &p, const double *rc, const Lo
   return wave_max<LPQ>(bad ? 1.0 : 0.0) == 0.0;
 }
 
-template <int NCH, int LPQ, bool kLoss>
+template <int NCH, int LPQ, bool kLoss, bool kDist>
 __device__ double evaluate_cost(const LocParams &p, const double *rc, const LossKA *lka, int nrow, const double *x,
                                 int lane, bool &finite, CapFrame &F) {
   cap_frame(x, F, false);
@@ -314,7 +331,7 @@ __device__ double evaluate_cost(const LocParams &p, const double *rc, const Loss
     const int R = lane + LPQ * ch;
     if (R < nrow) {
       const double *rr = rc + 4 * R;
-      const double r = loc_row(F, x, rr, p.cam[0], R & 1, rr[3], nullptr);
+      const double r = loc_row<kDist>(F, x, rr, p.cam, R & 1, rr[3], nullptr);
       bad = bad || !isfinite(r);
       if (kLoss) {
         double w;
@@ -336,7 +353,9 @@ __device__ double evaluate_cost(const LocParams &p, const double *rc, const Loss
 // per workgroup, so a finished wave's slot is reused at once.
 // kLoss = true: some observation of the batch has a robust loss (p.lk, p.la);
 // a batch without one runs the kLoss = false instances, the code without a loss.
-template <int NCH, int LPQ, bool kLoss>
+// kDist = true: the handle's camera model is ARSLAM_CAMERA_RADIAL (l1, l2 from
+// p.cam); false is the pinhole code, instruction for instruction.
+template <int NCH, int LPQ, bool kLoss, bool kDist>
 __global__ __launch_bounds__(64, 2) void k_localize(LocParams p) {
   const int lane = threadIdx.x & (LPQ - 1);
   const int q = blockIdx.x * (64 / LPQ) + threadIdx.x / LPQ;
@@ -404,7 +423,7 @@ __global__ __launch_bounds__(64, 2) void k_localize(LocParams p) {
   // J'r and J'J of the last linearization, in LDS (column norms squared = diag(H): HD(j))
   const double *g = red + sums_off<LPQ>() + 1, *H = red + sums_off<LPQ>() + 7;
   double x_norm = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3] + x[4] * x[4] + x[5] * x[5]);
-  bool finite = evaluate_jacobian<NCH, LPQ, kLoss>(p, rc, lka, nrow, x, lane, cost, red);
+  bool finite = evaluate_jacobian<NCH, LPQ, kLoss, kDist>(p, rc, lka, nrow, x, lane, cost, red);
   res.initial_cost = cost;
   if (!finite) {
     res.status = ARSLAM_FAILURE;
@@ -542,7 +561,7 @@ __global__ __launch_bounds__(64, 2) void k_localize(LocParams p) {
       }
       bool cfin = true;
       CapFrame Fc;
-      double cand = evaluate_cost<NCH, LPQ, kLoss>(p, rc, lka, nrow, xc, lane, cfin, Fc);
+      double cand = evaluate_cost<NCH, LPQ, kLoss, kDist>(p, rc, lka, nrow, xc, lane, cfin, Fc);
       if (!cfin) cand = DBL_MAX;
       // ParameterToleranceReached / FunctionToleranceReached
       if (sqrt(sq) <= p.ptol * (x_norm + p.ptol)) { res.status = ARSLAM_CONVERGENCE; res.rule = ARSLAM_RULE_PARAMETER; break; }
@@ -553,7 +572,7 @@ __global__ __launch_bounds__(64, 2) void k_localize(LocParams p) {
 #pragma unroll
         for (int j = 0; j < 6; ++j) x[j] = xc[j];
         x_norm = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3] + x[4] * x[4] + x[5] * x[5]);
-        (void)evaluate_jacobian<NCH, LPQ, kLoss>(p, rc, lka, nrow, x, lane, cost, red, &Fc.ac);
+        (void)evaluate_jacobian<NCH, LPQ, kLoss, kDist>(p, rc, lka, nrow, x, lane, cost, red, &Fc.ac);
         gmax = 0.0;
 #pragma unroll
         for (int j = 0; j < 6; ++j) gmax = fmax(gmax, fabs(g[j]));
@@ -582,6 +601,8 @@ __global__ __launch_bounds__(64, 2) void k_localize(LocParams p) {
 // its rows carry (1 without a loss: lk == null); -1 for both on the
 // observations of a skipped query.  One 64-thread block per query, thread j
 // its observation j (k <= ARSLAM_LOC_MAX_OBS = 64).  Runs only on request.
+// (kDist: an instance of its own, not a runtime flag)
+template <bool kDist>
 __global__ __launch_bounds__(64) void k_localize_terms(int nq, const double *__restrict__ cam,
                                                        const int *__restrict__ qs, const int *__restrict__ ot,
                                                        const double *__restrict__ corners,
@@ -605,8 +626,8 @@ __global__ __launch_bounds__(64) void k_localize_terms(int nq, const double *__r
     cap_frame(x, F, false);
     s = 0.0;
     for (int row = 0; row < 8; ++row) {
-      const double r = loc_row(F, x, aw + 4L * (4 * ot[o] + (row >> 1)), cam[0], row & 1, corners[8L * o + row],
-                               nullptr);
+      const double r = loc_row<kDist>(F, x, aw + 4L * (4 * ot[o] + (row >> 1)), cam, row & 1, corners[8L * o + row],
+                                      nullptr);
       s += r * r;
     }
     double rho;
@@ -635,7 +656,7 @@ constexpr double kCovMinPivot = 1e-14;   // a squared pivot of the equilibrated 
 // before the evaluation, as in k_localize.  The staging loop is k_localize's,
 // repeated: moved into a function shared by both kernels it changed
 // k_localize's instruction schedule, and the solve's ISA is held fixed here.
-template <int NCH, int LPQ, bool kLoss>
+template <int NCH, int LPQ, bool kLoss, bool kDist>
 __global__ __launch_bounds__(64, 2) void k_localize_cov(LocCovParams cp) {
   const LocParams &p = cp.p;
   const int lane = threadIdx.x & (LPQ - 1);
@@ -675,7 +696,7 @@ __global__ __launch_bounds__(64, 2) void k_localize_cov(LocCovParams cp) {
     double x[6], cost;
 #pragma unroll
     for (int j = 0; j < 6; ++j) x[j] = p.pose_out[6L * q + j];
-    have = evaluate_jacobian<NCH, LPQ, kLoss>(p, rc, lka, nrow, x, lane, cost, red) && isfinite(cost);
+    have = evaluate_jacobian<NCH, LPQ, kLoss, kDist>(p, rc, lka, nrow, x, lane, cost, red) && isfinite(cost);
   }
   if (!have) {
     cst = ARSLAM_COV_UNAVAILABLE;
@@ -774,47 +795,42 @@ __global__ __launch_bounds__(64, 2) void k_localize_cov(LocCovParams cp) {
 
 }  // namespace
 
+// the instance of K that p.max_k, "any loss" (p.lk) and the camera model (p.dist)
+// choose, and its grid: two queries per wave at k <= 8 (cfg5)
+#define ARSLAM_LOC_INSTANCE(K, NCH, LPQ) \
+  (p.dist ? (p.lk ? K<NCH, LPQ, true, true> : K<NCH, LPQ, false, true>) \
+          : (p.lk ? K<NCH, LPQ, true, false> : K<NCH, LPQ, false, false>))
+
 void launch_localize(const LocParams &p, hipStream_t s) {
   if (p.nq == 0) return;
   if (p.nt > 0)   // the map's corner points (inside the timed region: one launch per batch solve)
     hipLaunchKernelGGL(k_tag_corners, dim3((unsigned)((4 * p.nt + 255) / 256)), dim3(256), 0, s, p.nt, p.tag,
                        p.tsize, const_cast<double *>(p.aw));
   const dim3 block(64);
-  if (!p.lk) {   // no observation has a robust loss: the code without one
-    if (p.max_k <= 8)   // (cfg5: k = 8) two queries per wave
-      hipLaunchKernelGGL((k_localize<2, 32, false>), dim3((unsigned)((p.nq + 1) / 2)), block, 0, s, p);
-    else if (p.max_k <= 16) hipLaunchKernelGGL((k_localize<2, 64, false>), dim3((unsigned)p.nq), block, 0, s, p);
-    else hipLaunchKernelGGL((k_localize<kMaxChunks, 64, false>), dim3((unsigned)p.nq), block, 0, s, p);
-    return;
-  }
-  if (p.max_k <= 8) hipLaunchKernelGGL((k_localize<2, 32, true>), dim3((unsigned)((p.nq + 1) / 2)), block, 0, s, p);
-  else if (p.max_k <= 16) hipLaunchKernelGGL((k_localize<2, 64, true>), dim3((unsigned)p.nq), block, 0, s, p);
-  else hipLaunchKernelGGL((k_localize<kMaxChunks, 64, true>), dim3((unsigned)p.nq), block, 0, s, p);
+  // (a batch without a robust loss runs the code without one; a pinhole handle the pinhole code)
+  if (p.max_k <= 8)   // (cfg5: k = 8) two queries per wave
+    hipLaunchKernelGGL(ARSLAM_LOC_INSTANCE(k_localize, 2, 32), dim3((unsigned)((p.nq + 1) / 2)), block, 0, s, p);
+  else if (p.max_k <= 16) hipLaunchKernelGGL(ARSLAM_LOC_INSTANCE(k_localize, 2, 64), dim3((unsigned)p.nq), block, 0, s, p);
+  else hipLaunchKernelGGL(ARSLAM_LOC_INSTANCE(k_localize, kMaxChunks, 64), dim3((unsigned)p.nq), block, 0, s, p);
 }
 
-// k_localize's geometry and instance choice (by max_k and by "any loss"), on
-// the poses, results, losses and aw the last solve left on the device
+// k_localize's geometry and instance choice, on the poses, results, losses and
+// aw the last solve left on the device
 void launch_localize_cov(const LocCovParams &cp, hipStream_t s) {
   const LocParams &p = cp.p;
   if (p.nq == 0) return;
   const dim3 block(64);
-  if (!p.lk) {
-    if (p.max_k <= 8)
-      hipLaunchKernelGGL((k_localize_cov<2, 32, false>), dim3((unsigned)((p.nq + 1) / 2)), block, 0, s, cp);
-    else if (p.max_k <= 16) hipLaunchKernelGGL((k_localize_cov<2, 64, false>), dim3((unsigned)p.nq), block, 0, s, cp);
-    else hipLaunchKernelGGL((k_localize_cov<kMaxChunks, 64, false>), dim3((unsigned)p.nq), block, 0, s, cp);
-    return;
-  }
   if (p.max_k <= 8)
-    hipLaunchKernelGGL((k_localize_cov<2, 32, true>), dim3((unsigned)((p.nq + 1) / 2)), block, 0, s, cp);
-  else if (p.max_k <= 16) hipLaunchKernelGGL((k_localize_cov<2, 64, true>), dim3((unsigned)p.nq), block, 0, s, cp);
-  else hipLaunchKernelGGL((k_localize_cov<kMaxChunks, 64, true>), dim3((unsigned)p.nq), block, 0, s, cp);
+    hipLaunchKernelGGL(ARSLAM_LOC_INSTANCE(k_localize_cov, 2, 32), dim3((unsigned)((p.nq + 1) / 2)), block, 0, s, cp);
+  else if (p.max_k <= 16)
+    hipLaunchKernelGGL(ARSLAM_LOC_INSTANCE(k_localize_cov, 2, 64), dim3((unsigned)p.nq), block, 0, s, cp);
+  else hipLaunchKernelGGL(ARSLAM_LOC_INSTANCE(k_localize_cov, kMaxChunks, 64), dim3((unsigned)p.nq), block, 0, s, cp);
 }
 
 void launch_localize_terms(const LocParams &p, double *sq_out, double *w_out, hipStream_t s) {
   if (p.nq == 0) return;
-  hipLaunchKernelGGL(k_localize_terms, dim3((unsigned)p.nq), dim3(64), 0, s, p.nq, p.cam, p.qs, p.ot, p.corners, p.aw,
-                     p.pose_out, p.res, p.lk, p.la, sq_out, w_out);
+  hipLaunchKernelGGL((p.dist ? k_localize_terms<true> : k_localize_terms<false>), dim3((unsigned)p.nq), dim3(64), 0, s,
+                     p.nq, p.cam, p.qs, p.ot, p.corners, p.aw, p.pose_out, p.res, p.lk, p.la, sq_out, w_out);
 }
 
 }  // namespace arslam

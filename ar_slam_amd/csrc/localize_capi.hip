@@ -24,6 +24,10 @@ struct arslam_localizer {
   double def_tag_size = ARSLAM_DEFAULT_TAG_SIZE;
   bool has_size = false;
   arslam::DevBuf<double> tsize;
+  // The camera model (set_camera_model): which instances solve(),
+  // observation_terms() and covariance() launch; l1 and l2 are the loaded
+  // batch's camera[1], camera[2].
+  int camera_model = ARSLAM_CAMERA_PINHOLE;
   arslam::DevBuf<arslam_localize_result> res;
   // Robust losses.  The default (set_loss) holds for every observation of a
   // batch loaded without arrays; a batch's own arrays (load_loss) override it.
@@ -174,6 +178,7 @@ struct arslam_localizer {
     p.res = res.p; p.init_from_map = init_from_map; p.max_k = max_k;
     p.aw = aw.p; p.nt = nt;
     p.tsize = has_size ? tsize.p : nullptr;
+    p.dist = camera_model == ARSLAM_CAMERA_RADIAL ? 1 : 0;
     p.max_iters = opt.max_num_iterations; p.max_invalid = opt.max_num_consecutive_invalid_steps;
     p.jacobi = opt.jacobi_scaling;
     p.ftol = opt.function_tolerance; p.gtol = opt.gradient_tolerance; p.ptol = opt.parameter_tolerance;
@@ -291,6 +296,23 @@ int arslam_localizer_set_tag_size(arslam_localizer *h, double size) {
 int arslam_localizer_get_tag_size(const arslam_localizer *h, double *size) {
   if (!h || !size) return ARSLAM_E_INVALID_ARG;
   *size = h->def_tag_size;
+  return ARSLAM_OK;
+}
+
+int arslam_localizer_set_camera_model(arslam_localizer *h, int model) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return arslam::api_guarded([&] {
+    arslam::api_check(ARSLAM_CAMERA_MODEL_VALID(model), ARSLAM_E_INVALID_ARG,
+                      "camera model: ARSLAM_CAMERA_PINHOLE or ARSLAM_CAMERA_RADIAL");
+    if (model == h->camera_model) return;
+    h->camera_model = model;
+    h->solved = false;   // (the resident poses and results are the other model's)
+  });
+}
+
+int arslam_localizer_camera_model(const arslam_localizer *h, int *model) {
+  if (!h || !model) return ARSLAM_E_INVALID_ARG;
+  *model = h->camera_model;
   return ARSLAM_OK;
 }
 

@@ -137,12 +137,27 @@ __device__ __forceinline__ void vecmat3(const double *v, const double *M, double
   o[2] = v[0] * M[2] + v[1] * M[5] + v[2] * M[8];
 }
 
+// The radial camera model (ARSLAM_CAMERA_RADIAL, the TODO of projectCorner,
+// ar_slam_util.cpp:164-171) at the normalized point (x, y): the factor
+// d = 1 + r2 (l1 + l2 r2) and its derivative by r2, d' = l1 + 2 l2 r2,
+// r2 = x^2 + y^2.  l1 and l2 are constants of a solve.  No guard for a
+// polynomial that folds back: the calibration must be monotone over the field
+// of view (d + 2 r2 d' > 0), as p_z > 0 is the caller's.
+__device__ __forceinline__ double radial_factor(double x, double y, double l1, double l2, double *d1) {
+  const double r2 = x * x + y * y;
+  if (d1) *d1 = l1 + 2.0 * l2 * r2;
+  return 1.0 + r2 * (l1 + l2 * r2);
+}
+
 // Residual of one row (corner, comp) of ArucoReprojectionError, for a tag of
-// side 2 half.
+// side 2 half.  kDist: under the radial model, (u, v) = f d (x, y) with l1, l2;
+// else the pinhole, l1 and l2 unused -- the code it has always been.
+template <bool kDist = false>
 __device__ __forceinline__ double residual_row(const AngleAxis &ac, const double *cap,
                                                const AngleAxis &at, const double *tag, double f,
                                                double half, int corner, int comp, double obs,
-                                               double *a_out, double *p_out) {
+                                               double *a_out, double *p_out, double l1 = 0.0,
+                                               double l2 = 0.0) {
   const double cpt[3] = {half * corner_dx(corner), half * corner_dy(corner), 0.0};
   double a[3], p[3];
   aa_rotate(at, cpt, a);
@@ -152,10 +167,19 @@ __device__ __forceinline__ double residual_row(const AngleAxis &ac, const double
   const double xy = (comp == 0 ? p[0] : p[1]) / p[2];
   if (a_out) { a_out[0] = a[0]; a_out[1] = a[1]; a_out[2] = a[2]; }
   if (p_out) { p_out[0] = p[0]; p_out[1] = p[1]; p_out[2] = p[2]; }
+  if (kDist) {
+    const double x = p[0] / p[2], y = p[1] / p[2];
+    return f * (radial_factor(x, y, l1, l2, nullptr) * xy) - obs;
+  }
   return f * xy - obs;
 }
 
 // Residual row and its 13 non-zero Jacobian entries: [f, t_c(3), w_c(3), t_t(3), w_t(3)].
+// kDist: l1 = cam[1] and l2 = cam[2] are live and held (their two columns stay
+// zero); only the f column and the 1x3 row P differ from the pinhole's:
+// P = (f / p_z) [A, B, -(A x + B y)], (A, B) = (d + 2 x^2 d', 2 x y d') for a
+// u row and (2 x y d', d + 2 y^2 d') for a v row.
+template <bool kDist = false>
 __device__ __forceinline__ double residual_jacobian_row(const double *cam, const double *cap,
                                                         const double *tag, double half, int corner,
                                                         int comp, double obs, double J[13]) {
@@ -163,15 +187,25 @@ __device__ __forceinline__ double residual_jacobian_row(const double *cam, const
   const AngleAxis at = aa_prepare(tag + 3);
   double a[3], p[3];
   const double f = cam[0];
-  const double r = residual_row(ac, cap, at, tag, f, half, corner, comp, obs, a, p);
+  const double r = kDist ? residual_row<true>(ac, cap, at, tag, f, half, corner, comp, obs, a, p, cam[1], cam[2])
+                         : residual_row(ac, cap, at, tag, f, half, corner, comp, obs, a, p);
   const double x = p[0] / p[2], y = p[1] / p[2];
   const double fz = f / p[2];
-  const double P[3] = {comp == 0 ? fz : 0.0, comp == 0 ? 0.0 : fz, comp == 0 ? -fz * x : -fz * y};
+  double P[3] = {comp == 0 ? fz : 0.0, comp == 0 ? 0.0 : fz, comp == 0 ? -fz * x : -fz * y};
+  double dfac = 1.0;
+  if (kDist) {
+    double d1;
+    dfac = radial_factor(x, y, cam[1], cam[2], &d1);
+    const double w = comp == 0 ? x : y, c2 = 2.0 * d1 * w;   // d(d w)/d(x, y) = d e_w + 2 d' w (x, y)
+    P[0] = fz * ((comp == 0 ? dfac : 0.0) + c2 * x);   // (f / p_z) A
+    P[1] = fz * ((comp == 0 ? 0.0 : dfac) + c2 * y);   // (f / p_z) B
+    P[2] = -(P[0] * x + P[1] * y);
+  }
   double Mc[9];
   aa_matrix(ac, Mc);
   double PM[3];
   vecmat3(P, Mc, PM);
-  J[0] = comp == 0 ? x : y;
+  J[0] = kDist ? dfac * (comp == 0 ? x : y) : (comp == 0 ? x : y);
   J[1] = PM[0]; J[2] = PM[1]; J[3] = PM[2];
   J[7] = PM[0]; J[8] = PM[1]; J[9] = PM[2];
   // d/dw_c = -((P Mc) x a) Jr_c   (small branch: -(P x a))

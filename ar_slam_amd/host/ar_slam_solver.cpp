@@ -262,6 +262,15 @@ void ArSlamSolver::loadYamlString(const std::string &text) {   // :304-384
     camera_.size = ImageSize{(int)cam["width"].as_long(), (int)cam["height"].as_long()};
     const yaml::Node &cp = cam["params"];
     for (size_t i = 0; i < cp.size(); ++i) camera_.params.at(i) = cp[i].as_double();
+    // (optional: saveYaml leaves it out for a pinhole map, so a missing key means pinhole)
+    int model = ARSLAM_CAMERA_PINHOLE;
+    if (const yaml::Node *m = cam.find("model")) {
+      const std::string name = m->as_string();
+      if (name == "radial") model = ARSLAM_CAMERA_RADIAL;
+      else if (name != "pinhole") throw std::runtime_error("camera: model must be pinhole or radial, not " + name);
+    }
+    if (setCameraModel(model) != ARSLAM_OK)
+      throw std::runtime_error("camera: the map's model differs from the one the added residual blocks were made with");
   }
 }
 
@@ -306,6 +315,7 @@ void ArSlamSolver::saveYaml(std::ostream &y) const {   // :387-465 (yaml-cpp emi
   flow(camera_.params.data(), 3);
   y << "\n";
   if (camera_.size) y << "  width: " << camera_.size->width << "\n  height: " << camera_.size->height << "\n";
+  if (camera_model_ == ARSLAM_CAMERA_RADIAL) y << "  model: radial\n";   // (a pinhole map stays as it has always been)
   y << std::endl;
 }
 
@@ -480,6 +490,7 @@ void ArSlamSolver::localizeMany(unsigned first_loc_cap_idx) {   // :888-901, eac
   // evaluate there on the first request (nothing more runs when nobody asks)
   check(arslam_localizer_create(&localizer_, &options_));
   check(arslam_localizer_set_loss(localizer_, localize_loss_kind_, localize_loss_a_));
+  check(arslam_localizer_set_camera_model(localizer_, camera_model_));
   check(arslam_localizer_load_sized(localizer_, &b, sizes.data(), nullptr, nullptr));
   check(arslam_localizer_solve(localizer_, pose.data(), res.data(), nullptr));
   loc_first_ = first_loc_cap_idx;
@@ -544,6 +555,25 @@ int ArSlamSolver::setLocalizeLoss(int kind, double a) {
   localize_loss_kind_ = kind;
   localize_loss_a_ = a;
   return ARSLAM_OK;
+}
+
+int ArSlamSolver::setCameraModel(int model) {
+  if (!ARSLAM_CAMERA_MODEL_VALID(model)) return ARSLAM_E_INVALID_ARG;
+  if (model == camera_model_) return ARSLAM_OK;
+  for (const Block &b : blocks_)
+    if (b.added) return ARSLAM_E_STATE;   // its residual block was made under the model the solver has
+  const int rc = arslam_lm_set_camera_model(problem_, model);
+  if (rc != ARSLAM_OK) return rc;
+  camera_model_ = model;
+  dropLocalizer();   // (the last localizeMany's batch was solved under the other model)
+  return ARSLAM_OK;
+}
+
+void ArSlamSolver::cameraDistortion(double d[5]) const {
+  const bool radial = camera_model_ == ARSLAM_CAMERA_RADIAL;
+  d[0] = radial ? camera_.params[1] : 0.0;
+  d[1] = radial ? camera_.params[2] : 0.0;
+  d[2] = d[3] = d[4] = 0.0;
 }
 
 int ArSlamSolver::setDefaultArucoSize(double size) {

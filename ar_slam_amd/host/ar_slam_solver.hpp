@@ -188,6 +188,17 @@ class ArSlamSolver {
   // the initialisers and localizeMany's batch.
   int setDefaultArucoSize(double size);
   int setArucoSize(const std::string &id, double size);
+  // The camera model (ARSLAM_CAMERA_*, PINHOLE initially) of the mapper handle
+  // and of localizeMany's localizer; under RADIAL camera l1, l2 are a known
+  // calibration the solves hold.  Once a residual block has been added the
+  // model is bound: ARSLAM_E_STATE.  An unknown value: ARSLAM_E_INVALID_ARG.
+  // The initialisers stay the pinhole's (they only seed the LM).  The map file
+  // keeps it as `model: radial` inside `camera:`, written only under RADIAL.
+  int setCameraModel(int model);
+  int cameraModel() const { return camera_model_; }
+  // the plumb_bob vector beside getCameraInfo's K and P: [l1, l2, 0, 0, 0]
+  // under RADIAL, zeros under PINHOLE
+  void cameraDistortion(double d[5]) const;
   // The 6x6 covariance (arslam_localizer_covariance: row-major, [t_c, w_c],
   // unit-variance residuals) and its ARSLAM_COV_* status of a capture the last
   // localizeMany localized, at the pose it was given -- ceres::Covariance on
@@ -228,6 +239,7 @@ class ArSlamSolver {
   int localize_loss_kind_ = ARSLAM_LOSS_NONE;   // setLocalizeLoss
   double localize_loss_a_ = 0.0;
   double default_aruco_size_ = ARSLAM_DEFAULT_TAG_SIZE;
+  int camera_model_ = ARSLAM_CAMERA_PINHOLE;   // setCameraModel
   std::unordered_map<std::string, double> aruco_size_by_id_;   // setArucoSize before the tag exists
   // the last localizeMany: its resident batch, the captures it covered
   // (loc_first_ + q is query q) and their covariances once asked for

@@ -108,6 +108,27 @@ int arslam_slam_debug_init_pose(int which, const double rect[8], const double ca
   return ARSLAM_OK;
 }
 
+int arslam_slam_set_camera_model(arslam_slam *h, int model) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  int rc = ARSLAM_OK;
+  const int g = slam_guarded([&] { rc = h->s.setCameraModel(model); });
+  if (!g && rc == ARSLAM_E_STATE)
+    arslam::set_last_error("set_camera_model: residual blocks have been added; the camera model is bound");
+  return g ? g : rc;
+}
+
+int arslam_slam_camera_model(const arslam_slam *h, int *model) {
+  if (!h || !model) return ARSLAM_E_INVALID_ARG;
+  *model = h->s.cameraModel();
+  return ARSLAM_OK;
+}
+
+int arslam_slam_camera_distortion(const arslam_slam *h, double d[5]) {
+  if (!h || !d) return ARSLAM_E_INVALID_ARG;
+  h->s.cameraDistortion(d);
+  return ARSLAM_OK;
+}
+
 int arslam_slam_load_yaml(arslam_slam *h, const char *path) {
   if (!h || !path) return ARSLAM_E_INVALID_ARG;
   return slam_guarded([&] { h->s.loadYaml(path); });

@@ -51,6 +51,9 @@ EXPORTS = ["arslam_lm_options_init", "arslam_lm_create", "arslam_lm_destroy",
            "arslam_localizer_set_tag_size", "arslam_localizer_get_tag_size", "arslam_localizer_load_sized",
            "arslam_localize_many_sized",
            "arslam_slam_debug_init_pose", "arslam_slam_set_default_aruco_size", "arslam_slam_set_aruco_size", "arslam_slam_aruco_size",
+           "arslam_lm_set_camera_model", "arslam_lm_camera_model", "arslam_debug_residual_jacobian_model",
+           "arslam_localizer_set_camera_model", "arslam_localizer_camera_model",
+           "arslam_slam_set_camera_model", "arslam_slam_camera_model", "arslam_slam_camera_distortion",
            "arslam_debug_residual_jacobian", "arslam_debug_dense_llt", "arslam_debug_dense_llt_ex",
            "arslam_debug_tile_llt", "arslam_debug_tile_plan",
            "arslam_debug_angle_axis_rotate", "arslam_debug_selinv", "arslam_lm_debug_force_indefinite",
@@ -87,6 +90,9 @@ SETUP_LOAD, SETUP_VALUES, SETUP_APPEND = 0, 1, 2   # arslam_lm_summary.setup_kin
 # ceres::LossFunction of a residual block (arslam_lm.h ARSLAM_LOSS_*); a loss is (kind, a)
 LOSS_NONE, LOSS_HUBER, LOSS_SOFT_L_ONE, LOSS_CAUCHY = 0, 1, 2, 3
 DEFAULT_TAG_SIZE = 0.0635   # arslam_lm.h ARSLAM_DEFAULT_TAG_SIZE: the side of a tag, metres
+# the camera model of a handle (arslam_lm.h ARSLAM_CAMERA_*): the pinhole, or the radial model
+# (u, v) = f d (x, y), d = 1 + r2 (l1 + l2 r2), with camera l1, l2 as a known calibration
+CAMERA_PINHOLE, CAMERA_RADIAL = 0, 1
 _ip = C.POINTER(C.c_int)
 _up = C.POINTER(C.c_ubyte)
 
@@ -279,6 +285,15 @@ def lib():
         L.arslam_slam_set_aruco_size.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
         L.arslam_slam_aruco_size.argtypes = [C.c_void_p, C.c_int, _dp]
         L.arslam_slam_debug_init_pose.argtypes = [C.c_int, _dp, _dp, _dp, C.c_double, _dp]
+    if hasattr(L, "arslam_lm_set_camera_model"):   # (absent from older variant builds under A/B)
+        L.arslam_lm_set_camera_model.argtypes = [C.c_void_p, C.c_int]
+        L.arslam_lm_camera_model.argtypes = [C.c_void_p, _ip]
+        L.arslam_debug_residual_jacobian_model.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
+        L.arslam_localizer_set_camera_model.argtypes = [C.c_void_p, C.c_int]
+        L.arslam_localizer_camera_model.argtypes = [C.c_void_p, _ip]
+        L.arslam_slam_set_camera_model.argtypes = [C.c_void_p, C.c_int]
+        L.arslam_slam_camera_model.argtypes = [C.c_void_p, _ip]
+        L.arslam_slam_camera_distortion.argtypes = [C.c_void_p, _dp]
     L.arslam_lm_set_parameter_block_constant.argtypes = [C.c_void_p, _dp]
     L.arslam_lm_set_parameter_block_variable.argtypes = [C.c_void_p, _dp]
     L.arslam_lm_solve.argtypes = [C.c_void_p, C.POINTER(Summary)]
@@ -449,6 +464,17 @@ class _Handle:
         _check(lib().arslam_lm_get_tag_size(self._h, C.byref(s)))
         return s.value
 
+    def set_camera_model(self, model):
+        """The handle's camera model, CAMERA_PINHOLE (on creation) or CAMERA_RADIAL: under RADIAL
+        the camera block's l1, l2 are a known calibration the solve holds.  Drops a loaded problem
+        and a kept covariance; the next load or solve uses it."""
+        _check(lib().arslam_lm_set_camera_model(self._h, int(model)))
+
+    def camera_model(self):
+        m = C.c_int(0)
+        _check(lib().arslam_lm_camera_model(self._h, C.byref(m)))
+        return m.value
+
     def set_iteration_callback(self, fn):
         """ceres::IterationCallback: fn(iteration dict) -> SOLVER_CONTINUE / SOLVER_ABORT /
         SOLVER_TERMINATE_SUCCESSFULLY (None = continue); fn=None removes it."""
@@ -509,11 +535,14 @@ class ResidentProblem(_Handle):
 
     def __init__(self, camera, cap, tag, obs_cap, obs_tag, corners, camera_const=False,
                  cap_const=None, tag_const=None, comm=None, force_multirank=False, loss=None, obs_loss=None,
-                 tag_size=None, **opts):
+                 tag_size=None, camera_model=None, **opts):
         """loss = (kind, a): the robust loss of every observation (the handle's default loss);
         obs_loss = (kinds[n_obs], a[n_obs]): one loss per observation, in observation order;
-        tag_size = [n_tag] the tags' sides in metres (a scalar: every tag's); None: DEFAULT_TAG_SIZE."""
+        tag_size = [n_tag] the tags' sides in metres (a scalar: every tag's); None: DEFAULT_TAG_SIZE;
+        camera_model = CAMERA_PINHOLE / CAMERA_RADIAL (None: the handle's, PINHOLE)."""
         super().__init__(**opts)
+        if camera_model is not None:
+            self.set_camera_model(camera_model)
         if force_multirank:
             self.debug_force_multirank(True)
         if comm is not None:
@@ -740,6 +769,25 @@ def debug_residual_jacobian_sized(cam, cap, tag, corners, size):
                                                       tag.ctypes.data_as(_dp), corners.ctypes.data_as(_dp),
                                                       size.ctypes.data_as(_dp), r.ctypes.data_as(_dp),
                                                       J.ctypes.data_as(_dp)))
+    return r, J
+
+
+def debug_residual_jacobian_model(cam, cap, tag, corners, model, size=None):
+    """debug_residual_jacobian under a camera model (CAMERA_*; cam rows = f, l1, l2), for tags of
+    side size[n] (a scalar: every tag's; None: the default side)."""
+    cap = _f64(cap, (-1, 6))
+    n = cap.shape[0]
+    cam = _f64(np.broadcast_to(np.asarray(cam, np.float64), (n, 3)))
+    tag = _f64(tag, (-1, 6))
+    corners = _f64(corners, (-1, 8))
+    if size is not None:
+        size = _f64(np.broadcast_to(np.asarray(size, np.float64), (n,)))
+    r = np.zeros((n, 8))
+    J = np.zeros((n, 8, 15))
+    _check(lib().arslam_debug_residual_jacobian_model(n, int(model), cam.ctypes.data_as(_dp), cap.ctypes.data_as(_dp),
+                                                      tag.ctypes.data_as(_dp), corners.ctypes.data_as(_dp),
+                                                      size.ctypes.data_as(_dp) if size is not None else None,
+                                                      r.ctypes.data_as(_dp), J.ctypes.data_as(_dp)))
     return r, J
 
 
@@ -1159,13 +1207,16 @@ def localize_many(batch, init_from_map=True, pose=None, loss=None, covariance=Fa
 class Localizer:
     """Resident batched localizer: load a batch once, solve it many times."""
 
-    def __init__(self, batch, init_from_map=True, pose=None, loss=None, obs_loss=None, tag_size=None, **opts):
+    def __init__(self, batch, init_from_map=True, pose=None, loss=None, obs_loss=None, tag_size=None,
+                 camera_model=None, **opts):
         """loss = (kind, a): the robust loss of every observation (the handle's default loss);
         obs_loss = (kinds[n_obs], a[n_obs]): one loss per observation of this batch, in observation
         order, overriding the default; tag_size: the map tags' sides in metres, [n_tag] or a scalar
-        (None: DEFAULT_TAG_SIZE)."""
+        (None: DEFAULT_TAG_SIZE); camera_model = CAMERA_PINHOLE / CAMERA_RADIAL (None: PINHOLE)."""
         self._h = C.c_void_p()
         _check(lib().arslam_localizer_create(C.byref(self._h), C.byref(make_options(**opts))))
+        if camera_model is not None:
+            self.set_camera_model(camera_model)
         self.A = _LocArrays(batch, init_from_map, pose)
         self.n_query = self.A.s.n_query
         self.n_obs = self.A.s.n_obs
@@ -1187,6 +1238,16 @@ class Localizer:
         else:
             _check(lib().arslam_localizer_load_loss(self._h, C.byref(self.A.s), kinds.ctypes.data_as(_up),
                                                     scales.ctypes.data_as(_dp)))
+
+    def set_camera_model(self, model):
+        """CAMERA_PINHOLE or CAMERA_RADIAL (l1, l2 = the batch's camera[1], camera[2]): the model
+        of solve(), observation_terms() and covariance(); the batch stays loaded."""
+        _check(lib().arslam_localizer_set_camera_model(self._h, int(model)))
+
+    def camera_model(self):
+        m = C.c_int(0)
+        _check(lib().arslam_localizer_camera_model(self._h, C.byref(m)))
+        return m.value
 
     def set_tag_size(self, size):
         """The default side (metres) of every map tag of a batch loaded afterwards."""
@@ -1304,6 +1365,22 @@ class SlamSolver:
         s = C.c_double(0.0)
         _check(lib().arslam_slam_aruco_size(self._h, int(a), C.byref(s)))
         return s.value
+
+    def set_camera_model(self, model):
+        """CAMERA_PINHOLE or CAMERA_RADIAL for the mapper and the localizer the solver keeps.
+        STATE once residual blocks have been added."""
+        _check(lib().arslam_slam_set_camera_model(self._h, int(model)))
+
+    def camera_model(self):
+        m = C.c_int(0)
+        _check(lib().arslam_slam_camera_model(self._h, C.byref(m)))
+        return m.value
+
+    def camera_distortion(self):
+        """The plumb_bob vector beside camera_info: [l1, l2, 0, 0, 0] under RADIAL, else zeros."""
+        d = np.zeros(5)
+        _check(lib().arslam_slam_camera_distortion(self._h, d.ctypes.data_as(_dp)))
+        return d
 
     def load_yaml(self, path):
         _check(lib().arslam_slam_load_yaml(self._h, str(path).encode()))

@@ -155,8 +155,15 @@ def _tag_corner(d, n, size=None):
     return np.stack([half * d[0], half * d[1], np.zeros(n)], 1)
 
 
-def project_corners(camera, cap, tag, size=None):
-    """Project all 4 corners of each (cap row, tag row) pair -> (N,8); size: each row's tag side."""
+def _radial(x, y, distortion):
+    """The radial model's factor d = 1 + r2 (l1 + l2 r2) at the normalized point (x, y)."""
+    r2 = x * x + y * y
+    return 1.0 + r2 * (distortion[0] + distortion[1] * r2)
+
+
+def project_corners(camera, cap, tag, size=None, distortion=None):
+    """Project all 4 corners of each (cap row, tag row) pair -> (N,8); size: each row's tag side;
+    distortion = (l1, l2): through the radial camera model, (u, v) = f d (x, y) (None: the pinhole)."""
     n = cap.shape[0]
     out = np.empty((n, 8))
     for i, d in enumerate(ARUCO_DIRECTIONS):
@@ -166,6 +173,8 @@ def project_corners(camera, cap, tag, size=None):
         p = angle_axis_rotate(cap[:, 3:], b)
         out[:, 2 * i] = camera[0] * (p[:, 0] / p[:, 2])
         out[:, 2 * i + 1] = camera[0] * (p[:, 1] / p[:, 2])
+        if distortion is not None:
+            out[:, 2 * i:2 * i + 2] *= _radial(p[:, 0] / p[:, 2], p[:, 1] / p[:, 2], distortion)[:, None]
     return out
 
 
@@ -194,13 +203,17 @@ def _sample_cameras(rng, n, x_lo, x_hi, y_lo, y_hi, max_tilt, roll_range=0.5 * n
     return R_cw, pos
 
 
-def _visible_nearest(R_cw, pos, corners_w, centres, cand, k):
-    """k nearest (3-D) fully visible tags among ``cand``; None if < k visible."""
+def _visible_nearest(R_cw, pos, corners_w, centres, cand, k, distortion=None):
+    """k nearest (3-D) fully visible tags among ``cand``; None if < k visible.
+    distortion = (l1, l2): the image points go through the radial model."""
     p = np.einsum("ij,tcj->tci", R_cw, corners_w[cand] - pos)
     z = p[..., 2]
     with np.errstate(divide="ignore", invalid="ignore"):
         u = F_TRUE * p[..., 0] / z
         v = F_TRUE * p[..., 1] / z
+        if distortion is not None:
+            d = _radial(p[..., 0] / z, p[..., 1] / z, distortion)
+            u, v = u * d, v * d
     vis = ((z > 0.1) & (np.abs(u) < 0.5 * IMG_W - 1.0) & (np.abs(v) < 0.5 * IMG_H - 1.0)).all(1)
     if np.count_nonzero(vis) < k:
         return None
@@ -212,11 +225,16 @@ def _visible_nearest(R_cw, pos, corners_w, centres, cand, k):
 
 def make_graph(n_captures, grid_x, grid_y, seed, k=8, noise_px=0.5,
                init_trans_sigma=0.02, init_rot_sigma=0.02, f_init=1.1 * F_TRUE,
-               max_tilt=np.deg2rad(20.0), name="", full_rotation=False, depth=(0.6, 1.2), tag_size=None):
+               max_tilt=np.deg2rad(20.0), name="", full_rotation=False, depth=(0.6, 1.2), tag_size=None,
+               distortion=None):
     """Generate a connected capture/tag graph with exactly ``k`` tags per capture (``k`` an int,
     or a sequence: capture c sees ``k[c % len(k)]`` tags; cameras ``depth`` metres from the plane).
     ``tag_size``: the tags' sides in metres, a scalar or one per tag (None: ARUCO_SIZE, and the
-    graph of a seed is the one it has always been)."""
+    graph of a seed is the one it has always been).
+    ``distortion`` = (l1, l2): the detections of a lens with that radial distortion -- truth
+    corners and the visibility test both go through the model, the noise is added after it, and
+    the true and the initial camera carry l1, l2 (a known calibration).  None: the pinhole, and
+    the graph of a seed is the one it has always been."""
     ks = np.resize(np.asarray(k, np.int64), n_captures) if np.ndim(k) else np.full(n_captures, int(k))
     kmax = int(ks.max())
     rng = np.random.Generator(np.random.PCG64(seed))
@@ -231,7 +249,8 @@ def make_graph(n_captures, grid_x, grid_y, seed, k=8, noise_px=0.5,
     # :52-95) the tag z axis points away from the cameras, i.e. along world +z
     rot_range = np.pi if full_rotation else 0.5 * np.pi
     tag_true[:, 5] = rng.uniform(-rot_range, rot_range, n_tag)
-    camera_true = np.array([F_TRUE, 0.0, 0.0])
+    l1, l2 = (0.0, 0.0) if distortion is None else (float(distortion[0]), float(distortion[1]))
+    camera_true = np.array([F_TRUE, l1, l2])
 
     # tag corner world points (Nt,4,3)
     corners_w = np.empty((n_tag, 4, 3))
@@ -258,9 +277,9 @@ def make_graph(n_captures, grid_x, grid_y, seed, k=8, noise_px=0.5,
         for i in range(m):
             if filled >= n_captures:
                 break
-            sel = _visible_nearest(R_cw[i], pos[i], corners_w, centres, cand[i], ks[filled])
+            sel = _visible_nearest(R_cw[i], pos[i], corners_w, centres, cand[i], ks[filled], distortion)
             if sel is None and n_cand < n_tag:
-                sel = _visible_nearest(R_cw[i], pos[i], corners_w, centres, np.arange(n_tag), ks[filled])
+                sel = _visible_nearest(R_cw[i], pos[i], corners_w, centres, np.arange(n_tag), ks[filled], distortion)
             if sel is None:
                 continue
             obs_tags[filled] = sel
@@ -288,7 +307,7 @@ def make_graph(n_captures, grid_x, grid_y, seed, k=8, noise_px=0.5,
     obs_cap = np.repeat(np.arange(n_captures), ks).astype(np.int32)
     obs_tag = np.concatenate(obs_tags).astype(np.int32)
     corners = project_corners(camera_true, cap_true[obs_cap], tag_true[obs_tag],
-                              None if sizes is None else sizes[obs_tag])
+                              None if sizes is None else sizes[obs_tag], distortion)
     corners += rng.normal(0.0, noise_px, corners.shape)
 
     cap0 = cap_true.copy()
@@ -297,7 +316,7 @@ def make_graph(n_captures, grid_x, grid_y, seed, k=8, noise_px=0.5,
     tag0 = tag_true.copy()
     tag0[:, :3] += rng.normal(0.0, init_trans_sigma, (n_tag, 3))
     tag0[:, 3:] += rng.normal(0.0, init_rot_sigma, (n_tag, 3))
-    camera0 = np.array([f_init, 0.0, 0.0])
+    camera0 = np.array([f_init, l1, l2])
     return Graph(camera0, cap0, tag0, obs_cap, obs_tag, np.ascontiguousarray(corners),
                  camera_true, cap_true, tag_true, name)
 
@@ -329,10 +348,12 @@ class LocalizeBatch:
 
 
 def make_localize_batch(map_name="cfg3", n_query=4096, seed=3, k=8, noise_px=0.5,
-                        max_tilt=np.deg2rad(20.0), tag_size=None):
+                        max_tilt=np.deg2rad(20.0), tag_size=None, distortion=None):
     """cfg5: ``n_query`` captures of the ``map_name`` tag grid (truth), k tags each.
     ``tag_size``: the map tags' sides, a scalar or one per tag (None: ARUCO_SIZE, the batch of a
-    seed as it has always been)."""
+    seed as it has always been).  ``distortion`` = (l1, l2): detections through the radial camera
+    model (visibility too, noise after it); the batch's camera is then [f, l1, l2].  None: the
+    pinhole, the batch of a seed as it has always been."""
     _, grid_x, grid_y, _ = CONFIGS[map_name]
     g = config_graph(map_name)
     tag = g.tag_true.copy()
@@ -359,7 +380,7 @@ def make_localize_batch(map_name="cfg3", n_query=4096, seed=3, k=8, noise_px=0.5
         for i in range(m):
             if filled >= n_query:
                 break
-            sel = _visible_nearest(R_cw[i], pos[i], corners_w, centres, cand[i], k)
+            sel = _visible_nearest(R_cw[i], pos[i], corners_w, centres, cand[i], k, distortion)
             if sel is None:
                 continue
             obs[filled] = sel
@@ -368,9 +389,12 @@ def make_localize_batch(map_name="cfg3", n_query=4096, seed=3, k=8, noise_px=0.5
             filled += 1
     q_of = np.repeat(np.arange(n_query), k)
     obs_tag = obs.ravel().astype(np.int32)
-    corners = project_corners(g.camera_true, pose[q_of], tag[obs_tag], None if sizes is None else sizes[obs_tag])
+    camera = g.camera_true.copy()
+    if distortion is not None:
+        camera[1:] = distortion
+    corners = project_corners(camera, pose[q_of], tag[obs_tag], None if sizes is None else sizes[obs_tag], distortion)
     corners += rng.normal(0.0, noise_px, corners.shape)
-    return LocalizeBatch(g.camera_true.copy(), tag, (np.arange(n_query + 1) * k).astype(np.int32),
+    return LocalizeBatch(camera, tag, (np.arange(n_query + 1) * k).astype(np.int32),
                          obs_tag, np.ascontiguousarray(corners), pose, np.ones(n_tag, np.uint8))
 
 

@@ -14,8 +14,9 @@
  *
  * Each entry point below replaces one of those calls with the same argument
  * meaning: parameter blocks are caller-owned double arrays keyed by their
- * address (camera[3] = f,l1,l2; capture[6] = inv_pose t,w; tag[6] = pose
- * t,w), observations are copied (as the functor copies its ArucoRect,
+ * address (camera[3] = f,l1,l2 -- f is estimated; l1 and l2 are held
+ * constant and used under ARSLAM_CAMERA_RADIAL only; capture[6] = inv_pose
+ * t,w; tag[6] = pose t,w), observations are copied (as the functor copies its ArucoRect,
  * ar_slam_util.cpp:194-196), and results are written back into the caller's
  * arrays when the solve ends (Ceres' default; update_state_every_iteration
  * writes them after every improving step).
@@ -106,6 +107,22 @@ enum { ARSLAM_LOSS_NONE = 0, ARSLAM_LOSS_HUBER = 1, ARSLAM_LOSS_SOFT_L_ONE = 2, 
 #define ARSLAM_DEFAULT_TAG_SIZE 0.0635
 /* a side the API accepts: finite and > 0 (false for NaN) */
 #define ARSLAM_TAG_SIZE_VALID(s) ((s) > 0.0 && (s) <= 1.7976931348623157e308)
+
+/* The camera model of a handle's residual blocks.  PINHOLE, the default, is
+ * the reference's projectCorner as it stands: u = f x, v = f y with
+ * x = p_x / p_z, y = p_y / p_z, and camera[1], camera[2] ignored.  RADIAL is
+ * the TODO it carries (ar_slam_util.cpp:164-171), with l1 = camera[1] and
+ * l2 = camera[2] as a known calibration:
+ *   r2 = x^2 + y^2,  d = 1 + r2 (l1 + l2 r2),  (u, v) = f d (x, y).
+ * l1 and l2 are held constant by the solve (in Ceres terms a
+ * SubsetParameterization of the camera block on {1, 2}): their Jacobian
+ * columns are zero and the values the caller passes come back unchanged; f is
+ * still estimated unless the camera block is constant.  No guard is added for
+ * a polynomial that folds back: the calibration must be monotone over the
+ * field of view, d + 2 r2 d' > 0 with d' = l1 + 2 l2 r2, as every observed
+ * point must have p_z > 0.  Any other value is ARSLAM_E_INVALID_ARG. */
+enum { ARSLAM_CAMERA_PINHOLE = 0, ARSLAM_CAMERA_RADIAL = 1 };
+#define ARSLAM_CAMERA_MODEL_VALID(m) ((m) == ARSLAM_CAMERA_PINHOLE || (m) == ARSLAM_CAMERA_RADIAL)
 
 /* ceres::Solver::Options subset used by ArSlamSolver::optimize
  * (ar_slam_util.cpp:1003-1012); defaults from arslam_lm_options_init are
@@ -259,6 +276,17 @@ int arslam_lm_add_residual_block_loss(arslam_lm *h, const double corners[8], dou
 int arslam_lm_set_tag_size(arslam_lm *h, double size);
 int arslam_lm_get_tag_size(const arslam_lm *h, double *size);
 
+/* The handle's camera model (ARSLAM_CAMERA_*), PINHOLE on creation: a property
+ * of the handle, like the default tag side.  Changing it drops a problem
+ * loaded by arslam_lm_load_soa* and any cached covariance; the next load (or
+ * the next arslam_lm_solve of the pointer-keyed blocks) uses it, on every
+ * path: appends, the three eliminations, losses, sized tags, several ranks,
+ * arslam_lm_covariance and arslam_lm_covariance_pairs.  arslam_lm_reset keeps
+ * it.  An unknown value returns ARSLAM_E_INVALID_ARG and leaves the handle as
+ * it was.  A PINHOLE problem launches the kernels it always launched. */
+int arslam_lm_set_camera_model(arslam_lm *h, int model);
+int arslam_lm_camera_model(const arslam_lm *h, int *model);
+
 /* arslam_lm_add_residual_block_loss with this block's own tag side (every
  * block of one tag would pass the same; the side belongs to the block, as
  * to a Ceres functor). */
@@ -345,7 +373,7 @@ int arslam_lm_set_iteration_callback(arslam_lm *h, arslam_iteration_callback fn,
  * (Covariance::Options::apply_loss_function = true).  At the parameters the
  * last solve returned, H = J~'J~ over every active residual block and every
  * free parameter -- the focal f if the camera is free and used (never l1, l2:
- * their Jacobian columns are zero), 6 per free capture, 6 per free tag -- the
+ * they are held constant, used under ARSLAM_CAMERA_RADIAL), 6 per free capture, 6 per free tag -- the
  * Jacobian rows corrected by sqrt(rho'(s)) exactly as the solve corrects them,
  * no LM diagonal.  C = H^-1, for unit-variance residuals: with pixel noise
  * sigma, multiply by sigma^2.  Only the marginals are returned: the 6x6
@@ -429,7 +457,8 @@ int arslam_lm_covariance_block(arslam_lm *h, const double *block, double *cov, i
  * columns of b, row-major, 6x6 for two poses ([t, w] each).  With the camera in
  * a pair the stride stays 36: for the focal against a pose, in either order,
  * the first 6 values are cov(f, pose) and the other 30 are 0; camera against
- * camera has var(f) at [0] and 0 elsewhere (l1 / l2 are never free).
+ * camera has var(f) at [0] and 0 elsewhere (l1 / l2 are held constant under
+ * either camera model).
  *
  * status [n_pairs] (nullable): ARSLAM_COV_UNAVAILABLE, and -1 in the 36
  * values, if either block is constant or unused; ARSLAM_COV_RANK_DEFICIENT,
@@ -473,7 +502,7 @@ int arslam_lm_covariance_pairs(arslam_lm *h, const arslam_lm_cov_pair *pairs, in
  * through arslam_lm_add_residual_block, in Ceres' shapes, row-major: 6x6 for
  * two poses; 3x6 for the camera against a pose (row 0 = cov(f, pose)), 6x3 for
  * a pose against the camera (column 0), 3x3 for the camera against itself
- * (var(f) at [0]); the l1 / l2 rows and columns are 0, as in
+ * (var(f) at [0]); the l1 / l2 rows and columns are 0 (held constant), as in
  * arslam_lm_covariance_block.  Computes on every call.  *status (nullable) =
  * ARSLAM_COV_*; -1 in every value unless OK.  ARSLAM_E_INVALID_ARG for a
  * pointer that is not a block of the problem. */

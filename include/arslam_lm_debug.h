@@ -25,6 +25,15 @@ int arslam_debug_residual_jacobian(int n, const double *cam, const double *cap, 
 int arslam_debug_residual_jacobian_sized(int n, const double *cam, const double *cap, const double *tag,
                                          const double *corners, const double *size, double *r, double *J);
 
+/* The same rows under a camera model (arslam_lm.h ARSLAM_CAMERA_*; cam [n*3]
+ * = f, l1, l2 per observation), through the device functions the kDist
+ * instances of k_linearize use; size [n] as above, or NULL for the default
+ * side.  Columns 1 and 2 of J (l1, l2) are 0 under either model.  Under
+ * ARSLAM_CAMERA_PINHOLE r and J are arslam_debug_residual_jacobian's (or
+ * _sized's) bits. */
+int arslam_debug_residual_jacobian_model(int n, int model, const double *cam, const double *cap, const double *tag,
+                                         const double *corners, const double *size, double *r, double *J);
+
 /* The same rows after each observation's robust loss (arslam_lm.h
  * ARSLAM_LOSS_*; kind [n], a [n]), through the device functions k_linearize
  * uses: r [n*8] and J [n*8*15] times sqrt(rho'(s)), s = |r|^2 over the

@@ -170,6 +170,20 @@ int arslam_localize_many_sized(const arslam_localize_batch *b, const arslam_lm_o
                                const double *tag_size, int kind, double a, arslam_localize_result *res,
                                double *cov, int *cov_status);
 
+/* ---- camera model ----
+ * The handle's camera model (arslam_lm.h ARSLAM_CAMERA_*), PINHOLE on creation.
+ * Under RADIAL l1 = camera[1] and l2 = camera[2] of the loaded batch are a
+ * known calibration, as the whole camera block is for the localizer.  The
+ * model reaches arslam_localizer_load*, _solve, _observation_terms and
+ * _covariance; the batch stays loaded when it changes, but the next
+ * _observation_terms or _covariance needs a solve under the new model first
+ * (ARSLAM_E_STATE).  init_from_map's initCapturePose stays the pinhole's: it
+ * only seeds the LM.  An unknown value returns ARSLAM_E_INVALID_ARG and leaves
+ * the handle unchanged.  The one-shot arslam_localize_many* calls have no
+ * handle to set and stay PINHOLE. */
+int arslam_localizer_set_camera_model(arslam_localizer *h, int model);
+int arslam_localizer_camera_model(const arslam_localizer *h, int *model);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,21 @@ int arslam_slam_aruco_size(const arslam_slam *h, int a, double *size);
  * the call with the default argument (ARSLAM_DEFAULT_TAG_SIZE). */
 int arslam_slam_debug_init_pose(int which, const double rect[8], const double camera[3], const double pose_in[6],
                                 double size, double pose_out[6]);
+/* The camera model (arslam_lm.h ARSLAM_CAMERA_*; PINHOLE initially) of the
+ * mapper handle and the localizer handle the solver keeps: under RADIAL the
+ * camera's l1 and l2 are a known calibration that every solve holds.  Once a
+ * residual block has been added the model is bound: ARSLAM_E_STATE, as
+ * arslam_slam_set_aruco_size for a bound tag.  An unknown value is
+ * ARSLAM_E_INVALID_ARG and changes nothing.  The initialisers stay the
+ * pinhole's.  The map file keeps the model as `model: radial` inside `camera:`,
+ * written only under RADIAL (a pinhole map is byte for byte what it was);
+ * loading accepts `model: pinhole` or `radial`, takes a missing key as pinhole
+ * and fails on anything else. */
+int arslam_slam_set_camera_model(arslam_slam *h, int model);
+int arslam_slam_camera_model(const arslam_slam *h, int *model);
+/* The plumb_bob distortion vector beside arslam_slam_camera_info's K and P:
+ * [l1, l2, 0, 0, 0] under RADIAL, zeros under PINHOLE. */
+int arslam_slam_camera_distortion(const arslam_slam *h, double d[5]);
 
 int arslam_slam_load_yaml(arslam_slam *h, const char *path);
 int arslam_slam_load_yaml_string(arslam_slam *h, const char *text);
