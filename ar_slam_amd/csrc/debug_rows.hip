@@ -35,6 +35,23 @@ __global__ void k_debug_rj(int n, const double *__restrict__ cam, const double *
   for (int j = 0; j < 12; ++j) out[3 + j] = j13[1 + j];
 }
 
+// one thread per (observation, row): the radial model's residual and the row's
+// two l columns (residual_jacobian_row's Jl, as fill_rows<.., 2> takes them)
+template <bool kSized>
+__global__ void k_debug_rj_l(int n, const double *__restrict__ cam, const double *__restrict__ cap,
+                             const double *__restrict__ tag, const double *__restrict__ corners,
+                             const double *__restrict__ size, double *__restrict__ r, double *__restrict__ Jl) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= 8L * n) return;
+  const long o = e / 8;
+  const int row = (int)(e % 8), corner = row >> 1, comp = row & 1;
+  double j13[13], jl[2];
+  r[e] = residual_jacobian_row<true>(cam + 3 * o, cap + 6 * o, tag + 6 * o, kSized ? 0.5 * size[o] : kArucoHalf,
+                                     corner, comp, corners[8 * o + row], j13, jl);
+  Jl[2 * e] = jl[0];
+  Jl[2 * e + 1] = jl[1];
+}
+
 // the same rows corrected for each observation's loss (robustify_row, as
 // fill_rows<true> forms them) and rho(s) per observation; 8 n is a multiple of
 // 8, so an observation's 8 lanes are active together
@@ -140,6 +157,29 @@ extern "C" int arslam_debug_residual_jacobian_model(int n, int model, const doub
                                                     const double *size, double *r, double *J) {
   if (!ARSLAM_CAMERA_MODEL_VALID(model)) return ARSLAM_E_INVALID_ARG;
   return debug_rows(n, cam, cap, tag, corners, size, r, J, model);
+}
+
+extern "C" int arslam_debug_residual_jacobian_distortion(int n, const double *cam, const double *cap,
+                                                         const double *tag, const double *corners,
+                                                         const double *size, double *r, double *Jl) {
+  if (n < 0 || (n && (!cam || !cap || !tag || !corners || !r || !Jl))) return ARSLAM_E_INVALID_ARG;
+  for (int i = 0; size && i < n; ++i)
+    if (!arslam::tag_size_valid(size[i])) return ARSLAM_E_INVALID_ARG;
+  if (n == 0) return ARSLAM_OK;
+  return arslam::api_guarded([&] {
+    DevBuf<double> d_in, d_out;   // d_out: r [8 n] | Jl [16 n]
+    arslam::upload_rows(d_in, n, cam, cap, tag, corners, size);
+    d_out.alloc(24L * n);
+    double *d_r = d_out.p, *d_J = d_r + 8L * n;
+    const double *d_size = size ? d_in.p + 23L * n : nullptr;
+    auto kernel = size ? arslam::k_debug_rj_l<true> : arslam::k_debug_rj_l<false>;
+    hipLaunchKernelGGL(kernel, arslam::blocks_of_128(8L * n), dim3(128), 0, 0, n, d_in.p, d_in.p + 3L * n,
+                       d_in.p + 9L * n, d_in.p + 15L * n, d_size, d_r, d_J);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    arslam::download(r, d_r, 8L * n);
+    arslam::download(Jl, d_J, 16L * n);
+  });
 }
 
 extern "C" int arslam_debug_residual_jacobian_loss(int n, const double *cam, const double *cap,

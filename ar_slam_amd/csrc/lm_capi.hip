@@ -144,6 +144,8 @@ int arslam_lm_set_camera_model(arslam_lm *h, int model) {
     fail_if(!ARSLAM_CAMERA_MODEL_VALID(model), ARSLAM_E_INVALID_ARG,
             "camera model: ARSLAM_CAMERA_PINHOLE or ARSLAM_CAMERA_RADIAL");
     if (model == h->camera_model) return;
+    fail_if(model == ARSLAM_CAMERA_RADIAL && h->estimate_distortion && h->multi(), ARSLAM_E_UNSUPPORTED,
+            "estimate_distortion is single-rank only: ARSLAM_CAMERA_RADIAL with it on a handle of several ranks");
     h->camera_model = model;
     // (as arslam_lm_set_tag_size: the resident problem was linearized under the
     // other model; so was its last solve, which a kept covariance describes)
@@ -157,6 +159,60 @@ int arslam_lm_camera_model(const arslam_lm *h, int *model) {
   if (!h || !model) return ARSLAM_E_INVALID_ARG;
   *model = h->camera_model;
   return ARSLAM_OK;
+}
+
+int arslam_lm_set_estimate_distortion(arslam_lm *h, int on) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return arslam::api_guarded([&] {
+    fail_if(on != 0 && on != 1, ARSLAM_E_INVALID_ARG, "estimate_distortion: 0 or 1");
+    if (on == h->estimate_distortion) return;
+    fail_if(on && h->camera_model == ARSLAM_CAMERA_RADIAL && h->multi(), ARSLAM_E_UNSUPPORTED,
+            "estimate_distortion is single-rank only (the l1, l2 rows have no rank exchange)");
+    h->estimate_distortion = on;
+    // (as arslam_lm_set_camera_model: the resident problem and its last solve
+    // had the other set of parameters)
+    h->loaded = false;
+    h->pk_dirty = true;
+    h->cov_invalidate();
+  });
+}
+
+int arslam_lm_estimate_distortion(const arslam_lm *h, int *on) {
+  if (!h || !on) return ARSLAM_E_INVALID_ARG;
+  *on = h->estimate_distortion;
+  return ARSLAM_OK;
+}
+
+int arslam_lm_debug_camera_rows(arslam_lm *h, double radius, long n_cols, double *rows, int *row_slot) {
+  if (!h || !rows || !(radius > 0.0)) return ARSLAM_E_INVALID_ARG;
+  return arslam::api_guarded([&] {
+    fail_if(!h->loaded || h->multi() || !h->has_f || h->P.cam_row < 0, ARSLAM_E_STATE,
+            "camera_rows: a one-rank problem loaded with a free camera");
+    fail_if(n_cols != h->nR + 1, ARSLAM_E_INVALID_ARG, "camera_rows: n_cols must be the reduced row count + 1");
+    h->ensure_stream();
+    h->cov_invalidate();
+    // as solve()'s iteration 0 and its first step up to the factorization
+    h->x = h->d_xa.p;
+    h->xc = h->d_xb.p;
+    h->xbest = h->x;
+    HIP_CHECK(hipMemcpyAsync(h->x, h->u_x0, h->n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    for (auto &t : h->timers) t.on = false;
+    double c0, c1, c2, c3, c4;
+    h->linearize(&c0, &c1, &c2, &c3, &c4);
+    const arslam::LmDiagArgs ld{h->n, h->d_scale.p, h->d_colnorm.p, h->opt.min_lm_diagonal, h->opt.max_lm_diagonal,
+                                h->d_diag.p};
+    arslam::launch_scale(h->P, h->d_colnorm.p, h->opt.jacobi_scaling, h->d_scale.p, h->stream, &ld);
+    arslam::launch_schur(h->P, h->x, h->d_scale.p, h->d_diag.p, radius, h->Sp, h->stream, true, h->plan.n_tiles);
+    if (h->est_loaded) arslam::launch_schur_cam(h->P, h->CL, h->d_scale.p, h->d_diag.p, radius, h->Sp, h->stream);
+    DevBuf<double> d_out;
+    d_out.alloc(3 * n_cols);
+    arslam::debug_cam_rows(h->P, h->Sp, d_out.p, h->stream);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(rows, d_out.p, 3 * n_cols * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (row_slot)
+      for (int b = 0; b < 3; ++b) row_slot[b] = h->lay.row_slot[h->P.cam_row + b];
+  });
 }
 
 int arslam_lm_add_residual_block(arslam_lm *h, const double corners[8], double *camera,
@@ -484,6 +540,8 @@ int arslam_lm_set_comm_callback(arslam_lm *h, int rank, int nranks, arslam_allre
   if (!h || nranks < 1 || rank < 0 || rank >= nranks || ((nranks > 1 || h->force_multi) && !fn))
     return ARSLAM_E_INVALID_ARG;
   return arslam::api_guarded([&] {
+    fail_if(h->est_active() && (nranks > 1 || h->force_multi), ARSLAM_E_UNSUPPORTED,
+            "estimate_distortion is single-rank only (the l1, l2 rows have no rank exchange)");
     if (h->comm) { (void)ncclCommDestroy(h->comm); h->comm = nullptr; }
     h->rank = rank;
     h->nranks = nranks;
@@ -497,6 +555,8 @@ int arslam_lm_set_comm_callback(arslam_lm *h, int rank, int nranks, arslam_allre
 int arslam_lm_set_comm(arslam_lm *h, int rank, int nranks, const unsigned char id[ARSLAM_COMM_ID_BYTES]) {
   if (!h || !id || nranks < 1 || rank < 0 || rank >= nranks) return ARSLAM_E_INVALID_ARG;
   return arslam::api_guarded([&] {
+    fail_if(h->est_active() && (nranks > 1 || h->force_multi), ARSLAM_E_UNSUPPORTED,
+            "estimate_distortion is single-rank only (the l1, l2 rows have no rank exchange)");
     h->ensure_stream();
     if (h->comm) { (void)ncclCommDestroy(h->comm); h->comm = nullptr; }
     h->comm_cb = nullptr;
@@ -543,6 +603,8 @@ int arslam_lm_debug_force_indefinite(arslam_lm *h, unsigned long long step_mask)
 int arslam_lm_debug_force_multirank(arslam_lm *h, int on) {
   if (!h || (on != 0 && on != 1)) return ARSLAM_E_INVALID_ARG;
   return arslam::api_guarded([&] {
+    fail_if(on && h->est_active(), ARSLAM_E_UNSUPPORTED,
+            "estimate_distortion is single-rank only (the l1, l2 rows have no rank exchange)");
     if (h->comm) { (void)ncclCommDestroy(h->comm); h->comm = nullptr; }
     h->comm_cb = nullptr;
     h->rank = 0;

@@ -5,6 +5,8 @@
 
 void arslam_lm::cov_check_state(const char *who) const {
   const std::string w(who);
+  fail_if(est_active(), ARSLAM_E_UNSUPPORTED,
+          w + ": not supported while estimate_distortion is on (the covariance eliminations hold l1, l2)");
   fail_if(!loaded || solve_state == 0, ARSLAM_E_STATE, w + ": no completed solve of the loaded problem");
   fail_if(solve_state == 2, ARSLAM_E_STATE, w + ": the last solve ended with rule EVAL_FAILED");
   fail_if(multi(), ARSLAM_E_UNSUPPORTED, w + ": single-rank only");

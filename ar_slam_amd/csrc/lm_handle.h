@@ -223,6 +223,22 @@ struct arslam_lm {
   // the camera model of the next load (arslam_lm_set_camera_model): the loaded
   // problem's is DevProblem::camera_radial, and a change drops that problem
   int camera_model = ARSLAM_CAMERA_PINHOLE;
+  // "estimate the distortion" (arslam_lm_set_estimate_distortion): a property
+  // of the handle like the camera model, bound at the next load; it takes
+  // effect under ARSLAM_CAMERA_RADIAL only (est_active), and the loaded
+  // problem's is est_loaded (a free camera besides): CL beside P
+  int estimate_distortion = 0;
+  bool est_active() const { return estimate_distortion != 0 && camera_model == ARSLAM_CAMERA_RADIAL; }
+  // what the switch does not cover, refused before the handle changes
+  void est_check_load(const arslam_soa_problem *p_in) const;
+  bool est_loaded = false;
+  arslam::DevCamL CL{};
+  const arslam::DevCamL *cl() const { return est_loaded ? &CL : nullptr; }
+  std::vector<int> camg_start;    // DevCamL::camg_start, camg_items (x, y interleaved)
+  std::vector<int> camg_items;
+  int *u_camg_start = nullptr;
+  int2 *u_camg_items = nullptr;
+  DevBuf<double> d_jrows_l, d_cam_slab, d_lparts, d_lred;
   std::vector<double> soa_size;   // arslam_lm_load_soa*'s tag sides, per observation
   // the side of each observation's tag from the per-tag sides (null: the
   // handle's default for every tag); null when every side is the default

@@ -12,8 +12,11 @@
 namespace arslam {
 
 // ---- lm_linearize.hip ----
+// (cl: a problem whose l1, l2 are estimated -- the instances that also store
+// the rows' l columns, cl->jrows_l, and the per-capture partials of the l
+// gradient and column norms, cl->lparts; null: the launches it has always been)
 void launch_linearize(const DevProblem &P, const double *x, double *g, double *colnorm,
-                      double *obs_tg, double *parts, hipStream_t s);
+                      double *obs_tg, double *parts, hipStream_t s, const DevCamL *cl = nullptr);
 
 // ---- lm_schur.hip ----
 // k_schur<true>'s dynamic-LDS attribute on the current device (once per device)
@@ -39,10 +42,21 @@ void debug_set_reduced_diag(const DevProblem &P, double *S, long row, double v, 
 // k_schur's phase clocks, 16 words (zeros unless built with -DARSLAM_SCHUR_STAMPS)
 void debug_read_schur_stamps(unsigned long long *out);
 
+// ---- lm_schur_cam.hip ----
+// A problem whose l1, l2 are estimated (one rank, prep mode), after launch_schur on the same stream: the e-blocks' borders of the
+// Schur complement for the two l columns (k_schur_cam, from jrows, cl.jrows_l and
+// the cap_ui k_schur left) and their sums into reduced rows cam_row + 1,
+// cam_row + 2 and the rhs row, with the rows' D_f^2.
+void launch_schur_cam(const DevProblem &P, const DevCamL &cl, const double *scale, const double *diag, double radius, double *S,
+                      hipStream_t s);
+// debug: reduced rows cam_row .. cam_row + 2 of S against every reduced column
+// and the rhs, out[b (nR + 1) + col] (device memory)
+void debug_cam_rows(const DevProblem &P, double *S, double *out, hipStream_t s);
+
 // ---- lm_step.hip ----
 void launch_backsub(const DevProblem &P, const double *x, const double *scale, const double *diag,
                     double radius, const double *yF, double *xc, double *parts, hipStream_t s,
-                    bool reuse_ui = false, bool with_cost = false);
+                    bool reuse_ui = false, bool with_cost = false, const DevCamL *cl = nullptr);
 // candidate f-side slots: xc = x - s yF on reduced rows, xc = x elsewhere (every
 // f-side slot is written); fparts: 2 per 256 reduced rows
 void launch_update_f(const DevProblem &P, const double *x, const double *scale, const double *yF,
@@ -92,9 +106,12 @@ void launch_lm_diag(const DevProblem &P, const double *scale, const double *coln
 // its per-block partials.
 // (ld: also the LM diagonal clamp(s^2 colnorm) of every slot from ld->scale, into ld->diag)
 // (seq > 0: with hout, the last block stores seq into hout[kHostSeq] after the results)
+// (cl: a problem whose l1, l2 are estimated -- launch_linearize's l partials
+// are summed into cl->lred[0..3] first, and camera slots 1, 2 of g and
+// colnorm, the norms and the LM diagonal take them from there)
 void launch_slot_norms(const DevProblem &P, const double *red, double *g, double *colnorm, const double *x,
                        double *out, hipStream_t s, double *hout = nullptr, const LmDiagArgs *ld = nullptr,
-                       double seq = 0.0);
+                       double seq = 0.0, const DevCamL *cl = nullptr);
 // x[0..n) into the page-locked dst; the last block stores seq into *word (page-locked,
 // after the data; seq_done: a zeroed device int, left zero again)
 void launch_copy_out(const double *src, long n, double *dst, int *seq_done, double *word, double seq, hipStream_t s);

@@ -12,6 +12,10 @@
 //
 // Every sum is fixed-order (no atomics): over an observation's 8 rows, then
 // over the capture's rows chunk by chunk in row order.
+//
+// k_linearize_est, the same body (lm_linearize_body.h) for a problem whose
+// l1, l2 are estimated: it also stores the rows' two l columns and leaves the
+// capture's l gradient and column-norm partials.
 #include "lm_launch.h"
 #include "lm_rows.h"
 
@@ -48,103 +52,50 @@ constexpr int linearize_min_waves(bool chunked, bool sized, bool dist) {
 // (kSized: the same attribute for the one-chunk instances, 96 / 98 VGPRs as
 // without; the chunked ones ask for 2 waves instead of 4 and so take the
 // registers the others spill for: no scratch, profiles/tag_size/resource_usage.txt)
-// (kDist: linearize_min_waves)
+// (kDist: linearize_min_waves; the body: lm_linearize_body.h)
 template <bool kChunked, bool kLoss, bool kSized, bool kDist>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(linearize_min_waves(kChunked, kSized, kDist), 8))) void k_linearize(DevProblem P, const double *__restrict__ x,
                                                      double *__restrict__ g,
                                                      double *__restrict__ colnorm,
                                                      double *__restrict__ obs_tg,
                                                      double *__restrict__ parts) {
-  extern __shared__ __attribute__((aligned(16))) double sm[];
-  const int c = kChunked ? P.chunk_caps[blockIdx.x] : (int)blockIdx.x, lane = threadIdx.x;
-  const int o0 = P.cap_start[c], k = P.cap_start[c + 1] - o0;
-  if (!kChunked && k > kObsChunk) return;   // (the chunked launch's)
-  const int nrows = 8 * k;
-  // The rows go through LDS in chunks of kObsChunk observations (one wave's
-  // 64 rows), so any number of observations per capture fits; every sum runs
-  // on over the chunks in the same order as over the whole capture at once
-  double *rows = sm;
-  double *ocost = rows + (long)8 * kObsChunk * kRowStride;   // [kObsChunk]
-  // the running sums carried over the chunks, in LDS (nothing held in
-  // registers across the projection): lanes 0..13's per-capture sums, then
-  // the active and fixed cost
-  double *accs = ocost + kObsChunk;   // [16]
-  // (one chunk -- the usual capture -- as its own specialised copy: the loop
-  // around the projection cost the single-chunk code spills)
-  auto chunk = [&](int q0) __attribute__((always_inline)) {
-    const int kc = min(kObsChunk, k - q0), nr = 8 * kc;
-    fill_rows<kLoss, kSized, kDist>(P, x, nullptr, c, o0, 8 * q0, nr, nrows, rows, P.jrows, kLoss ? ocost : nullptr);
-    __syncthreads();
-    // Every sum below is over rows of one product of two LDS columns (ca, cb),
-    // picked per lane up front: one code path for the whole wave (a divergent
-    // if-chain ran each case's LDS round trips one after another)
-    // per observation: cost (r'r), tag gradient (6: F_t'r), tag column norms (6)
-    for (int e = lane; e < 13 * kc; e += kWave) {
-      const int q = e / 13, it = e % 13;
-      const double *rq = rows + (long)q * 8 * kRowStride;
-      const int ca = it == 0 ? 13 : it <= 6 ? 6 + it : it, cb = it <= 6 ? 13 : it;
-      double s = 0.0;
-#pragma unroll
-      for (int rr = 0; rr < 8; ++rr) s += rq[rr * kRowStride + ca] * rq[rr * kRowStride + cb];
-      if (it == 0) {
-        if (!kLoss) ocost[q] = 0.5 * s;   // (kLoss: rho / 2, left there by fill_rows)
-      }
-      else obs_tg[12L * P.obs_tpos[o0 + q0 + q] + (it - 1)] = s;   // (tag-major: k_lin_reduce reads a tag's at once)
-    }
-    // per capture: capture gradient (6: E'r), capture column norms (6), f gradient, f column norm
-    if (lane < 14) {
-      const int ca = lane < 6 ? 1 + lane : lane < 12 ? lane - 5 : 0;
-      const int cb = lane < 6 ? 13 : lane < 12 ? lane - 5 : lane == 12 ? 13 : 0;
-      double ps = q0 ? accs[lane] : 0.0;
-#pragma unroll 8
-      for (int r = 0; r < nr; ++r) ps += row_prod(rows + (long)r * kRowStride, ca, cb);
-      accs[lane] = ps;
-    }
-    __syncthreads();
-    if (lane == 0) {
-      double act = q0 ? accs[14] : 0.0, fix = q0 ? accs[15] : 0.0;
-      for (int q = 0; q < kc; ++q) {
-        if (P.obs_active[o0 + q0 + q]) act += ocost[q]; else fix += ocost[q];
-      }
-      accs[14] = act;
-      accs[15] = fix;
-    }
-  };
-  if (!kChunked) {   // (at most one chunk)
-    chunk(0);
-  } else {
-    for (int q0 = 0; q0 < k; q0 += kObsChunk) {
-      if (q0) __syncthreads();   // the previous chunk's LDS reads are done
-      chunk(q0);
-    }
-  }
-  if (lane < 14) {
-    const double ps = k ? accs[lane] : 0.0;
-    if (lane < 12) {
-      const long slot = slot_cap(P, c) + (lane % 6);
-      const double v = P.slot_free[slot] ? ps : 0.0;
-      if (lane < 6) g[slot] = v; else colnorm[slot] = v;
-    } else if (lane == 12) {
-      parts[(long)P_GF * P.nc + c] = ps;
-    } else {
-      parts[(long)P_CF * P.nc + c] = ps;
-    }
-  }
-  if (lane == 0) {
-    parts[(long)P_COST * P.nc + c] = k ? accs[14] : 0.0;
-    parts[(long)P_FIXED * P.nc + c] = k ? accs[15] : 0.0;
-  }
+  constexpr int kMode = kDist ? 1 : 0;
+  constexpr double *lparts = nullptr, *jrows_l = nullptr;
+#include "lm_linearize_body.h"
+}
+
+// The instance of a problem whose l1, l2 are estimated (DevCamL): the radial
+// rows, their two l columns into jrows_l and the l partials into lparts.  (the
+// radial instances' register bound)
+template <bool kChunked, bool kLoss, bool kSized>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(linearize_min_waves(kChunked, kSized, true), 8))) void k_linearize_est(DevProblem P, const double *__restrict__ x,
+                                                     double *__restrict__ g,
+                                                     double *__restrict__ colnorm,
+                                                     double *__restrict__ obs_tg,
+                                                     double *__restrict__ parts,
+                                                     double *__restrict__ lparts,
+                                                     double *__restrict__ jrows_l) {
+  constexpr int kMode = 2;
+#include "lm_linearize_body.h"
 }
 
 }  // namespace
 
 void launch_linearize(const DevProblem &P, const double *x, double *g, double *colnorm,
-                      double *obs_tg, double *parts, hipStream_t s) {
+                      double *obs_tg, double *parts, hipStream_t s, const DevCamL *cl) {
   if (P.nc == 0) return;
   const size_t lds = lds_rows(kObsChunk) + sizeof(double) * (kObsChunk + 16);
   // (the instance per loaded problem: kLoss iff it has robust losses, kSized
   // iff some tag's side is not the default, kDist iff loaded under the radial model)
   const bool loss = P.obs_loss_kind != nullptr, sized = P.obs_size != nullptr, dist = P.camera_radial != 0;
+  if (cl) {   // l1, l2 estimated: the instances that also leave the l columns and partials
+    hipLaunchKernelGGL(ARSLAM_PICK_INSTANCE_EST(k_linearize_est, false, loss, sized), dim3(P.nc), dim3(kWave), lds, s, P,
+                       x, g, colnorm, obs_tg, parts, cl->lparts, cl->jrows_l);
+    if (P.n_chunk_caps)
+      hipLaunchKernelGGL(ARSLAM_PICK_INSTANCE_EST(k_linearize_est, true, loss, sized), dim3(P.n_chunk_caps),
+                         dim3(kWave), lds, s, P, x, g, colnorm, obs_tg, parts, cl->lparts, cl->jrows_l);
+    return;
+  }
   hipLaunchKernelGGL(ARSLAM_PICK_INSTANCE(k_linearize, false, loss, sized, dist), dim3(P.nc), dim3(kWave), lds, s, P,
                      x, g, colnorm, obs_tg, parts);
   if (P.n_chunk_caps)

@@ -124,8 +124,23 @@ void arslam_lm::build_plans(const arslam::HostProblem &h, arslam::ReducedLayout 
   }
 }
 
+// "Estimate the distortion" covers one rank and a whole eliminated side: the
+// border of the Schur complement (lm_schur_cam.hip) has no rank exchange and
+// no direct groups.  Checked before load() touches the handle.
+void arslam_lm::est_check_load(const arslam_soa_problem *p_in) const {
+  if (!est_active()) return;
+  fail_if(multi(), ARSLAM_E_UNSUPPORTED,
+          "estimate_distortion is single-rank only (the l1, l2 rows have no rank exchange)");
+  if (opt.elimination != ARSLAM_ELIM_MIXED || !p_in) return;
+  const arslam::SchurSide cs = arslam::ceres_schur_side(p_in);
+  fail_if(!(cs.e_cam || cs.e_tag == 0 || cs.e_cap == 0), ARSLAM_E_UNSUPPORTED,
+          "estimate_distortion: ARSLAM_ELIM_MIXED whose e-block set mixes captures and tags is not supported "
+          "(ARSLAM_ELIM_CAPTURES, _TAGS or _AUTO)");
+}
+
 void arslam_lm::load(const arslam_soa_problem *p_in, const arslam::ObsLoss &in_loss) {
   const double t_load = now_s();
+  est_check_load(p_in);
   loaded = false;
   cov_invalidate();
   cov_sp_ready = false;
@@ -362,6 +377,24 @@ void arslam_lm::upload_problem(const arslam::HostProblem &h, const arslam::Reduc
     upload.add(&u_gather_items, reinterpret_cast<const int4 *>(sg.items.data()), n_items);
     upload.add(&u_gather_splits, reinterpret_cast<const int4 *>(sg.splits.data()), n_splits);
   }
+  // l1, l2 estimated (est_check_load passed: one rank, a whole side): per
+  // f-block the (e-block, local block) pairs that see it, in e-block order
+  const bool est = est_active() && has_f && L.cam_row >= 0;
+  if (est) {
+    camg_start.assign(nt + 1, 0);
+    for (int t : h.blk_tag) camg_start[t + 1]++;
+    for (int t = 0; t < nt; ++t) camg_start[t + 1] += camg_start[t];
+    camg_items.assign(2 * h.blk_tag.size(), 0);
+    std::vector<int> fill(camg_start.begin(), camg_start.end() - 1);
+    for (int c = 0; c < nc; ++c)
+      for (int a = h.cap_blk_start[c]; a < h.cap_blk_start[c + 1]; ++a) {
+        const int at = fill[h.blk_tag[a]]++;
+        camg_items[2L * at] = c;
+        camg_items[2L * at + 1] = a - h.cap_blk_start[c];
+      }
+    upload.add(&u_camg_start, camg_start.data(), camg_start.size());
+    upload.add(&u_camg_items, reinterpret_cast<const int2 *>(camg_items.data()), camg_items.size() / 2);
+  }
   n_clear = has_f ? plan.n_tiles : 0;
   if (has_f && !multi()) {
     // does the gather write into a fill tile (an appended problem's new
@@ -398,6 +431,22 @@ void arslam_lm::upload_problem(const arslam::HostProblem &h, const arslam::Reduc
   P.obs_loss_a = has_loss ? u_loss_a : nullptr;
   P.obs_size = has_size ? u_obs_size : nullptr;
   P.camera_radial = camera_model == ARSLAM_CAMERA_RADIAL ? 1 : 0;   // (the handle's model, bound at the load)
+  if (est) {   // (allocated under the switch only)
+    d_jrows_l.alloc(std::max(16L * nb, 1L));
+    d_cam_slab.alloc(std::max(8L * nc + 12L * (long)h.blk_tag.size(), 1L));
+    d_lparts.alloc(4L * std::max(nc, 1));
+    d_lred.alloc(4);
+  }
+  est_loaded = est;
+  CL = arslam::DevCamL{};
+  if (est) {
+    CL.jrows_l = d_jrows_l.p;
+    CL.lparts = d_lparts.p;
+    CL.lred = d_lred.p;
+    CL.cam_slab = d_cam_slab.p;
+    CL.camg_start = u_camg_start;
+    CL.camg_items = u_camg_items;
+  }
   P.tag_row = u_tag_row; P.row_slot = u_row_slot;
   P.tile_id = plan.tile_id; P.T = plan.T;
   P.tile_class = multi() && has_f ? plan.tile_class : nullptr;
@@ -577,6 +626,7 @@ bool arslam_lm::groups_fit_plan(const arslam::HostProblem &h, const std::vector<
 // ceres_e_* plus the new captures (they are not re-derived on the grown graph).
 bool arslam_lm::try_append(const arslam_soa_problem *p, const arslam::ObsLoss &in_loss) {
   if (!loaded || multi() || !has_f) return false;
+  if (est_active()) return false;   // (the border's gather lists are built by a full load)
   const double t0 = now_s();
   arslam::MixedProblem m;
   const arslam_soa_problem *dev = nullptr;   // the device problem's source

@@ -171,6 +171,27 @@ struct DevProblem {
   const double *obs_size = nullptr;               // [nb] metres
 };
 
+// The handle's "estimate the distortion" switch on a problem loaded under
+// ARSLAM_CAMERA_RADIAL with a free camera: what the kernels of that path read
+// and write besides DevProblem.  A struct of its own, passed to those kernels
+// alone: DevProblem and every kernel that takes it stay as they are.
+// jrows_l: the rows' two l columns beside jrows ((row, a) of a capture at
+// 16 o0 + a 8k + row).  lparts, lred: k_linearize_est's per-capture partials of
+// the l gradient and squared column norms and their sums.  cam_slab:
+// k_schur_cam's border of the Schur complement, 2 (m + 3) values per e-block c
+// (m = 1 + 6 distinct f-blocks) at 8 c + 12 cap_blk_start[c]: for a in
+// {l1, l2} the entries against f, the local tag columns, l1, l2 (b <= a) and
+// the rhs.  camg_*: per f-block the (e-block, local block) pairs that see it,
+// in e-block order (the border gather's summation order).
+struct DevCamL {
+  double *jrows_l = nullptr;        // [16 nb]
+  double *lparts = nullptr;         // [4 nc]
+  double *lred = nullptr;           // [4]
+  double *cam_slab = nullptr;       // [8 nc + 12 cap_blk_start[nc]]
+  const int *camg_start = nullptr;  // [nt + 1]
+  const int2 *camg_items = nullptr; // [cap_blk_start[nc]] {e-block, local block 0..}
+};
+
 // element (r, c), r >= c, of the compact-tiled reduced system
 __device__ inline double *reduced_elem(double *S, const DevProblem &P, long r, long c) {
   return S + (long)P.tile_id[(r >> 6) * P.T + (c >> 6)] * 4096 + (r & 63) * 64 + (c & 63);

@@ -12,6 +12,9 @@
 // finish stores the sequence number the host polls; k_copy_out hands the
 // parameters over the same way.
 //
+// k_cam_l_reduce and k_slot_norms_l (k_slot_norms' body, lm_slot_norms_body.h):
+// the camera's l1, l2 slots of a problem that estimates them.
+//
 // Every sum that feeds an LM decision (cost, model cost change, step and
 // gradient norms) is fixed-order: a fixed element -> thread assignment and a
 // fixed tree, whichever block finishes last, and no atomics in any sum, so a
@@ -176,6 +179,7 @@ __global__ void k_lm_diag(long n, const double *__restrict__ scale, const double
 // camera + tag slots (out[3..5]): max |g|, sum g^2, sum x^2.  The split lets
 // the capture-sharded path reduce only the disjoint capture part across ranks.
 
+// (the body: lm_slot_norms_body.h)
 __global__ __launch_bounds__(256) void k_slot_norms(long n, long cap_lo, long cap_hi,
                                                     const unsigned char *__restrict__ free_,
                                                     const unsigned char *__restrict__ f_own,
@@ -185,97 +189,45 @@ __global__ __launch_bounds__(256) void k_slot_norms(long n, long cap_lo, long ca
                                                     double *__restrict__ out,
                                                     double *__restrict__ hout, const double *__restrict__ scale,
                                                     double dmin, double dmax, double *__restrict__ diag, double seq) {
-  __shared__ double rs[6][256];
-  __shared__ int last;
+  constexpr bool kL = false;
+  constexpr const double *lred = nullptr;
+#include "lm_slot_norms_body.h"
+}
+
+// ... of a problem whose l1, l2 are estimated
+__global__ __launch_bounds__(256) void k_slot_norms_l(long n, long cap_lo, long cap_hi,
+                                                      const unsigned char *__restrict__ free_,
+                                                      const unsigned char *__restrict__ f_own,
+                                                      double *__restrict__ g, double *__restrict__ colnorm,
+                                                      const double *__restrict__ red,
+                                                      const double *__restrict__ x,
+                                                      double *__restrict__ out,
+                                                      double *__restrict__ hout, const double *__restrict__ scale,
+                                                      double dmin, double dmax, double *__restrict__ diag, double seq,
+                                                      const double *__restrict__ lred) {
+  constexpr bool kL = true;
+#include "lm_slot_norms_body.h"
+}
+
+// The camera's l sums: block i (of 4) adds k_linearize_est's partials
+// lparts[i nc .. (i + 1) nc) -- J_l1'r, J_l2'r, |J_l1|^2, |J_l2|^2 per capture --
+// capture c in thread c mod 256, then one pairwise tree: a fixed order.
+__global__ __launch_bounds__(256) void k_cam_l_reduce(const double *__restrict__ lparts, int nc,
+                                                      double *__restrict__ lred) {
+  __shared__ double red[256];
   const int t = threadIdx.x;
-  // the camera slots from the reduced per-capture partials (f gradient and
-  // column norm; l1, l2 have no Jacobian column): written once, and used here
-  // in place of g[0..2]
-  const double g0 = free_[0] ? red[P_GF] : 0.0;
-  if (blockIdx.x == 0 && t == 0) {
-    g[0] = g0;
-    colnorm[0] = free_[0] ? red[P_CF] : 0.0;
-    g[1] = g[2] = 0.0;
-    colnorm[1] = colnorm[2] = 0.0;
-  }
-  const double cn0 = free_[0] ? red[P_CF] : 0.0;   // (colnorm[0], as block 0 writes it)
-  double v[6] = {0, 0, 0, 0, 0, 0};
-  for (long i = (long)blockIdx.x * 256 + t; i < n; i += (long)kNormBlocks * 256) {
-    if (diag) {   // the LM diagonal of the new linearization (launch_exec_reset's k_lm_diag work)
-      const double cn = i >= 3 ? colnorm[i] : (i == 0 ? cn0 : 0.0);
-      diag[i] = fmin(fmax(scale[i] * scale[i] * cn, dmin), dmax);
-    }
-    // (several ranks: each slot counted on the rank holding it, DevProblem::f_own)
-    if (!free_[i] || (f_own && !f_own[i])) continue;
-    const int o = (i >= cap_lo && i < cap_hi) ? 0 : 3;
-    const double gv = i >= 3 ? g[i] : (i == 0 ? g0 : 0.0), xv = x[i];
-    v[o] = fmax(v[o], fabs(gv));
-    v[o + 1] += gv * gv;
-    v[o + 2] += xv * xv;
-  }
-  for (int q = 0; q < 6; ++q) rs[q][t] = v[q];
+  const double *src = lparts + (long)blockIdx.x * nc;
+  double acc = 0.0;
+  for (int i = t; i < nc; i += 256) acc += src[i];
+  red[t] = acc;
   __syncthreads();
   for (int off = 128; off >= kWave; off >>= 1) {
-    if (t < off) {
-      rs[0][t] = fmax(rs[0][t], rs[0][t + off]);
-      rs[1][t] += rs[1][t + off];
-      rs[2][t] += rs[2][t + off];
-      rs[3][t] = fmax(rs[3][t], rs[3][t + off]);
-      rs[4][t] += rs[4][t + off];
-      rs[5][t] += rs[5][t + off];
-    }
-    __syncthreads();
-  }
-  if (t < kWave)
-    for (int q = 0; q < 6; ++q) {
-      const double r = (q % 3 == 0) ? wave_tree_max(rs[q][t], kWave) : wave_tree_sum(rs[q][t], kWave);
-      if (t == 0) rs[q][0] = r;
-    }
-  // out[8 + 6 b + q]: block b's partials; out[7] (as an int): blocks done.
-  // The last block to finish reduces the kNormBlocks partials over a fixed
-  // tree (independent of which block is last) into out[0..5], and resets the
-  // count for the next launch.
-  double *part = out + 8;
-  int *done = reinterpret_cast<int *>(out + 7);
-  if (t == 0) {
-    for (int q = 0; q < 6; ++q) part[6L * blockIdx.x + q] = rs[q][0];
-    __threadfence();   // the partials before the count (agent scope: the blocks span XCDs)
-    last = atomicAdd(done, 1) == kNormBlocks - 1;
-  }
-  __syncthreads();
-  if (!last) return;
-  __threadfence();     // every block's partials after the count
-  if (t < kNormBlocks)
-    for (int q = 0; q < 6; ++q) rs[q][t] = part[6L * t + q];
-  __syncthreads();
-  for (int off = kNormBlocks / 2; off >= kWave; off >>= 1) {
-    if (t < off)
-      for (int q = 0; q < 6; ++q)
-        rs[q][t] = (q % 3 == 0) ? fmax(rs[q][t], rs[q][t + off]) : rs[q][t] + rs[q][t + off];
+    if (t < off) red[t] += red[t + off];
     __syncthreads();
   }
   if (t < kWave) {
-    const int left = kNormBlocks < kWave ? kNormBlocks : kWave;
-    double r6[6];
-    for (int q = 0; q < 6; ++q) {
-      const double v0 = t < left ? rs[q][t] : 0.0;
-      r6[q] = (q % 3 == 0) ? wave_tree_max(v0, left) : wave_tree_sum(v0, left);
-    }
-    if (t == 0)
-      for (int q = 0; q < 6; ++q) rs[q][0] = r6[q];
-  }
-  __syncthreads();
-  if (t < 6) {
-    out[t] = rs[t][0];
-    if (hout) {
-      hout[t] = rs[t][0];
-      __threadfence_system();
-    }
-  }
-  if (t == 0) atomicExch(done, 0);
-  if (hout && seq > 0.0) {
-    __syncthreads();
-    if (t == 0) __hip_atomic_store(hout + kHostSeq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    const double r = wave_tree_sum(red[t], kWave);
+    if (t == 0) lred[blockIdx.x] = r;
   }
 }
 
@@ -319,8 +271,16 @@ void launch_reduce_parts(const double *parts, int nc, const double *fparts, int 
 }
 
 void launch_slot_norms(const DevProblem &P, const double *red, double *g, double *colnorm, const double *x,
-                       double *out, hipStream_t s, double *hout, const LmDiagArgs *ld, double seq) {
+                       double *out, hipStream_t s, double *hout, const LmDiagArgs *ld, double seq,
+                       const DevCamL *cl) {
   // out[0..5] results, out[7] the block count (zero between launches), out[8..] the per-block partials
+  if (cl) {   // l1, l2 estimated: their sums first, then the instance that reads them
+    hipLaunchKernelGGL(k_cam_l_reduce, dim3(4), dim3(256), 0, s, cl->lparts, P.nc, cl->lred);
+    hipLaunchKernelGGL(k_slot_norms_l, dim3(kNormBlocks), dim3(256), 0, s, P.n, 3L, 3L + 6L * P.nc, P.slot_free,
+                       P.f_own, g, colnorm, red, x, out, hout, ld ? ld->scale : nullptr, ld ? ld->dmin : 0.0,
+                       ld ? ld->dmax : 0.0, ld ? ld->diag : nullptr, seq, cl->lred);
+    return;
+  }
   hipLaunchKernelGGL(k_slot_norms, dim3(kNormBlocks), dim3(256), 0, s, P.n, 3L, 3L + 6L * P.nc, P.slot_free, P.f_own, g,
                      colnorm, red, x, out, hout, ld ? ld->scale : nullptr, ld ? ld->dmin : 0.0,
                      ld ? ld->dmax : 0.0, ld ? ld->diag : nullptr, seq);

@@ -46,11 +46,14 @@ __device__ __forceinline__ double lm_d2(const double *diag, long slot, double ra
 // rho'' <= 0) on one row of an observation whose 8 rows sit in 8 consecutive
 // lanes: r and its 13 Jacobian entries times sqrt(rho'(s)), s = |r|^2 over
 // the 8 rows.  Returns rho(s), the same in the 8 lanes.
-__device__ __forceinline__ double robustify_row(int kind, double a, double &r, double J[13]) {
+// (w_out: also the factor itself, for the columns the caller keeps beside J)
+__device__ __forceinline__ double robustify_row(int kind, double a, double &r, double J[13],
+                                                double *w_out = nullptr) {
   const double s = obs_sum8(r * r);
   double rho, rho1;
   loss_eval(kind, a, s, &rho, &rho1);
   const double w = sqrt(rho1);
+  if (w_out) *w_out = w;
 #pragma unroll
   for (int j = 0; j < 13; ++j) J[j] *= w;
   r *= w;
@@ -72,11 +75,17 @@ __device__ __forceinline__ double robustify_row(int kind, double a, double &r, d
 // every tag has the default side, a constant of the code.
 // kDist: the rows of the radial camera model, l1 and l2 from camera slots 1
 // and 2 of x (held: they never move, so a capture's rows are consistent over a
-// solve); else the pinhole's.
-template <bool kLoss = false, bool kSized = false, bool kDist = false>
+// solve); else the pinhole's.  kDist = 2 (the handle's "estimate the distortion"
+// switch, DevCamL::jrows_l = lout): the radial rows, and the row's two l columns,
+// d r / d l1 and d r / d l2 (corrected like the rest of the row), stored
+// column-major per capture in lout ((row, a) at 16 o0 + a nrows
+// + row); lsum then gets the lane's row's J_l1 r, J_l2 r, J_l1^2, J_l2^2 (zeros
+// for a lane without a row): the capture's l gradient and column-norm terms.
+template <bool kLoss = false, bool kSized = false, int kDist = 0>
 __device__ __forceinline__ void fill_rows(const DevProblem &P, const double *x, const double *scale, int c,
                           int o0, int row0, int nr, int nrows, double *rows, double *gout = nullptr,
-                          double *ocost = nullptr) {
+                          double *ocost = nullptr, double *lsum = nullptr, double *lout = nullptr) {
+  if (kDist == 2) lsum[0] = lsum[1] = lsum[2] = lsum[3] = 0.0;
   const double *cam = x;
   const double *cap = x + slot_cap(P, c);
   for (int lr = threadIdx.x; lr < nr; lr += kWave) {
@@ -90,12 +99,22 @@ __device__ __forceinline__ void fill_rows(const DevProblem &P, const double *x, 
     // still takes the capture first; the Jacobian halves come back as e|f)
     const bool sw = group_swapped(P, c);
     const double half = kSized ? 0.5 * P.obs_size[obs] : kArucoHalf;
-    double r = residual_jacobian_row<kDist>(cam, sw ? tag : cap, sw ? cap : tag, half, corner, comp,
-                                            P.corners[8L * obs + 2 * corner + comp], J);
+    double Jl[2], w = 1.0;
+    double r = residual_jacobian_row<kDist != 0>(cam, sw ? tag : cap, sw ? cap : tag, half, corner, comp,
+                                                 P.corners[8L * obs + 2 * corner + comp], J,
+                                                 kDist == 2 ? Jl : nullptr);
     if (kLoss) {
       // (nr is a multiple of 8: an observation's 8 lanes are in the loop together)
-      const double rho = robustify_row(P.obs_loss_kind[obs], P.obs_loss_a[obs], r, J);
+      const double rho = robustify_row(P.obs_loss_kind[obs], P.obs_loss_a[obs], r, J, kDist == 2 ? &w : nullptr);
       if (ocost && (lr & 7) == 0) ocost[lr >> 3] = 0.5 * rho;
+    }
+    if (kDist == 2) {
+      if (kLoss) { Jl[0] *= w; Jl[1] *= w; }
+      double *gl = lout + 16L * o0 + row;
+      gl[0] = Jl[0];
+      gl[nrows] = Jl[1];
+      lsum[0] = Jl[0] * r; lsum[1] = Jl[1] * r;
+      lsum[2] = Jl[0] * Jl[0]; lsum[3] = Jl[1] * Jl[1];
     }
     if (sw) {
 #pragma unroll
@@ -156,6 +175,13 @@ __device__ __forceinline__ void fill_rows(const DevProblem &P, const double *x, 
 #define ARSLAM_PICK_INSTANCE(K, chunked, loss, sized, dist)                                 \
   ((dist) ? ARSLAM_PICK_INSTANCE_D(K, chunked, loss, sized, true)                           \
           : ARSLAM_PICK_INSTANCE_D(K, chunked, loss, sized, false))
+// The "estimate the distortion" switch (a DevCamL beside the problem; always
+// the radial model): k_linearize_est and k_backsub_est, kernels of their own
+// around the same bodies, four instances of each form -- twelve per form in
+// all, and the eight the other problems launch keep their names and code.
+#define ARSLAM_PICK_INSTANCE_EST(K, chunked, loss, sized)                                   \
+  ((sized) ? ((loss) ? K<chunked, true, true> : K<chunked, false, true>)                    \
+           : ((loss) ? K<chunked, true, false> : K<chunked, false, false>))
 template <bool kChunked>
 __device__ __forceinline__ int chunk_capture(const DevProblem &P, int &k) {
   const int c = kChunked ? P.chunk_caps[blockIdx.x] : (int)blockIdx.x;

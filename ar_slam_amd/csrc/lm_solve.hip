@@ -89,7 +89,7 @@ void arslam_lm::linearize_launch() {
   // page-locked h_lin (no copy launch); several: h_lin is copied after the exchanges
   const bool direct = !multi();
   timers[PH_LIN].start(stream);
-  arslam::launch_linearize(P, x, d_g.p, d_colnorm.p, d_obs_tg.p, d_parts.p, stream);
+  arslam::launch_linearize(P, x, d_g.p, d_colnorm.p, d_obs_tg.p, d_parts.p, stream, cl());
   // (several ranks: this rank's partial cost and fixed cost also saved, the
   // step's reductions reuse d_red, for the scalar exchange; the LM diagonal
   // from the partial sums is final for the capture slots and this rank's own
@@ -100,15 +100,17 @@ void arslam_lm::linearize_launch() {
   if (multi()) lin_xpending = true;
   const arslam::LmDiagArgs ld{n, d_scale.p, d_colnorm.p, opt.min_lm_diagonal, opt.max_lm_diagonal, d_diag.p};
   lin_seq = direct ? next_seq(h_lin.p + 16 + arslam::kHostSeq) : 0.0;
+  // (l1, l2 estimated: their gradient and column norms from d_lparts first)
   arslam::launch_slot_norms(P, d_red.p, d_g.p, d_colnorm.p, x, d_norms_p, stream, direct ? h_lin.p + 16 : nullptr,
-                            diag_in_lin ? &ld : nullptr, lin_seq);
+                            diag_in_lin ? &ld : nullptr, lin_seq, cl());
   timers[PH_LIN].stop(stream);
 }
 
 // (several ranks) the norms and the LM diagonal again, from the exchanged sums
 void arslam_lm::lin_norms() {
   const arslam::LmDiagArgs ld{n, d_scale.p, d_colnorm.p, opt.min_lm_diagonal, opt.max_lm_diagonal, d_diag.p};
-  arslam::launch_slot_norms(P, d_red.p, d_g.p, d_colnorm.p, x, d_norms_p, stream, nullptr, diag_in_lin ? &ld : nullptr);
+  arslam::launch_slot_norms(P, d_red.p, d_g.p, d_colnorm.p, x, d_norms_p, stream, nullptr, diag_in_lin ? &ld : nullptr,
+                            0.0, cl());
   lin_xpending = false;
   norms_pending = true;   // capture slots and the held f-side slots: combined with the next scalars
 }
@@ -425,7 +427,7 @@ void arslam_lm::back_substitute(double radius) {
   // (k_update_f writes every f-side slot of xc, k_backsub every capture
   // slot, then evaluates the candidate's cost per capture: k_cost fused)
   arslam::launch_update_f(P, x, d_scale.p, d_yF.p, xc, d_fparts.p, stream);
-  arslam::launch_backsub(P, x, d_scale.p, d_diag.p, radius, d_yF.p, xc, d_parts.p, stream, has_f, true);
+  arslam::launch_backsub(P, x, d_scale.p, d_diag.p, radius, d_yF.p, xc, d_parts.p, stream, has_f, true, cl());
   timers[PH_BACK].stop(stream);
 }
 
@@ -479,6 +481,8 @@ double arslam_lm::enqueue_step(double radius, bool reuse_diag, int solve_index) 
     const bool fill_first_store = !multi() && opt.factor_executor == 1;
     arslam::launch_schur(P, x, d_scale.p, d_diag.p, radius, Sp, stream, !multi(),
                          fill_first_store ? n_clear : plan.n_tiles, reset_in_schur ? &er : nullptr);
+    // (l1, l2 estimated: their border of the Schur complement, after the gather)
+    if (est_loaded) arslam::launch_schur_cam(P, CL, d_scale.p, d_diag.p, radius, Sp, stream);
     const bool force_indefinite = dbg_indefinite_mask >> std::min(solve_index, 63) & 1ull;
     if (multi()) arslam::launch_prep_reduced(P, d_diag.p, radius, Sp, stream, 0);
     else if (force_indefinite)   // test hook

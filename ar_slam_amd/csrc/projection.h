@@ -179,10 +179,14 @@ __device__ __forceinline__ double residual_row(const AngleAxis &ac, const double
 // zero); only the f column and the 1x3 row P differ from the pinhole's:
 // P = (f / p_z) [A, B, -(A x + B y)], (A, B) = (d + 2 x^2 d', 2 x y d') for a
 // u row and (2 x y d', d + 2 y^2 d') for a v row.
+// Jl (kDist only; the mapper's "estimate the distortion" switch): also the two
+// columns the held model leaves zero, d(u, v)/dl1 = f r2 (x, y) and
+// d(u, v)/dl2 = f r2^2 (x, y), from the values the row already has.
 template <bool kDist = false>
 __device__ __forceinline__ double residual_jacobian_row(const double *cam, const double *cap,
                                                         const double *tag, double half, int corner,
-                                                        int comp, double obs, double J[13]) {
+                                                        int comp, double obs, double J[13],
+                                                        double *Jl = nullptr) {
   const AngleAxis ac = aa_prepare(cap + 3);
   const AngleAxis at = aa_prepare(tag + 3);
   double a[3], p[3];
@@ -200,6 +204,11 @@ __device__ __forceinline__ double residual_jacobian_row(const double *cam, const
     P[0] = fz * ((comp == 0 ? dfac : 0.0) + c2 * x);   // (f / p_z) A
     P[1] = fz * ((comp == 0 ? 0.0 : dfac) + c2 * y);   // (f / p_z) B
     P[2] = -(P[0] * x + P[1] * y);
+    if (Jl) {
+      const double r2 = x * x + y * y, fw = f * w;
+      Jl[0] = fw * r2;
+      Jl[1] = fw * (r2 * r2);
+    }
   }
   double Mc[9];
   aa_matrix(ac, Mc);

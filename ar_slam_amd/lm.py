@@ -54,6 +54,8 @@ EXPORTS = ["arslam_lm_options_init", "arslam_lm_create", "arslam_lm_destroy",
            "arslam_lm_set_camera_model", "arslam_lm_camera_model", "arslam_debug_residual_jacobian_model",
            "arslam_localizer_set_camera_model", "arslam_localizer_camera_model",
            "arslam_slam_set_camera_model", "arslam_slam_camera_model", "arslam_slam_camera_distortion",
+           "arslam_lm_set_estimate_distortion", "arslam_lm_estimate_distortion",
+           "arslam_debug_residual_jacobian_distortion", "arslam_lm_debug_camera_rows",
            "arslam_debug_residual_jacobian", "arslam_debug_dense_llt", "arslam_debug_dense_llt_ex",
            "arslam_debug_tile_llt", "arslam_debug_tile_plan",
            "arslam_debug_angle_axis_rotate", "arslam_debug_selinv", "arslam_lm_debug_force_indefinite",
@@ -92,6 +94,7 @@ LOSS_NONE, LOSS_HUBER, LOSS_SOFT_L_ONE, LOSS_CAUCHY = 0, 1, 2, 3
 DEFAULT_TAG_SIZE = 0.0635   # arslam_lm.h ARSLAM_DEFAULT_TAG_SIZE: the side of a tag, metres
 # the camera model of a handle (arslam_lm.h ARSLAM_CAMERA_*): the pinhole, or the radial model
 # (u, v) = f d (x, y), d = 1 + r2 (l1 + l2 r2), with camera l1, l2 as a known calibration
+# (or, on a mapper handle with set_estimate_distortion, as parameters of the solve)
 CAMERA_PINHOLE, CAMERA_RADIAL = 0, 1
 _ip = C.POINTER(C.c_int)
 _up = C.POINTER(C.c_ubyte)
@@ -294,6 +297,11 @@ def lib():
         L.arslam_slam_set_camera_model.argtypes = [C.c_void_p, C.c_int]
         L.arslam_slam_camera_model.argtypes = [C.c_void_p, _ip]
         L.arslam_slam_camera_distortion.argtypes = [C.c_void_p, _dp]
+    if hasattr(L, "arslam_lm_set_estimate_distortion"):   # (absent from older variant builds under A/B)
+        L.arslam_lm_set_estimate_distortion.argtypes = [C.c_void_p, C.c_int]
+        L.arslam_lm_estimate_distortion.argtypes = [C.c_void_p, _ip]
+        L.arslam_debug_residual_jacobian_distortion.argtypes = [C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
+        L.arslam_lm_debug_camera_rows.argtypes = [C.c_void_p, C.c_double, C.c_long, _dp, _ip]
     L.arslam_lm_set_parameter_block_constant.argtypes = [C.c_void_p, _dp]
     L.arslam_lm_set_parameter_block_variable.argtypes = [C.c_void_p, _dp]
     L.arslam_lm_solve.argtypes = [C.c_void_p, C.POINTER(Summary)]
@@ -475,6 +483,19 @@ class _Handle:
         _check(lib().arslam_lm_camera_model(self._h, C.byref(m)))
         return m.value
 
+    def set_estimate_distortion(self, on=True):
+        """Estimate the distortion (off on creation): under CAMERA_RADIAL, with the camera block not
+        constant, l1 and l2 are parameters like f and camera[1], camera[2] come back estimated;
+        ignored under CAMERA_PINHOLE.  Drops a loaded problem and a kept covariance.  While it is in
+        effect several ranks, ELIM_MIXED on a set that mixes sides and the covariances are refused
+        (UNSUPPORTED)."""
+        _check(lib().arslam_lm_set_estimate_distortion(self._h, int(on)))
+
+    def estimate_distortion(self):
+        v = C.c_int(0)
+        _check(lib().arslam_lm_estimate_distortion(self._h, C.byref(v)))
+        return bool(v.value)
+
     def set_iteration_callback(self, fn):
         """ceres::IterationCallback: fn(iteration dict) -> SOLVER_CONTINUE / SOLVER_ABORT /
         SOLVER_TERMINATE_SUCCESSFULLY (None = continue); fn=None removes it."""
@@ -535,14 +556,17 @@ class ResidentProblem(_Handle):
 
     def __init__(self, camera, cap, tag, obs_cap, obs_tag, corners, camera_const=False,
                  cap_const=None, tag_const=None, comm=None, force_multirank=False, loss=None, obs_loss=None,
-                 tag_size=None, camera_model=None, **opts):
+                 tag_size=None, camera_model=None, estimate_distortion=None, **opts):
         """loss = (kind, a): the robust loss of every observation (the handle's default loss);
         obs_loss = (kinds[n_obs], a[n_obs]): one loss per observation, in observation order;
         tag_size = [n_tag] the tags' sides in metres (a scalar: every tag's); None: DEFAULT_TAG_SIZE;
-        camera_model = CAMERA_PINHOLE / CAMERA_RADIAL (None: the handle's, PINHOLE)."""
+        camera_model = CAMERA_PINHOLE / CAMERA_RADIAL (None: the handle's, PINHOLE);
+        estimate_distortion = True: under CAMERA_RADIAL l1, l2 are estimated (set_estimate_distortion)."""
         super().__init__(**opts)
         if camera_model is not None:
             self.set_camera_model(camera_model)
+        if estimate_distortion is not None:
+            self.set_estimate_distortion(estimate_distortion)
         if force_multirank:
             self.debug_force_multirank(True)
         if comm is not None:
@@ -613,6 +637,18 @@ class ResidentProblem(_Handle):
         _check(lib().arslam_lm_debug_reduced_rows(self._h, cr.ctypes.data_as(_ip), tr.ctypes.data_as(_ip),
                                                   C.byref(cam)))
         return cr[:self.A.s.n_cap], tr[:self.A.s.n_tag], cam.value
+
+    def debug_camera_rows(self, radius):
+        """(rows (3, n_reduced + 1), row_slot (3,)): the camera's reduced rows f, l1, l2 of the
+        assembled reduced system at the loaded point under the given radius, the last column the
+        rows' right-hand side entries (arslam_lm_debug_camera_rows)."""
+        cam = self.debug_reduced_rows()[2]
+        n_cols = cam + 4
+        rows = np.zeros((3, n_cols))
+        slot = np.zeros(3, np.int32)
+        _check(lib().arslam_lm_debug_camera_rows(self._h, float(radius), n_cols, rows.ctypes.data_as(_dp),
+                                                 slot.ctypes.data_as(_ip)))
+        return rows, slot
 
     def owned_captures(self):
         """Indices of the captures this rank owns (every capture on one rank)."""
@@ -789,6 +825,25 @@ def debug_residual_jacobian_model(cam, cap, tag, corners, model, size=None):
                                                       size.ctypes.data_as(_dp) if size is not None else None,
                                                       r.ctypes.data_as(_dp), J.ctypes.data_as(_dp)))
     return r, J
+
+
+def debug_residual_jacobian_distortion(cam, cap, tag, corners, size=None):
+    """The radial model's residuals (n, 8) and the rows' two distortion columns (n, 8, 2),
+    d r / d l1 and d r / d l2 (cam rows = f, l1, l2), for tags of side size[n] (None: default)."""
+    cap = _f64(cap, (-1, 6))
+    n = cap.shape[0]
+    cam = _f64(np.broadcast_to(np.asarray(cam, np.float64), (n, 3)))
+    tag = _f64(tag, (-1, 6))
+    corners = _f64(corners, (-1, 8))
+    if size is not None:
+        size = _f64(np.broadcast_to(np.asarray(size, np.float64), (n,)))
+    r = np.zeros((n, 8))
+    Jl = np.zeros((n, 8, 2))
+    _check(lib().arslam_debug_residual_jacobian_distortion(n, cam.ctypes.data_as(_dp), cap.ctypes.data_as(_dp),
+                                                           tag.ctypes.data_as(_dp), corners.ctypes.data_as(_dp),
+                                                           size.ctypes.data_as(_dp) if size is not None else None,
+                                                           r.ctypes.data_as(_dp), Jl.ctypes.data_as(_dp)))
+    return r, Jl
 
 
 def debug_residual_jacobian_loss(cam, cap, tag, corners, kinds, a):

@@ -14,8 +14,9 @@
  *
  * Each entry point below replaces one of those calls with the same argument
  * meaning: parameter blocks are caller-owned double arrays keyed by their
- * address (camera[3] = f,l1,l2 -- f is estimated; l1 and l2 are held
- * constant and used under ARSLAM_CAMERA_RADIAL only; capture[6] = inv_pose
+ * address (camera[3] = f,l1,l2 -- f is estimated; l1 and l2 are used under
+ * ARSLAM_CAMERA_RADIAL only, held constant there unless
+ * arslam_lm_set_estimate_distortion is on; capture[6] = inv_pose
  * t,w; tag[6] = pose t,w), observations are copied (as the functor copies its ArucoRect,
  * ar_slam_util.cpp:194-196), and results are written back into the caller's
  * arrays when the solve ends (Ceres' default; update_state_every_iteration
@@ -283,9 +284,34 @@ int arslam_lm_get_tag_size(const arslam_lm *h, double *size);
  * path: appends, the three eliminations, losses, sized tags, several ranks,
  * arslam_lm_covariance and arslam_lm_covariance_pairs.  arslam_lm_reset keeps
  * it.  An unknown value returns ARSLAM_E_INVALID_ARG and leaves the handle as
- * it was.  A PINHOLE problem launches the kernels it always launched. */
+ * it was.  A PINHOLE problem launches the kernels it always launched.
+ * (ARSLAM_E_UNSUPPORTED, handle unchanged: RADIAL on a handle of several ranks
+ * whose arslam_lm_set_estimate_distortion is on.) */
 int arslam_lm_set_camera_model(arslam_lm *h, int model);
 int arslam_lm_camera_model(const arslam_lm *h, int *model);
+
+/* "Estimate the distortion", off (0) on creation: a property of the handle,
+ * like the camera model.  It takes effect only for a problem loaded under
+ * ARSLAM_CAMERA_RADIAL; under PINHOLE the two columns are zero and the switch
+ * is ignored.  With it on and the camera block not constant, l1 and l2 are
+ * parameters like f (Ceres' AutoDiffCostFunction<..., 8, 3, 6, 6> with the
+ * distortion in projectCorner): their columns d(u, v)/dl1 = f r^2 (x, y) and
+ * d(u, v)/dl2 = f r^4 (x, y) enter the gradient, the Jacobi scale, the LM
+ * diagonal, the reduced system, the step and its norms, and the caller's
+ * camera[1], camera[2] come back estimated (start them at zero or at a
+ * guess).  A constant camera block holds all three.  Off: the values passed
+ * come back unchanged, by the kernels the handle always launched.
+ * Changing it drops a problem loaded by arslam_lm_load_soa* and any kept
+ * covariance; arslam_lm_reset keeps it.  A value other than 0 or 1 returns
+ * ARSLAM_E_INVALID_ARG and leaves the handle as it was.
+ * Limits while it is in effect, each ARSLAM_E_UNSUPPORTED with the handle
+ * left as it was: several ranks (arslam_lm_set_comm, _set_comm_callback; the
+ * switch itself on a handle that has them); ARSLAM_ELIM_MIXED on a problem
+ * whose e-block set mixes captures and tags (a set that is one whole side is
+ * solved); arslam_lm_covariance* (the covariance eliminations hold l1, l2).
+ * An appended pointer-keyed problem is loaded in full (setup_kind says so). */
+int arslam_lm_set_estimate_distortion(arslam_lm *h, int on);
+int arslam_lm_estimate_distortion(const arslam_lm *h, int *on);
 
 /* arslam_lm_add_residual_block_loss with this block's own tag side (every
  * block of one tag would pass the same; the side belongs to the block, as
@@ -345,7 +371,9 @@ int arslam_lm_set_comm(arslam_lm *h, int rank, int nranks,
  * fn(ctx, buf, count, dtype, op) -- reduce `count` elements of `buf` in
  * place over all ranks, return 0 on success -- and copies the result back.
  * For ranks that share one GPU (RCCL needs one GPU per rank) and for tests.
- * Like arslam_lm_set_comm, this drops a loaded problem (load again). */
+ * Like arslam_lm_set_comm, this drops a loaded problem (load again).  Either
+ * call with more than one rank is ARSLAM_E_UNSUPPORTED, the handle unchanged,
+ * while arslam_lm_set_estimate_distortion is in effect. */
 enum { ARSLAM_DT_F64 = 0, ARSLAM_DT_U8 = 1 };
 enum { ARSLAM_OP_SUM = 0, ARSLAM_OP_MAX = 1 };
 typedef int (*arslam_allreduce_fn)(void *ctx, void *buf, size_t count, int dtype, int op);
@@ -408,7 +436,8 @@ int arslam_lm_set_iteration_callback(arslam_lm *h, arslam_iteration_callback fn,
  * handle, NO_CONVERGENCE included (the linearization at the returned point).
  * ARSLAM_E_STATE when no completed solve precedes the call or the last one
  * ended with rule EVAL_FAILED (both checked before any device call).
- * ARSLAM_E_UNSUPPORTED with several ranks (arslam_lm_debug_force_multirank
+ * ARSLAM_E_UNSUPPORTED while arslam_lm_set_estimate_distortion is in effect
+ * (checked first), with several ranks (arslam_lm_debug_force_multirank
  * included) and when the loaded problem's elimination_used is
  * ARSLAM_ELIM_MIXED; ARSLAM_ELIM_CAPTURES, _TAGS, and _AUTO or _MIXED
  * resolving to one whole side are supported.  The call changes nothing a
@@ -487,8 +516,8 @@ int arslam_lm_covariance_block(arslam_lm *h, const double *block, double *cov, i
  * memory does not grow with n_pairs beyond the 36 values per distinct pair.
  *
  * Preconditions and errors as arslam_lm_covariance: ARSLAM_E_STATE without a
- * completed solve, ARSLAM_E_UNSUPPORTED with several ranks and under
- * ARSLAM_ELIM_MIXED (so not for the SLAM mirror, which runs MIXED and holds no
+ * completed solve, ARSLAM_E_UNSUPPORTED with several ranks, under
+ * arslam_lm_set_estimate_distortion and under ARSLAM_ELIM_MIXED (so not for the SLAM mirror, which runs MIXED and holds no
  * block constant); an earlier arslam_lm_covariance call is neither needed nor
  * in the way.  ARSLAM_E_INVALID_ARG for a bad kind or index or n_pairs < 0;
  * n_pairs == 0 is OK.  Nothing is allocated or launched for this before its

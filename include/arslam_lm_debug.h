@@ -34,6 +34,14 @@ int arslam_debug_residual_jacobian_sized(int n, const double *cam, const double 
 int arslam_debug_residual_jacobian_model(int n, int model, const double *cam, const double *cap, const double *tag,
                                          const double *corners, const double *size, double *r, double *J);
 
+/* The two distortion columns of the radial model's rows, which
+ * arslam_debug_residual_jacobian_model leaves zero (they are held there):
+ * Jl[(8 i + row) * 2 + a] = d r / d l1 (a = 0), d r / d l2 (a = 1) for
+ * observation i; r as arslam_debug_residual_jacobian_model(RADIAL) returns it.
+ * size: null = every tag of ARSLAM_DEFAULT_TAG_SIZE. */
+int arslam_debug_residual_jacobian_distortion(int n, const double *cam, const double *cap, const double *tag,
+                                              const double *corners, const double *size, double *r, double *Jl);
+
 /* The same rows after each observation's robust loss (arslam_lm.h
  * ARSLAM_LOSS_*; kind [n], a [n]), through the device functions k_linearize
  * uses: r [n*8] and J [n*8*15] times sqrt(rho'(s)), s = |r|^2 over the
@@ -131,6 +139,19 @@ int arslam_debug_tile_solve(long n, const double *A, const unsigned char *tile_p
  * the camera is not free.  Each nullable.  The order in which a reference has
  * to eliminate to reproduce arslam_lm_cov_info.min_pivot. */
 int arslam_lm_debug_reduced_rows(arslam_lm *h, int *cap_row, int *tag_row, int *cam_row);
+
+/* The camera's three rows of the assembled reduced system of the loaded
+ * problem (one rank, a free camera) at its loaded point, under the Jacobi
+ * scale of that point and the given trust-region radius: the linearization,
+ * the Schur elimination and the gathers (with arslam_lm_set_estimate_distortion
+ * in effect also the l1, l2 border), and nothing more -- no factorization.
+ * n_cols must be the reduced row count + 1 (camera row + 4).
+ * rows[b * n_cols + col], b = 0 (f), 1 (l1), 2 (l2): the symmetric matrix's
+ * entry against reduced column col < n_cols - 1 (the LM diagonal included),
+ * and at col = n_cols - 1 the row's right-hand side entry.  row_slot[3]: the
+ * rows' parameter slots (0, 1, 2).  Without the switch rows 1, 2 hold their
+ * D^2 alone.  The next solve starts from the loaded state as usual. */
+int arslam_lm_debug_camera_rows(arslam_lm *h, double radius, long n_cols, double *rows, int *row_slot);
 
 /* Host-only symbolic analysis of the reduced system (no device needed): the
  * row layout arslam_lm_load_soa would choose for problem p under the given
