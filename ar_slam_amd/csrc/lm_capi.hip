@@ -215,6 +215,127 @@ int arslam_lm_debug_camera_rows(arslam_lm *h, double radius, long n_cols, double
   });
 }
 
+}  // extern "C"
+
+namespace {
+// the caller's slot (camera 3, captures 6 each, tags 6 each) of each slot of the
+// loaded device problem, -1 for a direct group's copy of its capture; returns
+// the caller's slot count
+long caller_slots(const arslam_lm *h, std::vector<long> &map, int *n_cap, int *n_tag) {
+  const int nc = h->nc, nt = h->nt;
+  map.assign(h->n, -1);
+  for (int j = 0; j < 3; ++j) map[j] = j;
+  const auto put = [&](long dev_block, long caller_block) {
+    for (int j = 0; j < 6; ++j) map[3 + 6 * dev_block + j] = 3 + 6 * caller_block + j;
+  };
+  if (h->elim_used == ARSLAM_ELIM_MIXED) {
+    const arslam::MixedProblem &m = h->mx;
+    *n_cap = m.src_n_cap, *n_tag = m.src_n_tag;
+    for (int g = 0; g < nc; ++g)
+      if (m.kind[g] != arslam::kMixDirect)
+        put(g, m.kind[g] == arslam::kMixTag ? (long)m.src_n_cap + m.group_src[g] : m.group_src[g]);
+    for (int f = 0; f < nt; ++f) put((long)nc + f, m.f_is_cap[f] ? m.f_src[f] : (long)m.src_n_cap + m.f_src[f]);
+  } else if (h->elim_used == ARSLAM_ELIM_TAGS) {   // e-blocks: the tags, f-blocks: the captures
+    *n_cap = nt, *n_tag = nc;
+    for (int t = 0; t < nc; ++t) put(t, (long)nt + t);
+    for (int c = 0; c < nt; ++c) put((long)nc + c, c);
+  } else {
+    *n_cap = nc, *n_tag = nt;
+    for (long b = 0; b < (long)nc + nt; ++b) put(b, b);
+  }
+  return 3 + 6L * (*n_cap + *n_tag);
+}
+}  // namespace
+
+extern "C" {
+
+int arslam_lm_debug_step_stages(arslam_lm *h, double radius, arslam_lm_step_info *info, double *g, double *colnorm,
+                                double *scale, double *diag, double *S, int *row_slot, double *y, double *xc) {
+  if (!h || !info || !(radius > 0.0)) return ARSLAM_E_INVALID_ARG;
+  return arslam::api_guarded([&] {
+    fail_if(!h->loaded || h->multi(), ARSLAM_E_STATE, "step_stages: a problem loaded on one rank");
+    h->ensure_stream();
+    h->cov_invalidate();
+    std::memset(info, 0, sizeof(*info));
+    std::vector<long> map;
+    info->n = caller_slots(h, map, &info->n_cap, &info->n_tag);
+    info->n_reduced = h->has_f ? h->nR : 0;
+    info->n_padded = h->has_f ? h->P.N : 0;
+    info->cam_row = h->has_f ? h->P.cam_row : -1;
+    info->elimination_used = h->elim_used;
+    info->n_groups = h->nc;
+    info->n_direct = h->elim_used == ARSLAM_ELIM_MIXED ? h->mx.n_direct : 0;
+    info->n_big_groups = h->P.n_big_caps;
+    info->n_chunk_groups = h->P.n_chunk_caps;
+    info->n_split_dest = h->has_f ? h->P.n_splits : 0;
+    info->max_contrib = h->has_f ? h->sg.max_contrib : 0;
+    info->n_tiles = h->has_f ? h->plan.n_tiles : 0;
+    info->n_assembled_tiles = h->has_f ? h->plan.n_assembled : 0;
+    // as solve()'s iteration 0 ...
+    h->x = h->d_xa.p;
+    h->xc = h->d_xb.p;
+    h->xbest = h->x;
+    HIP_CHECK(hipMemcpyAsync(h->x, h->u_x0, h->n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    for (auto &t : h->timers) t.on = false;
+    double gmax, gnorm, xnorm;
+    h->linearize(&info->cost, &info->fixed_cost, &gmax, &gnorm, &xnorm);
+    const arslam::LmDiagArgs ld{h->n, h->d_scale.p, h->d_colnorm.p, h->opt.min_lm_diagonal, h->opt.max_lm_diagonal,
+                                h->d_diag.p};
+    arslam::launch_scale(h->P, h->d_colnorm.p, h->opt.jacobi_scaling, h->d_scale.p, h->stream, &ld);
+    // ... and enqueue_step's launches for its first step, every tile cleared,
+    // with the copy of S between the assembly and the factorization
+    arslam::ExecReset er{};
+    const bool reset_in_schur = h->prepare_step(false, &er);
+    DevBuf<double> d_dense;
+    const long N = info->n_padded;
+    if (h->has_f) {
+      arslam::launch_schur(h->P, h->x, h->d_scale.p, h->d_diag.p, radius, h->Sp, h->stream, true, h->plan.n_tiles,
+                           reset_in_schur ? &er : nullptr);
+      if (h->est_loaded) arslam::launch_schur_cam(h->P, h->CL, h->d_scale.p, h->d_diag.p, radius, h->Sp, h->stream);
+      if (S) {
+        d_dense.alloc(N * N);
+        arslam::debug_reduced_dense(h->P, h->Sp, d_dense.p, h->stream);
+      }
+      h->factor_reduced(LONG_MAX, false);
+    }
+    h->back_substitute(radius);
+    const double seq = h->reduce_step_scalars();
+    HIP_CHECK(hipGetLastError());
+    h->flag_sync(h->h_step.p + arslam::kHostSeq, seq);
+    const double *red = h->h_step.p;
+    if (red[arslam::NPART + 3] != 0.0)
+      throw Error(ARSLAM_E_DEVICE, executor_fault_message((int)red[arslam::NPART + 4], h->rank, 0, h->plan, h->stream));
+    info->model_cost_change = red[arslam::P_MODEL];
+    info->candidate_cost = red[arslam::P_COST];
+    info->candidate_fixed_cost = red[arslam::P_FIXED];
+    info->e_step2 = red[arslam::P_STEP2];
+    info->f_step2 = red[arslam::NPART];
+    info->e_step_bad = red[arslam::P_YBAD] != 0.0;
+    info->candidate_bad = red[arslam::P_CBAD] != 0.0;
+    info->f_step_bad = red[arslam::NPART + 1] != 0.0;
+    info->indefinite = red[arslam::NPART + 2] != 0.0;
+    // the device vectors by the caller's slots
+    std::vector<double> tmp(h->n);
+    const struct { const double *src; double *dst; } vecs[5] = {
+        {h->d_g.p, g}, {h->d_colnorm.p, colnorm}, {h->d_scale.p, scale}, {h->d_diag.p, diag}, {h->xc, xc}};
+    for (const auto &v : vecs) {
+      if (!v.dst) continue;
+      HIP_CHECK(hipMemcpyAsync(tmp.data(), v.src, h->n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIP_CHECK(hipStreamSynchronize(h->stream));
+      std::fill(v.dst, v.dst + info->n, 0.0);
+      for (long i = 0; i < h->n; ++i)
+        if (map[i] >= 0) v.dst[map[i]] = tmp[i];
+    }
+    if (h->has_f) {
+      if (S) HIP_CHECK(hipMemcpyAsync(S, d_dense.p, N * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      if (y) HIP_CHECK(hipMemcpyAsync(y, h->d_yF.p, h->nR * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIP_CHECK(hipStreamSynchronize(h->stream));
+      for (long r = 0; r < h->nR && row_slot; ++r)
+        row_slot[r] = h->lay.row_slot[r] < 0 ? -1 : (int)map[h->lay.row_slot[r]];
+    }
+  });
+}
+
 int arslam_lm_add_residual_block(arslam_lm *h, const double corners[8], double *camera,
                                  double *capture, double *tag) {
   if (!h) return ARSLAM_E_INVALID_ARG;
@@ -514,8 +635,18 @@ int arslam_lm_covariance_block_pair(arslam_lm *h, const double *block_a, const d
 int arslam_lm_debug_reduced_rows(arslam_lm *h, int *cap_row, int *tag_row, int *cam_row) {
   if (!h) return ARSLAM_E_INVALID_ARG;
   return arslam::api_guarded([&] {
-    fail_if(!h->loaded || h->multi() || h->elim_used == ARSLAM_ELIM_MIXED, ARSLAM_E_STATE,
-            "reduced_rows: a one-rank problem loaded with capture or tag elimination");
+    fail_if(!h->loaded || h->multi(), ARSLAM_E_STATE, "reduced_rows: a problem loaded on one rank");
+    if (cam_row) *cam_row = h->has_f ? h->P.cam_row : -1;
+    if (h->elim_used == ARSLAM_ELIM_MIXED) {   // the f-blocks are tags and captures; the groups have no rows
+      const arslam::MixedProblem &m = h->mx;
+      for (int c = 0; c < m.src_n_cap && cap_row; ++c) cap_row[c] = -1;
+      for (int t = 0; t < m.src_n_tag && tag_row; ++t) tag_row[t] = -1;
+      for (int f = 0; f < h->nt; ++f) {
+        int *row = m.f_is_cap[f] ? cap_row : tag_row;
+        if (row) row[m.f_src[f]] = (size_t)f < h->lay.tag_row.size() ? h->lay.tag_row[f] : -1;
+      }
+      return;
+    }
     const bool swapped = h->elim_used == ARSLAM_ELIM_TAGS;
     // (the device problem's e-blocks nc, f-blocks nt; no reduced system: the layout has no rows)
     int *e_row = swapped ? tag_row : cap_row, *f_row = swapped ? cap_row : tag_row;

@@ -52,6 +52,9 @@ void launch_schur_cam(const DevProblem &P, const DevCamL &cl, const double *scal
 // debug: reduced rows cam_row .. cam_row + 2 of S against every reduced column
 // and the rhs, out[b (nR + 1) + col] (device memory)
 void debug_cam_rows(const DevProblem &P, double *S, double *out, hipStream_t s);
+// debug: the padded reduced system, N x N with both triangles, 0 where the factor
+// has no tile (device memory)
+void debug_reduced_dense(const DevProblem &P, const double *S, double *out, hipStream_t s);
 
 // ---- lm_step.hip ----
 void launch_backsub(const DevProblem &P, const double *x, const double *scale, const double *diag,

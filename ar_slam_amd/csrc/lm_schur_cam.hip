@@ -239,6 +239,18 @@ __global__ void k_debug_cam_rows(DevProblem P, double *S, double *__restrict__ o
   out[i] = v;
 }
 
+// debug: the whole padded reduced system out of the compact tiles, both
+// triangles: out[i N + j] = element (max(i, j), min(i, j)) of the lower tiles,
+// 0 where the factor has no tile.  A copy and nothing more.
+__global__ void k_debug_reduced_dense(DevProblem P, const double *__restrict__ S, double *__restrict__ out) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= P.N * P.N) return;
+  const long i = e / P.N, j = e - i * P.N;
+  const long r = i > j ? i : j, c = i > j ? j : i;
+  const int id = P.tile_id[(r >> 6) * P.T + (c >> 6)];
+  out[e] = id < 0 ? 0.0 : S[(long)id * 4096 + (r & 63) * 64 + (c & 63)];
+}
+
 }  // namespace
 
 void launch_schur_cam(const DevProblem &P, const DevCamL &cl, const double *scale, const double *diag, double radius,
@@ -253,6 +265,12 @@ void launch_schur_cam(const DevProblem &P, const DevCamL &cl, const double *scal
 void debug_cam_rows(const DevProblem &P, double *S, double *out, hipStream_t s) {
   const long n = 3 * (P.nR + 1);
   hipLaunchKernelGGL(k_debug_cam_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, P, S, out);
+}
+
+void debug_reduced_dense(const DevProblem &P, const double *S, double *out, hipStream_t s) {
+  const long n = P.N * P.N;
+  if (n == 0) return;
+  hipLaunchKernelGGL(k_debug_reduced_dense, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, P, S, out);
 }
 
 }  // namespace arslam

@@ -56,6 +56,7 @@ EXPORTS = ["arslam_lm_options_init", "arslam_lm_create", "arslam_lm_destroy",
            "arslam_slam_set_camera_model", "arslam_slam_camera_model", "arslam_slam_camera_distortion",
            "arslam_lm_set_estimate_distortion", "arslam_lm_estimate_distortion",
            "arslam_debug_residual_jacobian_distortion", "arslam_lm_debug_camera_rows",
+           "arslam_lm_debug_step_stages",
            "arslam_debug_residual_jacobian", "arslam_debug_dense_llt", "arslam_debug_dense_llt_ex",
            "arslam_debug_tile_llt", "arslam_debug_tile_plan",
            "arslam_debug_angle_axis_rotate", "arslam_debug_selinv", "arslam_lm_debug_force_indefinite",
@@ -189,6 +190,21 @@ class CovInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class StepInfo(C.Structure):
+    """arslam_lm_step_info (include/arslam_lm_debug.h)."""
+    _fields_ = [("n", C.c_long), ("n_cap", C.c_int), ("n_tag", C.c_int), ("n_reduced", C.c_long),
+                ("n_padded", C.c_long), ("cam_row", C.c_int), ("elimination_used", C.c_int), ("n_groups", C.c_int),
+                ("n_direct", C.c_int), ("n_big_groups", C.c_int), ("n_chunk_groups", C.c_int),
+                ("n_split_dest", C.c_int), ("max_contrib", C.c_int), ("n_tiles", C.c_long),
+                ("n_assembled_tiles", C.c_long), ("cost", C.c_double), ("fixed_cost", C.c_double),
+                ("model_cost_change", C.c_double), ("candidate_cost", C.c_double),
+                ("candidate_fixed_cost", C.c_double), ("e_step2", C.c_double), ("f_step2", C.c_double),
+                ("e_step_bad", C.c_int), ("candidate_bad", C.c_int), ("f_step_bad", C.c_int), ("indefinite", C.c_int)]
+
+    def to_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class SoaProblem(C.Structure):
     _fields_ = [("n_cap", C.c_int), ("n_tag", C.c_int), ("n_obs", C.c_int),
                 ("camera", _dp), ("cap", _dp), ("tag", _dp),
@@ -302,6 +318,9 @@ def lib():
         L.arslam_lm_estimate_distortion.argtypes = [C.c_void_p, _ip]
         L.arslam_debug_residual_jacobian_distortion.argtypes = [C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
         L.arslam_lm_debug_camera_rows.argtypes = [C.c_void_p, C.c_double, C.c_long, _dp, _ip]
+    if hasattr(L, "arslam_lm_debug_step_stages"):   # (likewise)
+        L.arslam_lm_debug_step_stages.argtypes = [C.c_void_p, C.c_double, C.POINTER(StepInfo), _dp, _dp, _dp, _dp, _dp,
+                                                  _ip, _dp, _dp]
     L.arslam_lm_set_parameter_block_constant.argtypes = [C.c_void_p, _dp]
     L.arslam_lm_set_parameter_block_variable.argtypes = [C.c_void_p, _dp]
     L.arslam_lm_solve.argtypes = [C.c_void_p, C.POINTER(Summary)]
@@ -523,6 +542,35 @@ class _Handle:
         """Test hook: the multi-rank path (split, two-phase factorization, every collective) with
         one rank, so set_comm(0, 1, uid) makes a one-rank RCCL communicator on a one-GPU box."""
         _check(lib().arslam_lm_debug_force_multirank(self._h, 1 if on else 0))
+
+    def debug_step_stages(self, radius):
+        """Every stage of one LM step of the loaded problem at its loaded point under `radius`
+        (arslam_lm_debug_step_stages): a dict of the arslam_lm_step_info fields and
+        ``g``, ``colnorm``, ``scale``, ``diag``, ``xc`` (n,) by the caller's slots; ``S``
+        (n_reduced, n_reduced) the assembled system before the factorization, ``rhs``
+        (n_reduced,) its right-hand side row, ``S_padded`` (n_padded, n_padded) every row of the
+        padded system; ``row_slot`` (n_reduced,) the caller's slot of a row, -1 for padding; ``y``
+        (n_reduced,) the reduced solution."""
+        info = StepInfo()
+        L = lib()
+        _check(L.arslam_lm_debug_step_stages(self._h, float(radius), C.byref(info), None, None, None, None, None,
+                                             None, None, None))
+        n, nR, N = info.n, info.n_reduced, info.n_padded
+        v = {k: np.zeros(n) for k in ("g", "colnorm", "scale", "diag", "xc")}
+        S = np.zeros((max(N, 1), max(N, 1)))
+        slot = np.zeros(max(nR, 1), np.int32)
+        y = np.zeros(max(nR, 1))
+        _check(L.arslam_lm_debug_step_stages(self._h, float(radius), C.byref(info), v["g"].ctypes.data_as(_dp),
+                                             v["colnorm"].ctypes.data_as(_dp), v["scale"].ctypes.data_as(_dp),
+                                             v["diag"].ctypes.data_as(_dp), S.ctypes.data_as(_dp),
+                                             slot.ctypes.data_as(_ip), y.ctypes.data_as(_dp),
+                                             v["xc"].ctypes.data_as(_dp)))
+        out = info.to_dict()
+        out.update(v)
+        S = S[:N, :N]
+        out.update(S_padded=S, S=S[:nR, :nR].copy(), rhs=S[nR, :nR].copy() if N else np.zeros(0),
+                   row_slot=slot[:nR], y=y[:nR])
+        return out
 
     def set_comm(self, rank, nranks, uid):
         """Join the ranks' exchange: ``uid`` is an RCCL unique id (bytes, one GPU per

@@ -132,10 +132,10 @@ int arslam_debug_selinv(long n, const double *A, const unsigned char *tile_patte
 int arslam_debug_tile_solve(long n, const double *A, const unsigned char *tile_pattern, int nrhs, const double *B,
                             double *X_out, int *info);
 
-/* The loaded problem's reduced rows, by the caller's blocks (one rank, capture
- * or tag elimination): cap_row [n_cap], tag_row [n_tag] = the first of the
- * block's 6 rows in the reduced system, -1 for a block that is eliminated,
- * constant or unused; *cam_row = the focal's row (l1, l2 follow it), -1 if
+/* The loaded problem's reduced rows, by the caller's blocks (one rank; any
+ * elimination, a mixed set included): cap_row [n_cap], tag_row [n_tag] = the
+ * first of the block's 6 rows in the reduced system, -1 for a block that is
+ * eliminated, constant or unused (eliminated: free and -1); *cam_row = the focal's row (l1, l2 follow it), -1 if
  * the camera is not free.  Each nullable.  The order in which a reference has
  * to eliminate to reproduce arslam_lm_cov_info.min_pivot. */
 int arslam_lm_debug_reduced_rows(arslam_lm *h, int *cap_row, int *tag_row, int *cam_row);
@@ -152,6 +152,45 @@ int arslam_lm_debug_reduced_rows(arslam_lm *h, int *cap_row, int *tag_row, int *
  * rows' parameter slots (0, 1, 2).  Without the switch rows 1, 2 hold their
  * D^2 alone.  The next solve starts from the loaded state as usual. */
 int arslam_lm_debug_camera_rows(arslam_lm *h, double radius, long n_cols, double *rows, int *row_slot);
+
+/* Every stage of one LM step of the loaded problem (one rank; SoA or
+ * pointer-keyed; any elimination; with or without a free camera or a reduced
+ * system) at its loaded point under the given radius, as solve()'s first step
+ * launches them: the linearization, the Jacobi scale with the LM diagonal, the
+ * Schur elimination and its gathers in prep mode over a system cleared in
+ * every tile, the l1, l2 border where it is estimated, the factorization, the
+ * backward solve, the back-substitution with the fused candidate cost, and the
+ * reduction of the step's scalars.  Every array is nullable.
+ * g, colnorm, scale, diag, xc [info.n]: by parameter slot in the caller's order
+ *   (camera 3, captures 6 each, tags 6 each), whichever side is eliminated;
+ *   xc is the candidate x + step.
+ * S [info.n_padded^2]: the assembled system before the factorization, row
+ *   major, both triangles, every row of the padded system (row n_reduced: the
+ *   right-hand side and its pivot; the padding rows), 0 where the factor has
+ *   no tile.  row_slot [info.n_reduced]: the caller's slot of a reduced row,
+ *   -1 for an alignment padding row.  y [info.n_reduced]: the reduced solution.
+ * Sizes first: call with every array null.  The next solve starts from the
+ * loaded state and gives the bits it gives without this call. */
+typedef struct {
+  long n;                 /* the caller's parameter slots, 3 + 6 n_cap + 6 n_tag */
+  int n_cap, n_tag;       /* the caller's blocks */
+  long n_reduced;         /* rows of the reduced system, alignment padding included; 0: none */
+  long n_padded;          /* tiles per side * 64 (> n_reduced); 0: none */
+  int cam_row;            /* -1: the camera is not free */
+  int elimination_used;   /* ARSLAM_ELIM_CAPTURES, _TAGS or _MIXED */
+  int n_groups;           /* eliminated blocks + direct groups (the e-side of the device problem) */
+  int n_direct;           /* direct groups of a mixed set */
+  int n_big_groups;       /* groups on the second Schur launch (more than 10 distinct f-blocks) */
+  int n_chunk_groups;     /* groups of more than 8 observations (the chunked instances) */
+  int n_split_dest;       /* gather destinations summed in pieces */
+  int max_contrib;        /* most contributions of one gather destination */
+  long n_tiles, n_assembled_tiles;   /* tiles of the factor; of them assembled at the load */
+  double cost, fixed_cost;           /* the linearization's */
+  double model_cost_change, candidate_cost, candidate_fixed_cost, e_step2, f_step2;
+  int e_step_bad, candidate_bad, f_step_bad, indefinite;   /* the step's flags */
+} arslam_lm_step_info;
+int arslam_lm_debug_step_stages(arslam_lm *h, double radius, arslam_lm_step_info *info, double *g, double *colnorm,
+                                double *scale, double *diag, double *S, int *row_slot, double *y, double *xc);
 
 /* Host-only symbolic analysis of the reduced system (no device needed): the
  * row layout arslam_lm_load_soa would choose for problem p under the given
