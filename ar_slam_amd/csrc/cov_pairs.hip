@@ -33,8 +33,7 @@
 // folds into the factor (pivot 1e300) and the rows after it identity padding;
 // rows >= nR of every factor tile and rows and columns >= nR of L_kk^{-1} are
 // read as zero, so those rows contribute exactly nothing and stay zero in X.
-#include "llt_tile.h"
-#include "lm_cov.h"
+#include "cov_device.h"
 
 #include <algorithm>
 #include <stdexcept>
@@ -167,35 +166,6 @@ __global__ __launch_bounds__(256) void k_tsolve_bwd(const double *__restrict__ S
 // Right-hand sides and blocks (arslam_lm_covariance_pairs).  A block of the
 // device problem is {role, index}: kCovFocal, kCovF (f-block = reduced side),
 // kCovE (e-block = eliminated side).
-
-// element (r, c) of panel column block `slot` of a batch of panels
-__device__ __forceinline__ double *panel_elem(double *B, int T, int slot, long r, int c) {
-  return B + ((long)(slot / kCovPanelBlocks) * T + (r >> 6)) * (T64 * T64) + (r & 63) * T64 +
-         (slot % kCovPanelBlocks) * 6 + c;
-}
-
-// Ri = R^{-1} of e-block c's 6x6 upper-triangular R (k_cov_schur), one lane;
-// false when R is singular or not finite
-__device__ bool r_inverse(const double *__restrict__ Rq, double *Ri) {
-  bool good = true;
-  for (int a = 0; a < 6; ++a) good = good && Rq[7 * a] > 0.0 && Rq[7 * a] < INFINITY;
-  for (int col = 0; col < 6; ++col)
-    for (int a = 5; a >= 0; --a) {
-      double v = a == col ? 1.0 : 0.0;
-      for (int p = a + 1; p <= col; ++p) v -= Rq[6 * a + p] * Ri[6 * p + col];
-      Ri[6 * a + col] = a <= col ? v / Rq[7 * a] : 0.0;
-      good = good && isfinite(Ri[6 * a + col]);
-    }
-  return good;
-}
-
-// reduced row of local column col of e-block c (the focal, then 6 per distinct
-// f-block); -1: a constant f-block's, or no free focal
-__device__ __forceinline__ long local_col_row(const DevProblem &P, int b0, int col) {
-  if (col == 0) return P.cam_row;
-  const int r = P.tag_row[P.blk_tag[b0 + (col - 1) / 6]];
-  return r < 0 ? -1 : r + (col - 1) % 6;
-}
 
 // One wavefront per distinct right-hand block, into its 6 columns of the
 // (zeroed) panels: unit columns at the reduced rows of the focal (one column)

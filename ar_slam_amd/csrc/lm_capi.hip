@@ -215,6 +215,28 @@ int arslam_lm_debug_camera_rows(arslam_lm *h, double radius, long n_cols, double
   });
 }
 
+int arslam_lm_debug_cov_camera_rows(arslam_lm *h, long n_cols, double *rows, int *row_slot) {
+  if (!h || !rows) return ARSLAM_E_INVALID_ARG;
+  return arslam::api_guarded([&] {
+    h->cov_check_state("cov_camera_rows", true);
+    fail_if(!h->has_f || h->P.cam_row < 0, ARSLAM_E_STATE, "cov_camera_rows: a problem loaded with a free camera");
+    fail_if(n_cols != h->nR + 1, ARSLAM_E_INVALID_ARG, "cov_camera_rows: n_cols must be the reduced row count + 1");
+    h->cov_valid = false;
+    // the covariance's linearization, elimination, border and gathers, the rows read before the factorization
+    arslam_lm::CovFactor cf;
+    h->cov_factor(cf, true, true);
+    fail_if(!cf.factored, ARSLAM_E_STATE, "cov_camera_rows: the problem has no gauge anchor");
+    DevBuf<double> d_out;
+    d_out.alloc(3 * n_cols);
+    arslam::debug_cam_rows(h->P, h->Sp, d_out.p, h->stream);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(rows, d_out.p, 3 * n_cols * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (row_slot)
+      for (int b = 0; b < 3; ++b) row_slot[b] = h->lay.row_slot[h->P.cam_row + b];
+  });
+}
+
 }  // extern "C"
 
 namespace {
@@ -565,7 +587,7 @@ int arslam_lm_covariance_block(arslam_lm *h, const double *block, double *cov, i
             "parameter block is not part of the problem");
     fail_if(!h->pk_loaded || h->pk_dirty, ARSLAM_E_STATE,
             "covariance_block: no completed arslam_lm_solve of the problem as it stands");
-    if (!h->cov_valid) h->covariance();
+    if (!h->cov_valid || h->cov_from_lens) h->covariance();   // (a kept _lens result is not this form's)
     if (key == h->camera_ptr) {
       std::fill(cov, cov + 9, 0.0);
       cov[0] = h->cov_var_f;
@@ -628,6 +650,87 @@ int arslam_lm_covariance_block_pair(arslam_lm *h, const double *block_a, const d
       else if (ra == 6 && cb == 3) for (int r = 0; r < 6; ++r) cov[3 * r] = c[r];   // column 0: cov(a, f)
       else cov[0] = c[0];
     }
+    if (status) *status = st;
+  });
+}
+
+int arslam_lm_covariance_lens(arslam_lm *h, double *cov_cap, double *cov_tag, double *cov_cam, int *cap_status,
+                              int *tag_status, int *cam_status, arslam_lm_cov_info *info) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return arslam::api_guarded([&] {
+    h->covariance(true);
+    if (cov_cap && !h->cov_cap.empty()) std::memcpy(cov_cap, h->cov_cap.data(), h->cov_cap.size() * sizeof(double));
+    if (cov_tag && !h->cov_tag.empty()) std::memcpy(cov_tag, h->cov_tag.data(), h->cov_tag.size() * sizeof(double));
+    if (cov_cam) std::memcpy(cov_cam, h->cov_cam, 9 * sizeof(double));
+    if (cap_status && !h->cov_cap_status.empty())
+      std::memcpy(cap_status, h->cov_cap_status.data(), h->cov_cap_status.size() * sizeof(int));
+    if (tag_status && !h->cov_tag_status.empty())
+      std::memcpy(tag_status, h->cov_tag_status.data(), h->cov_tag_status.size() * sizeof(int));
+    if (cam_status) *cam_status = h->cov_cam_status;
+    if (info) *info = h->cov_info;
+  });
+}
+
+int arslam_lm_covariance_block_lens(arslam_lm *h, const double *block, double *cov, int *status) {
+  if (!h || !block || !cov) return ARSLAM_E_INVALID_ARG;
+  return arslam::api_guarded([&] {
+    double *key = const_cast<double *>(block);
+    const auto ci = h->cap_of.find(key);
+    const auto ti = h->tag_of.find(key);
+    fail_if(key != h->camera_ptr && ci == h->cap_of.end() && ti == h->tag_of.end(), ARSLAM_E_INVALID_ARG,
+            "parameter block is not part of the problem");
+    fail_if(!h->pk_loaded || h->pk_dirty, ARSLAM_E_STATE,
+            "covariance_block_lens: no completed arslam_lm_solve of the problem as it stands");
+    if (!h->cov_valid || !h->cov_from_lens) h->covariance(true);
+    if (key == h->camera_ptr) {
+      std::memcpy(cov, h->cov_cam, 9 * sizeof(double));
+      if (status) *status = h->cov_cam_status;
+      return;
+    }
+    const bool is_cap = ci != h->cap_of.end();
+    const int i = is_cap ? ci->second : ti->second;
+    const std::vector<double> &c = is_cap ? h->cov_cap : h->cov_tag;
+    const std::vector<int> &st = is_cap ? h->cov_cap_status : h->cov_tag_status;
+    fail_if((size_t)i >= st.size(), ARSLAM_E_STATE, "covariance_block_lens: the block is not part of the solved problem");
+    std::memcpy(cov, c.data() + 36L * i, 36 * sizeof(double));
+    if (status) *status = st[i];
+  });
+}
+
+int arslam_lm_covariance_pairs_lens(arslam_lm *h, const arslam_lm_cov_pair *pairs, int n_pairs, double *cov,
+                                    int *status, arslam_lm_cov_info *info) {
+  if (!h || n_pairs < 0 || (n_pairs > 0 && (!pairs || !cov))) return ARSLAM_E_INVALID_ARG;
+  return arslam::api_guarded([&] { h->covariance_pairs(pairs, n_pairs, cov, status, info, true); });
+}
+
+int arslam_lm_covariance_block_pair_lens(arslam_lm *h, const double *block_a, const double *block_b, double *cov,
+                                         int *status) {
+  if (!h || !block_a || !block_b || !cov) return ARSLAM_E_INVALID_ARG;
+  return arslam::api_guarded([&] {
+    arslam_lm_cov_pair pr{};
+    int size[2] = {6, 6};
+    const double *blocks[2] = {block_a, block_b};
+    for (int s = 0; s < 2; ++s) {
+      double *key = const_cast<double *>(blocks[s]);
+      const auto ci = h->cap_of.find(key);
+      const auto ti = h->tag_of.find(key);
+      fail_if(key != h->camera_ptr && ci == h->cap_of.end() && ti == h->tag_of.end(), ARSLAM_E_INVALID_ARG,
+              "parameter block is not part of the problem");
+      const int kind = key == h->camera_ptr ? ARSLAM_BLOCK_CAMERA : ci != h->cap_of.end() ? ARSLAM_BLOCK_CAPTURE : ARSLAM_BLOCK_TAG;
+      const int index = kind == ARSLAM_BLOCK_CAMERA ? 0 : kind == ARSLAM_BLOCK_CAPTURE ? ci->second : ti->second;
+      if (kind == ARSLAM_BLOCK_CAMERA) size[s] = 3;
+      (s == 0 ? pr.kind_a : pr.kind_b) = kind;
+      (s == 0 ? pr.index_a : pr.index_b) = index;
+    }
+    fail_if(!h->pk_loaded || h->pk_dirty, ARSLAM_E_STATE,
+            "covariance_block_pair_lens: no completed arslam_lm_solve of the problem as it stands");
+    double c[36];
+    int st = ARSLAM_COV_UNAVAILABLE;
+    h->covariance_pairs(&pr, 1, c, &st, nullptr, true);
+    // Ceres' shapes: rows of a by columns of b, the camera block 3 wide -- the top-left of the 6x6
+    const int ra = size[0], cb = size[1];
+    for (int r = 0; r < ra; ++r)
+      for (int q = 0; q < cb; ++q) cov[cb * r + q] = st == ARSLAM_COV_OK ? c[6 * r + q] : -1.0;
     if (status) *status = st;
   });
 }

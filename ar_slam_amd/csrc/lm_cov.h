@@ -1,8 +1,9 @@
 // lm_cov.h -- the covariance of the LM solver on the device: the selected
 // inverse of the factored reduced system and the marginal blocks (selinv.hip),
-// and the multi-right-hand-side tile solve and the cross-covariance blocks
-// (cov_pairs.hip).  Called by lm_covariance.hip, and by debug_tiles.hip for
-// the component tests.
+// the multi-right-hand-side tile solve and the cross-covariance blocks
+// (cov_pairs.hip), and the border and block kernels of a problem whose l1, l2
+// are estimated (cov_lens.hip).  Called by lm_covariance.hip, and by
+// debug_tiles.hip for the component tests.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
@@ -104,5 +105,29 @@ struct CovPairTask {
 void launch_cov_pair_blocks(const DevProblem &P, const double *X, const double *scale, const double *Gb,
                             const double *Rb, const CovPairTask *tasks, int n_tasks, double *out, int *status,
                             const int *flag, hipStream_t s);
+
+// ---- cov_lens.hip ----
+// The same with the camera's l1, l2 estimated (DevCamL: the loaded problem's
+// switch), the camera block three wide.
+// After launch_cov_schur on the same stream: G_la = Q'L_a of every e-block into
+// Glb (12 nc doubles; a = l1, l2 from cl.jrows_l) and the e-blocks' borders
+// L_a'F_q - G_la'G_q into cl.cam_slab in k_schur_cam's layout;
+// launch_schur_cam_gather then assembles reduced rows cam_row + 1, cam_row + 2
+// (after launch_schur_gather; a diagonal of 0 on slots 1, 2 adds nothing there).
+void launch_cov_schur_cam(const DevProblem &P, const DevCamL &cl, const double *scale, const double *Qb,
+                          const double *Gb, double *Glb, hipStream_t s);
+// launch_cov_blocks with the e-blocks' l columns (Glb) and cov_cam [9], the
+// marginal of [f, l1, l2] (row-major, exactly symmetric), in place of var_f.
+void launch_cov_blocks_lens(const DevProblem &P, const double *Z, const double *scale, const double *Gb,
+                            const double *Rb, const double *Glb, double *cov_e, int *status_e, double *cov_f,
+                            double *cov_cam, const int *flag, hipStream_t s);
+// launch_cov_pair_rhs / launch_cov_pair_blocks with the camera (kCovFocal)
+// three wide: three unit columns as a right-hand side, three rows as a, three
+// columns as b, the rest 0.
+void launch_cov_pair_rhs_lens(const DevProblem &P, const double *Gb, const double *Rb, const double *Glb,
+                              const int2 *rhs, int n_rhs, double *B, hipStream_t s);
+void launch_cov_pair_blocks_lens(const DevProblem &P, const double *X, const double *scale, const double *Gb,
+                                 const double *Rb, const double *Glb, const CovPairTask *tasks, int n_tasks,
+                                 double *out, int *status, const int *flag, hipStream_t s);
 
 }  // namespace arslam

@@ -3,10 +3,10 @@
 
 #include <map>
 
-void arslam_lm::cov_check_state(const char *who) const {
+void arslam_lm::cov_check_state(const char *who, bool lens) const {
   const std::string w(who);
-  fail_if(est_active(), ARSLAM_E_UNSUPPORTED,
-          w + ": not supported while estimate_distortion is on (the covariance eliminations hold l1, l2)");
+  fail_if(!lens && est_active(), ARSLAM_E_UNSUPPORTED,
+          w + ": not supported while estimate_distortion is on (its camera output is one scalar: use the _lens form)");
   fail_if(!loaded || solve_state == 0, ARSLAM_E_STATE, w + ": no completed solve of the loaded problem");
   fail_if(solve_state == 2, ARSLAM_E_STATE, w + ": the last solve ended with rule EVAL_FAILED");
   fail_if(multi(), ARSLAM_E_UNSUPPORTED, w + ": single-rank only");
@@ -18,9 +18,13 @@ void arslam_lm::cov_check_state(const char *who) const {
 // the last solve returned, the reduced system without the LM diagonal (its own
 // elimination kernel, the LM step's gather) and its factorization as in an LM
 // step.  Everything it writes on the device is scratch the next solve rebuilds
-// from the loaded state.
-void arslam_lm::cov_factor(CovFactor &cf) {
+// from the loaded state.  lens (the _lens entry points) on a problem whose l1, l2
+// are live: they are rows of H like f -- k_cov_schur_cam's border and the LM
+// step's border gather put them into the reduced system (cov_lens.hip).
+// assemble_only (arslam_lm_debug_cov_camera_rows): stop before the factorization.
+void arslam_lm::cov_factor(CovFactor &cf, bool lens, bool assemble_only) {
   ensure_stream();
+  cf.live = lens && est_loaded;
   // the device problem's structure (its host copy is not kept after a load)
   std::vector<int> &h_cs = cf.cap_start;
   h_cs.assign(nc + 1, 0);
@@ -80,16 +84,21 @@ void arslam_lm::cov_factor(CovFactor &cf) {
   // equations' F'F - W'U^-1 W loses cond(U) digits, too many for a
   // covariance), gathered as an LM step's is, then factored.  The gather's
   // diagonal is 0 on the free slots; the camera's l1 / l2 rows, which hold
-  // nothing else, get the pivot 1
+  // nothing else, get the pivot 1 -- unless they are live: then the border
+  // gather writes those rows, and adds this 0
   std::vector<double> dg(n);
   for (long i = 0; i < n; ++i) dg[i] = slot_free[i] ? 0.0 : 1.0;
-  dg[1] = dg[2] = 1.0;
+  dg[1] = dg[2] = cf.live ? 0.0 : 1.0;
   d_cov_diag.alloc(n);
   HIP_CHECK(hipMemcpyAsync(d_cov_diag.p, dg.data(), n * sizeof(double), hipMemcpyHostToDevice, stream));
   d_cov_Q.alloc(std::max(48L * nb, 1L));
   d_cov_Y.alloc(std::max(6L * (nc + 6L * n_blk), 1L));
   d_cov_R.alloc(std::max(36L * nc, 1L));
   arslam::launch_cov_schur(P, d_scale.p, d_cov_Q.p, d_cov_Y.p, d_cov_R.p, has_f, stream);
+  if (cf.live) {
+    d_cov_Gl.alloc(12L * std::max(nc, 1));
+    arslam::launch_cov_schur_cam(P, CL, d_scale.p, d_cov_Q.p, d_cov_Y.p, d_cov_Gl.p, stream);
+  }
   if (has_f) {
     const bool dag = opt.factor_executor == 1;
     if (dag) {
@@ -100,7 +109,8 @@ void arslam_lm::cov_factor(CovFactor &cf) {
     }
     arslam::launch_zero_tiles(plan, Sp, stream);
     arslam::launch_schur_gather(P, d_cov_diag.p, 1.0, Sp, stream);
-    factor_reduced(LONG_MAX, false);   // (every tile was cleared: no first-update store)
+    if (cf.live) arslam::launch_schur_cam_gather(P, CL, d_cov_diag.p, 1.0, Sp, stream);
+    if (!assemble_only) factor_reduced(LONG_MAX, false);   // (every tile was cleared: no first-update store)
     info.n_factor_products = plan.total_upd_tiles + (long)plan.h_gather.size() + plan.T;
   } else {
     HIP_CHECK(hipMemsetAsync(d_flag.p, 0, sizeof(int), stream));
@@ -111,7 +121,8 @@ void arslam_lm::cov_factor(CovFactor &cf) {
 
 // The calls' one stream sync, behind everything the caller enqueued after
 // cov_factor; then the numeric test: no failed pivot, and the smallest squared
-// pivot of the real rows (not l1 / l2, the padding or the rhs) at least 1e-14.
+// pivot of the real rows (not the padding or the rhs, and l1 / l2 only when
+// they are live) at least 1e-14.
 void arslam_lm::cov_numeric_test(CovFactor &cf) {
   arslam_lm_cov_info &info = cf.info;
   if (cf.factored) {
@@ -132,7 +143,7 @@ void arslam_lm::cov_numeric_test(CovFactor &cf) {
       bool first = true;
       for (long r = 0; r < (has_f ? nR : 0); ++r) {
         const int sl = lay.row_slot[r];
-        if (sl < 0 || sl == 1 || sl == 2) continue;
+        if (sl < 0 || (!cf.live && (sl == 1 || sl == 2))) continue;
         const double l = ld[(size_t)(r >> 6) * 4096 + (r & 63) * 65];
         const double p2 = l * l;
         if (first || !(p2 >= mp)) mp = p2;   // (a NaN pivot stays)
@@ -148,14 +159,17 @@ void arslam_lm::cov_numeric_test(CovFactor &cf) {
 // Marginal covariances at the point the last solve returned (arslam_lm.h):
 // cov_factor, the selected inverse over the factor's tiles and the two block
 // kernels (selinv.hip).  The result is kept on the host in the caller's block
-// order.
-void arslam_lm::covariance() {
-  cov_check_state("covariance");
+// order.  lens: arslam_lm_covariance_lens -- with l1, l2 live the lens
+// instances of the block kernels and the camera's 3x3; held, the same launches
+// as without it, var(f) at [0] of the 3x3.
+void arslam_lm::covariance(bool lens) {
+  cov_check_state(lens ? "covariance_lens" : "covariance", lens);
   cov_valid = false;
   CovFactor cf;
-  cov_factor(cf);
+  cov_factor(cf, lens);
   arslam_lm_cov_info &info = cf.info;
-  std::vector<double> out(36L * nc + 36L * nt + 1, -1.0);
+  const int n_cam = cf.live ? 9 : 1;   // the tail of d_cov_out: the camera's 3x3, or var(f)
+  std::vector<double> out(36L * nc + 36L * nt + n_cam, -1.0);
   std::vector<int> st_e(std::max(nc, 1), 0);
   if (cf.factored) {
     // 3. the selected inverse on the factor's tiles
@@ -172,8 +186,13 @@ void arslam_lm::covariance() {
     // 4. the blocks
     d_cov_out.alloc(out.size());
     d_cov_status.alloc(std::max(nc, 1));
-    arslam::launch_cov_blocks(P, has_f ? d_cov_Z.p : nullptr, d_scale.p, d_cov_Y.p, d_cov_R.p, d_cov_out.p, d_cov_status.p,
-                              d_cov_out.p + 36L * nc, d_cov_out.p + 36L * nc + 36L * nt, d_flag.p, stream);
+    if (cf.live)
+      arslam::launch_cov_blocks_lens(P, d_cov_Z.p, d_scale.p, d_cov_Y.p, d_cov_R.p, d_cov_Gl.p, d_cov_out.p,
+                                     d_cov_status.p, d_cov_out.p + 36L * nc, d_cov_out.p + 36L * nc + 36L * nt, d_flag.p,
+                                     stream);
+    else
+      arslam::launch_cov_blocks(P, has_f ? d_cov_Z.p : nullptr, d_scale.p, d_cov_Y.p, d_cov_R.p, d_cov_out.p, d_cov_status.p,
+                                d_cov_out.p + 36L * nc, d_cov_out.p + 36L * nc + 36L * nt, d_flag.p, stream);
     HIP_CHECK(hipEventRecord(cov_ev[4], stream));
     HIP_CHECK(hipMemcpyAsync(out.data(), d_cov_out.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
     if (nc) HIP_CHECK(hipMemcpyAsync(st_e.data(), d_cov_status.p, nc * sizeof(int), hipMemcpyDeviceToHost, stream));
@@ -200,7 +219,20 @@ void arslam_lm::covariance() {
   cov_tag = swapped ? ce : cf_;
   cov_cap_status = swapped ? sf : se;
   cov_tag_status = swapped ? se : sf;
-  cov_var_f = out.back();
+  // the camera: its 3x3 over [f, l1, l2] (held l1, l2: their rows and columns 0), and var(f)
+  const double *tail = out.data() + 36L * (nc + nt);
+  const bool cam_free = has_f && P.cam_row >= 0;
+  cov_cam_status = !cam_free ? ARSLAM_COV_UNAVAILABLE : deficient ? ARSLAM_COV_RANK_DEFICIENT : ARSLAM_COV_OK;
+  if (cov_cam_status != ARSLAM_COV_OK) {
+    std::fill(cov_cam, cov_cam + 9, -1.0);
+  } else if (cf.live) {
+    std::copy(tail, tail + 9, cov_cam);
+  } else {
+    std::fill(cov_cam, cov_cam + 9, 0.0);
+    cov_cam[0] = tail[0];
+  }
+  cov_var_f = cf.live ? cov_cam[0] : tail[0];
+  cov_from_lens = lens;
   cov_info = info;
   cov_valid = true;
 }
@@ -219,9 +251,12 @@ void arslam_lm::covariance() {
 // their ancestors in the elimination tree and nothing else, and the backward
 // pass computes only the tile rows some pair of the panel reads (and their
 // ancestors): per-panel byte masks, built here.
+// lens: arslam_lm_covariance_pairs_lens -- the camera's block is [f, l1, l2];
+// with l1, l2 live its right-hand side is three unit columns and the lens
+// instances of the two small kernels run (cov_lens.hip).
 void arslam_lm::covariance_pairs(const arslam_lm_cov_pair *pairs, int n_pairs, double *cov, int *status,
-                                 arslam_lm_cov_info *info_out) {
-  cov_check_state("covariance_pairs");
+                                 arslam_lm_cov_info *info_out, bool lens) {
+  cov_check_state(lens ? "covariance_pairs_lens" : "covariance_pairs", lens);
   const bool swapped = elim_used == ARSLAM_ELIM_TAGS;
   const int n_caller_cap = swapped ? nt : nc, n_caller_tag = swapped ? nc : nt;
   // the caller's block in the device problem: {role, idx} (tag elimination: the e-blocks are the caller's tags)
@@ -247,7 +282,8 @@ void arslam_lm::covariance_pairs(const arslam_lm_cov_pair *pairs, int n_pairs, d
     blk[2L * i + 1] = device_block(pairs[i].kind_b, pairs[i].index_b);
   }
   CovFactor cf;
-  cov_factor(cf);
+  cov_factor(cf, lens);
+  const bool live = cf.live;
   const auto available = [&](const Blk &b) {
     if (b.role == arslam::kCovFocal) return has_f && P.cam_row >= 0;
     if (b.role == arslam::kCovF)
@@ -321,12 +357,18 @@ void arslam_lm::covariance_pairs(const arslam_lm_cov_pair *pairs, int n_pairs, d
           arslam::tile_solve_mark(cov_tp, m, r);
           arslam::tile_solve_mark(cov_tp, m, r + 5);
         };
+        // (the camera's three live rows may straddle a tile boundary)
+        const auto cam_rows = [&] {
+          if (P.cam_row < 0) return;
+          arslam::tile_solve_mark(cov_tp, m, P.cam_row);
+          if (live) arslam::tile_solve_mark(cov_tp, m, P.cam_row + 2);
+        };
         if (role == arslam::kCovFocal) {
-          if (P.cam_row >= 0) arslam::tile_solve_mark(cov_tp, m, P.cam_row);
+          cam_rows();
         } else if (role == arslam::kCovF) {
           rows6(f_row(idx));
         } else {
-          if (P.cam_row >= 0) arslam::tile_solve_mark(cov_tp, m, P.cam_row);
+          cam_rows();
           for (int u = h_bs[idx]; u < h_bs[idx + 1]; ++u) rows6(f_row(h_bt[u]));
         }
       };
@@ -357,7 +399,8 @@ void arslam_lm::covariance_pairs(const arslam_lm_cov_pair *pairs, int n_pairs, d
       if (has_f) {
         const size_t m0 = (size_t)bt * batch_panels * T;   // this batch's first panel in the masks
         HIP_CHECK(hipMemsetAsync(d_pair_B.p, 0, panel * np * sizeof(double), stream));
-        arslam::launch_cov_pair_rhs(P, d_cov_Y.p, d_cov_R.p, d_pair_rhs.p + r0, nr, d_pair_B.p, stream);
+        if (live) arslam::launch_cov_pair_rhs_lens(P, d_cov_Y.p, d_cov_R.p, d_cov_Gl.p, d_pair_rhs.p + r0, nr, d_pair_B.p, stream);
+        else arslam::launch_cov_pair_rhs(P, d_cov_Y.p, d_cov_R.p, d_pair_rhs.p + r0, nr, d_pair_B.p, stream);
         HIP_CHECK(hipEventRecord(pair_ev[2 * bt], stream));
         arslam::launch_tile_solve(plan, cov_tp, Sp, nR, d_pair_B.p, np, d_pair_mask.p + m0,
                                   d_pair_mask.p + (size_t)all_panels * T + m0, d_flag.p, stream);
@@ -365,8 +408,12 @@ void arslam_lm::covariance_pairs(const arslam_lm_cov_pair *pairs, int n_pairs, d
         for (int p = 0; p < np; ++p)
           info.n_selinv_products += arslam::tile_solve_products(plan, cov_tp, active + m0 + (size_t)p * T, needed + m0 + (size_t)p * T);
       }
-      arslam::launch_cov_pair_blocks(P, has_f ? d_pair_B.p : nullptr, d_scale.p, d_cov_Y.p, d_cov_R.p, d_pair_tasks.p + t0,
-                                     t1 - t0, d_pair_out.p, d_pair_status.p, d_flag.p, stream);
+      if (live)
+        arslam::launch_cov_pair_blocks_lens(P, d_pair_B.p, d_scale.p, d_cov_Y.p, d_cov_R.p, d_cov_Gl.p, d_pair_tasks.p + t0,
+                                            t1 - t0, d_pair_out.p, d_pair_status.p, d_flag.p, stream);
+      else
+        arslam::launch_cov_pair_blocks(P, has_f ? d_pair_B.p : nullptr, d_scale.p, d_cov_Y.p, d_cov_R.p, d_pair_tasks.p + t0,
+                                       t1 - t0, d_pair_out.p, d_pair_status.p, d_flag.p, stream);
       t0 = t1;
     }
     HIP_CHECK(hipEventRecord(cov_ev[3], stream));
@@ -385,7 +432,9 @@ void arslam_lm::covariance_pairs(const arslam_lm_cov_pair *pairs, int n_pairs, d
     info.t_selinv_ms = solve;
     info.t_blocks_ms = std::max(0.f, all - solve);
   }
-  // the caller's pairs: its (a, b) as computed or transposed; the focal's 6 values first
+  // the caller's pairs: its (a, b) as computed or transposed; the focal's 6 values
+  // first -- the lens form: the camera's rows (as a) or columns (as b), 3 when live
+  const int n_camv = live ? 3 : 1;
   for (int i = 0; i < n_pairs; ++i) {
     double *c = cov + 36L * i;
     int s = ARSLAM_COV_UNAVAILABLE;
@@ -402,7 +451,10 @@ void arslam_lm::covariance_pairs(const arslam_lm_cov_pair *pairs, int n_pairs, d
           for (int q = 0; q < 6; ++q) m[6 * r + q] = as_is ? o[6 * r + q] : o[6 * q + r];
         const bool fa = ba.role == arslam::kCovFocal, fb = bb.role == arslam::kCovFocal;
         std::fill(c, c + 36, 0.0);
-        if (fa) std::copy(m, m + (fb ? 1 : 6), c);                 // row 0: cov(f, b)
+        if (lens) {
+          const int ra = fa ? n_camv : 6, cb = fb ? n_camv : 6;
+          for (int r = 0; r < ra; ++r) std::copy(m + 6 * r, m + 6 * r + cb, c + 6 * r);
+        } else if (fa) std::copy(m, m + (fb ? 1 : 6), c);          // row 0: cov(f, b)
         else if (fb) for (int r = 0; r < 6; ++r) c[r] = m[6 * r];   // column 0: cov(a, f)
         else std::copy(m, m + 36, c);
       }

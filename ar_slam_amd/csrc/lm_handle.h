@@ -527,6 +527,9 @@ struct arslam_lm {
   arslam::SelinvPlan cov_sp;
   bool cov_sp_ready = false;   // cov_sp is the loaded plan's
   DevBuf<double> d_cov_Z, d_cov_Q, d_cov_Y, d_cov_R, d_cov_out, d_cov_diag;   // d_cov_out: e-blocks 36 nc | f-blocks 36 nt | var(f)
+  // the e-blocks' G_la = Q'L_a, 12 each: allocated at the first _lens call on a
+  // problem whose l1, l2 are live (d_cov_out then ends with the camera's 3x3)
+  DevBuf<double> d_cov_Gl;
   DevBuf<int> d_cov_status;
   hipEvent_t cov_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   // the kept result, in the caller's block order (arslam_lm_covariance_block serves it)
@@ -534,8 +537,14 @@ struct arslam_lm {
   std::vector<double> cov_cap, cov_tag;
   std::vector<int> cov_cap_status, cov_tag_status;
   double cov_var_f = -1.0;
+  // the camera's 3x3 over [f, l1, l2] and its status; cov_from_lens: the kept
+  // result is arslam_lm_covariance_lens' (the pointer-keyed forms serve only
+  // their own kind's)
+  double cov_cam[9] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};
+  int cov_cam_status = ARSLAM_COV_UNAVAILABLE;
+  bool cov_from_lens = false;
   arslam_lm_cov_info cov_info{};
-  void covariance();
+  void covariance(bool lens = false);
   void cov_invalidate() {
     solve_state = 0;
     cov_valid = false;
@@ -551,12 +560,13 @@ struct arslam_lm {
     std::vector<int> cap_start;   // the device problem's e-block CSR
     bool deficient = false;
     bool factored = false;        // the device work was enqueued
+    bool live = false;            // a _lens call on a problem whose l1, l2 are estimated: they are rows of H
     arslam_lm_cov_info info{};
   };
   bool cov_e_free(int c) const { return slot_free[3 + 6L * c] != 0; }
   bool cov_f_free(int t) const { return slot_free[3 + 6L * nc + 6L * t] != 0; }
-  void cov_check_state(const char *who) const;
-  void cov_factor(CovFactor &cf);
+  void cov_check_state(const char *who, bool lens = false) const;
+  void cov_factor(CovFactor &cf, bool lens = false, bool assemble_only = false);
   void cov_numeric_test(CovFactor &cf);
 
   // ---- cross-covariance blocks (arslam_lm_covariance_pairs) ----
@@ -572,5 +582,5 @@ struct arslam_lm {
   DevBuf<int> d_pair_status;
   std::vector<hipEvent_t> pair_ev;   // two per batch, around its solve
   void covariance_pairs(const arslam_lm_cov_pair *pairs, int n_pairs, double *cov, int *status,
-                        arslam_lm_cov_info *info);
+                        arslam_lm_cov_info *info, bool lens = false);
 };

@@ -49,6 +49,11 @@ void debug_read_schur_stamps(unsigned long long *out);
 // cam_row + 2 and the rhs row, with the rows' D_f^2.
 void launch_schur_cam(const DevProblem &P, const DevCamL &cl, const double *scale, const double *diag, double radius, double *S,
                       hipStream_t s);
+// The second half of launch_schur_cam on its own: the sums of the borders in
+// cl.cam_slab into S (k_schur_cam_gather), whoever stored them there -- the
+// covariance's elimination assembles its border with it (cov_lens.hip).
+void launch_schur_cam_gather(const DevProblem &P, const DevCamL &cl, const double *diag, double radius, double *S,
+                             hipStream_t s);
 // debug: reduced rows cam_row .. cam_row + 2 of S against every reduced column
 // and the rhs, out[b (nR + 1) + col] (device memory)
 void debug_cam_rows(const DevProblem &P, double *S, double *out, hipStream_t s);

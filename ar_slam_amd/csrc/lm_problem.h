@@ -192,6 +192,12 @@ struct DevCamL {
   const int2 *camg_items = nullptr; // [cap_blk_start[nc]] {e-block, local block 0..}
 };
 
+// where e-block c's border lives in DevCamL::cam_slab, and its leading dimension m + 3
+__device__ __forceinline__ long cam_slab_off(const DevProblem &P, int c) { return 8L * c + 12L * P.cap_blk_start[c]; }
+__device__ __forceinline__ int cam_slab_ld(const DevProblem &P, int c) {
+  return 4 + 6 * (P.cap_blk_start[c + 1] - P.cap_blk_start[c]);
+}
+
 // element (r, c), r >= c, of the compact-tiled reduced system
 __device__ inline double *reduced_elem(double *S, const DevProblem &P, long r, long c) {
   return S + (long)P.tile_id[(r >> 6) * P.T + (c >> 6)] * 4096 + (r & 63) * 64 + (c & 63);

@@ -36,12 +36,6 @@ namespace {
 // the chunk's observations' local blocks (kObsChunk ints)
 __host__ __device__ constexpr int schur_cam_lds_doubles(int nblk) { return 12 * kObsChunk + 12 * nblk + kObsChunk / 2; }
 
-// where e-block c's border lives in DevCamL::cam_slab, and its leading dimension m + 3
-__device__ __forceinline__ long cam_slab_off(const DevProblem &P, int c) { return 8L * c + 12L * P.cap_blk_start[c]; }
-__device__ __forceinline__ int cam_slab_ld(const DevProblem &P, int c) {
-  return 4 + 6 * (P.cap_blk_start[c + 1] - P.cap_blk_start[c]);
-}
-
 __global__ __launch_bounds__(kWave) void k_schur_cam(DevProblem P, DevCamL CL, const double *__restrict__ scale) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int c = blockIdx.x, lane = threadIdx.x;
@@ -258,6 +252,12 @@ void launch_schur_cam(const DevProblem &P, const DevCamL &cl, const double *scal
   if (P.nc == 0 || P.cam_row < 0) return;
   const size_t lds = sizeof(double) * schur_cam_lds_doubles(P.max_blk_per_cap);
   hipLaunchKernelGGL(k_schur_cam, dim3(P.nc), dim3(kWave), lds, s, P, cl, scale);
+  launch_schur_cam_gather(P, cl, diag, radius, S, s);
+}
+
+void launch_schur_cam_gather(const DevProblem &P, const DevCamL &cl, const double *diag, double radius, double *S,
+                             hipStream_t s) {
+  if (P.nc == 0 || P.cam_row < 0) return;
   const unsigned tag_blocks = (unsigned)((12L * P.nt + 255) / 256);
   hipLaunchKernelGGL(k_schur_cam_gather, dim3(7 + tag_blocks), dim3(256), 0, s, P, cl, S, diag, radius);
 }

@@ -18,8 +18,7 @@
 // of X_kk are read as zero.  The leading block of a triangular inverse is the
 // inverse of the leading block, so Z on the real rows is exact, and zero on
 // the others.
-#include "llt_tile.h"
-#include "lm_cov.h"
+#include "cov_device.h"
 
 #include <algorithm>
 
@@ -167,14 +166,6 @@ __global__ __launch_bounds__(256) void k_selinv_diag(const double *__restrict__ 
 // ---------------------------------------------------------------------------
 // Marginal blocks of the covariance from Z (arslam_lm_covariance).
 
-// Z[r][c] of the selected inverse (either triangle: the stored tile is (max, min))
-__device__ __forceinline__ double z_elem(const double *__restrict__ Z, const DevProblem &P, long r, long c) {
-  const long a = r >= c ? r : c, b = r >= c ? c : r;
-  const int id = P.tile_id[(a >> 6) * P.T + (b >> 6)];
-  // (every pair of one e-block's f-blocks is an assembled tile; a pair outside the factor has no Z)
-  return id < 0 ? __builtin_nan("") : Z[(long)id * 4096 + (a & 63) * 64 + (b & 63)];
-}
-
 // Reduced-side blocks: thread (t, e) writes element e = 6 i + j of f-block t's
 // 6x6 block, s_i s_j Z[row + i][row + j], the lower element for both (i, j)
 // and (j, i); t == nt: var(f) from the camera's first row.  A block that is
@@ -198,13 +189,6 @@ __global__ void k_cov_fblocks(DevProblem P, const double *__restrict__ Z, const 
   const long sl = 3 + 6L * P.nc + 6L * t;
   const int hi = i >= j ? i : j, lo = i >= j ? j : i;
   cov_f[id] = scale[sl + hi] * scale[sl + lo] * z_elem(Z, P, row + hi, row + lo);
-}
-
-// sum over the wavefront, the same bits in every lane (xor butterfly)
-__device__ __forceinline__ double wave_sum64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
 }
 
 // Elimination of e-block c for the covariance, one wavefront each, by an

@@ -62,6 +62,8 @@ EXPORTS = ["arslam_lm_options_init", "arslam_lm_create", "arslam_lm_destroy",
            "arslam_debug_angle_axis_rotate", "arslam_debug_selinv", "arslam_lm_debug_force_indefinite",
            "arslam_lm_covariance", "arslam_lm_covariance_block", "arslam_lm_debug_reduced_rows",
            "arslam_lm_covariance_pairs", "arslam_lm_covariance_block_pair", "arslam_debug_tile_solve",
+           "arslam_lm_covariance_lens", "arslam_lm_covariance_block_lens", "arslam_lm_covariance_pairs_lens",
+           "arslam_lm_covariance_block_pair_lens", "arslam_lm_debug_cov_camera_rows",
            "arslam_lm_debug_force_multirank", "arslam_lm_debug_break_dependency", "arslam_lm_debug_tag_pair_tile",
            "arslam_debug_reduced_plan", "arslam_debug_reduced_plan_side", "arslam_debug_schur_stamps", "arslam_debug_ceres_e_blocks",
            "arslam_debug_order_memory",
@@ -346,6 +348,12 @@ def lib():
     L.arslam_lm_covariance_block.argtypes = [C.c_void_p, _dp, _dp, _ip]
     L.arslam_lm_covariance_pairs.argtypes = [C.c_void_p, _ip, C.c_int, _dp, _ip, C.POINTER(CovInfo)]
     L.arslam_lm_covariance_block_pair.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip]
+    if hasattr(L, "arslam_lm_covariance_lens"):   # (absent from older variant builds under A/B)
+        L.arslam_lm_covariance_lens.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip, _ip, _ip, C.POINTER(CovInfo)]
+        L.arslam_lm_covariance_block_lens.argtypes = [C.c_void_p, _dp, _dp, _ip]
+        L.arslam_lm_covariance_pairs_lens.argtypes = [C.c_void_p, _ip, C.c_int, _dp, _ip, C.POINTER(CovInfo)]
+        L.arslam_lm_covariance_block_pair_lens.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip]
+        L.arslam_lm_debug_cov_camera_rows.argtypes = [C.c_void_p, C.c_long, _dp, _ip]
     L.arslam_debug_tile_solve.argtypes = [C.c_long, _dp, _up, C.c_int, _dp, _dp, _ip]
     L.arslam_lm_debug_reduced_rows.argtypes = [C.c_void_p, _ip, _ip, _ip]
     L.arslam_debug_ceres_e_blocks.argtypes = [C.POINTER(SoaProblem), _ip]
@@ -506,8 +514,9 @@ class _Handle:
         """Estimate the distortion (off on creation): under CAMERA_RADIAL, with the camera block not
         constant, l1 and l2 are parameters like f and camera[1], camera[2] come back estimated;
         ignored under CAMERA_PINHOLE.  Drops a loaded problem and a kept covariance.  While it is in
-        effect several ranks, ELIM_MIXED on a set that mixes sides and the covariances are refused
-        (UNSUPPORTED)."""
+        effect several ranks, ELIM_MIXED on a set that mixes sides and the covariances whose camera
+        output is one scalar are refused (UNSUPPORTED); ``covariance_lens`` and the other ``_lens``
+        forms carry the camera block whole and work."""
         _check(lib().arslam_lm_set_estimate_distortion(self._h, int(on)))
 
     def estimate_distortion(self):
@@ -676,6 +685,53 @@ class ResidentProblem(_Handle):
                                                 C.byref(info)))
         return cov, st[:n], info.to_dict()
 
+    def covariance_lens(self):
+        """``covariance()`` with the camera block whole (arslam_lm_covariance_lens): ``cam`` (3, 3),
+        the marginal of [f, l1, l2], and ``cam_status`` beside the other keys (``var_f`` = cam[0, 0]
+        when the camera has a covariance, else -1).  Works under ``set_estimate_distortion``: l1, l2
+        are then rows of H and every block is the marginal of that larger H.  Held l1, l2: their
+        rows and columns of ``cam`` are 0 and the rest is ``covariance()``'s bits."""
+        n_cap, n_tag = self.A.s.n_cap, self.A.s.n_tag
+        cap = np.zeros((n_cap, 6, 6))
+        tag = np.zeros((n_tag, 6, 6))
+        cam = np.zeros((3, 3))
+        cs = np.zeros(max(n_cap, 1), np.int32)
+        ts = np.zeros(max(n_tag, 1), np.int32)
+        cam_st = C.c_int(0)
+        info = CovInfo()
+        _check(lib().arslam_lm_covariance_lens(self._h, cap.ctypes.data_as(_dp), tag.ctypes.data_as(_dp),
+                                               cam.ctypes.data_as(_dp), cs.ctypes.data_as(_ip),
+                                               ts.ctypes.data_as(_ip), C.byref(cam_st), C.byref(info)))
+        return {"cap": cap, "tag": tag, "cam": cam, "var_f": cam[0, 0] if cam_st.value == COV_OK else -1.0,
+                "cap_status": cs[:n_cap], "tag_status": ts[:n_tag], "cam_status": cam_st.value,
+                "info": info.to_dict()}
+
+    def covariance_pairs_lens(self, pairs):
+        """``covariance_pairs()`` over the matrix of ``covariance_lens()``
+        (arslam_lm_covariance_pairs_lens): BLOCK_CAMERA is the 3-wide block [f, l1, l2] -- rows 0..2
+        of the (6, 6) as a, columns 0..2 as b, the top-left (3, 3) against itself, 0 elsewhere."""
+        flat = np.ascontiguousarray([[a[0], a[1], b[0], b[1]] for a, b in pairs], np.int32).reshape(-1, 4)
+        n = len(flat)
+        cov = np.zeros((n, 6, 6))
+        st = np.zeros(max(n, 1), np.int32)
+        info = CovInfo()
+        _check(lib().arslam_lm_covariance_pairs_lens(self._h, flat.ctypes.data_as(_ip) if n else None, C.c_int(n),
+                                                     cov.ctypes.data_as(_dp) if n else None, st.ctypes.data_as(_ip),
+                                                     C.byref(info)))
+        return cov, st[:n], info.to_dict()
+
+    def debug_cov_camera_rows(self):
+        """(rows (3, n_reduced + 1), row_slot (3,)): the camera's reduced rows f, l1, l2 of the
+        covariance's reduced system at the point the last ``solve()`` returned -- no LM diagonal, the
+        last column (the right-hand side) 0 (arslam_lm_debug_cov_camera_rows)."""
+        cam = self.debug_reduced_rows()[2]
+        n_cols = cam + 4
+        rows = np.zeros((3, n_cols))
+        slot = np.zeros(3, np.int32)
+        _check(lib().arslam_lm_debug_cov_camera_rows(self._h, n_cols, rows.ctypes.data_as(_dp),
+                                                     slot.ctypes.data_as(_ip)))
+        return rows, slot
+
     def debug_reduced_rows(self):
         """(cap_row (n_cap,), tag_row (n_tag,), cam_row): the first reduced row of each block, -1 off
         the reduced side (arslam_lm_debug_reduced_rows)."""
@@ -796,6 +852,30 @@ class Problem(_Handle):
         st = C.c_int(0)
         _check(lib().arslam_lm_covariance_block_pair(self._h, a.ctypes.data_as(_dp), b.ctypes.data_as(_dp),
                                                      out.ctypes.data_as(_dp), C.byref(st)))
+        return out, st.value
+
+    def covariance_block_lens(self, block):
+        """``covariance_block`` with the camera's (3, 3) over [f, l1, l2] whole
+        (arslam_lm_covariance_block_lens); works under ``set_estimate_distortion``."""
+        if not (isinstance(block, np.ndarray) and block.dtype == np.float64 and block.size in (3, 6)):
+            raise TypeError("parameter block must be a float64 array of size 3 or 6")
+        k = block.size
+        out = np.zeros((k, k))
+        st = C.c_int(0)
+        _check(lib().arslam_lm_covariance_block_lens(self._h, block.ctypes.data_as(_dp), out.ctypes.data_as(_dp),
+                                                     C.byref(st)))
+        return out, st.value
+
+    def covariance_block_pair_lens(self, a, b):
+        """``covariance_block_pair`` with the camera block's three rows / columns [f, l1, l2]
+        (arslam_lm_covariance_block_pair_lens); works under ``set_estimate_distortion``."""
+        for blk in (a, b):
+            if not (isinstance(blk, np.ndarray) and blk.dtype == np.float64 and blk.size in (3, 6)):
+                raise TypeError("parameter block must be a float64 array of size 3 or 6")
+        out = np.zeros((a.size, b.size))
+        st = C.c_int(0)
+        _check(lib().arslam_lm_covariance_block_pair_lens(self._h, a.ctypes.data_as(_dp), b.ctypes.data_as(_dp),
+                                                          out.ctypes.data_as(_dp), C.byref(st)))
         return out, st.value
 
     def reset(self):

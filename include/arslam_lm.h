@@ -308,7 +308,9 @@ int arslam_lm_camera_model(const arslam_lm *h, int *model);
  * left as it was: several ranks (arslam_lm_set_comm, _set_comm_callback; the
  * switch itself on a handle that has them); ARSLAM_ELIM_MIXED on a problem
  * whose e-block set mixes captures and tags (a set that is one whole side is
- * solved); arslam_lm_covariance* (the covariance eliminations hold l1, l2).
+ * solved); arslam_lm_covariance, _covariance_block, _covariance_pairs and
+ * _covariance_block_pair, whose outputs have one scalar for the camera.  Their
+ * _lens forms (below) carry the camera block whole and work under the switch.
  * An appended pointer-keyed problem is loaded in full (setup_kind says so). */
 int arslam_lm_set_estimate_distortion(arslam_lm *h, int on);
 int arslam_lm_estimate_distortion(const arslam_lm *h, int *on);
@@ -437,7 +439,8 @@ int arslam_lm_set_iteration_callback(arslam_lm *h, arslam_iteration_callback fn,
  * ARSLAM_E_STATE when no completed solve precedes the call or the last one
  * ended with rule EVAL_FAILED (both checked before any device call).
  * ARSLAM_E_UNSUPPORTED while arslam_lm_set_estimate_distortion is in effect
- * (checked first), with several ranks (arslam_lm_debug_force_multirank
+ * (checked first; arslam_lm_covariance_lens is the form that works under the
+ * switch), with several ranks (arslam_lm_debug_force_multirank
  * included) and when the loaded problem's elimination_used is
  * ARSLAM_ELIM_MIXED; ARSLAM_ELIM_CAPTURES, _TAGS, and _AUTO or _MIXED
  * resolving to one whole side are supported.  The call changes nothing a
@@ -472,6 +475,32 @@ int arslam_lm_covariance(arslam_lm *h, double *cov_cap, double *cov_tag, double 
  * = ARSLAM_COV_*; -1 in the values unless OK.  ARSLAM_E_INVALID_ARG for a
  * pointer that is not a block of the problem. */
 int arslam_lm_covariance_block(arslam_lm *h, const double *block, double *cov, int *status);
+
+/* ---- the same with the camera block whole: [f, l1, l2] ----
+ * arslam_lm_covariance with cov_cam [9], the 3x3 marginal of the camera block
+ * (row-major, [i][j] and [j][i] the same bits), and cam_status in place of
+ * var_f.  It is not refused while arslam_lm_set_estimate_distortion is in
+ * effect: H then runs over l1, l2 too (when the loaded problem has them live:
+ * ARSLAM_CAMERA_RADIAL, the switch, a camera block that is not constant), the
+ * capture and tag blocks are the marginals of that larger H -- wider, because
+ * the lens is uncertain -- and the numeric test's min_pivot runs over the rows
+ * of l1, l2 as well (same threshold).  With l1, l2 held (the switch off,
+ * ARSLAM_CAMERA_PINHOLE, a constant camera) their rows and columns of cov_cam
+ * are 0, [0] is var(f), and every other output is bit for bit what
+ * arslam_lm_covariance returns on that handle (where that call is refused:
+ * what it returns on a handle that never set the switch), by the same
+ * launches.  A constant or unused camera: ARSLAM_COV_UNAVAILABLE and -1 in the
+ * nine values.  Every other rule -- the point, apply_loss_function, no LM
+ * diagonal, unit-variance residuals, the anchor's gauge, the structural check,
+ * the refusals (several ranks, an unresolved ARSLAM_ELIM_MIXED, no completed
+ * solve), what a later solve returns -- is arslam_lm_covariance's.  Nothing is
+ * allocated for the live lens before the first _lens call on such a problem.
+ * Each output nullable. */
+int arslam_lm_covariance_lens(arslam_lm *h, double *cov_cap, double *cov_tag, double *cov_cam, int *cap_status,
+                              int *tag_status, int *cam_status, arslam_lm_cov_info *info);
+/* arslam_lm_covariance_block with the camera's 3x3 in the nine values of the
+ * camera pointer.  Served from the kept result of an earlier _lens call. */
+int arslam_lm_covariance_block_lens(arslam_lm *h, const double *block, double *cov, int *status);
 
 /* ---- cross-covariance blocks (ceres::Covariance::Compute(pairs), GetCovarianceBlock(a, b)) ----
  * Block (a, b) of the same matrix C = H^-1 as arslam_lm_covariance: the same
@@ -537,6 +566,24 @@ int arslam_lm_covariance_pairs(arslam_lm *h, const arslam_lm_cov_pair *pairs, in
  * pointer that is not a block of the problem. */
 int arslam_lm_covariance_block_pair(arslam_lm *h, const double *block_a, const double *block_b,
                                     double *cov, int *status);
+
+/* arslam_lm_covariance_pairs over the matrix of arslam_lm_covariance_lens,
+ * ARSLAM_BLOCK_CAMERA the 3-wide block [f, l1, l2], and not refused under
+ * arslam_lm_set_estimate_distortion.  Still 36 values per pair, a 6x6
+ * row-major: the camera as a fills rows 0..2 (cov(cam_i, b_j)), as b columns
+ * 0..2, against itself the top-left 3x3; the rest is 0.  With l1, l2 held
+ * their rows and columns are 0 and the values are arslam_lm_covariance_pairs'
+ * bits (that call keeps a pose against the focal in its first six values;
+ * this one in column 0, the transpose of (camera, pose)).  (a, b) and (b, a)
+ * are transposes of the same bits.  Everything else as
+ * arslam_lm_covariance_pairs. */
+int arslam_lm_covariance_pairs_lens(arslam_lm *h, const arslam_lm_cov_pair *pairs, int n_pairs,
+                                    double *cov /* [n_pairs*36] */, int *status /* [n_pairs], nullable */,
+                                    arslam_lm_cov_info *info /* nullable */);
+/* arslam_lm_covariance_block_pair over the same matrix, in Ceres' shapes: the
+ * camera pointer's rows or columns are the three of [f, l1, l2]. */
+int arslam_lm_covariance_block_pair_lens(arslam_lm *h, const double *block_a, const double *block_b,
+                                         double *cov, int *status);
 
 /* Diagnostics */
 int arslam_device_count(void);

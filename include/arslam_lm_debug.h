@@ -153,6 +153,17 @@ int arslam_lm_debug_reduced_rows(arslam_lm *h, int *cap_row, int *tag_row, int *
  * D^2 alone.  The next solve starts from the loaded state as usual. */
 int arslam_lm_debug_camera_rows(arslam_lm *h, double radius, long n_cols, double *rows, int *row_slot);
 
+/* The same three rows of the covariance's reduced system: after a completed
+ * solve (the preconditions of arslam_lm_covariance_lens), at the point it
+ * returned, under that solve's Jacobi scale and with no LM diagonal -- the
+ * covariance's linearization, its orthogonal elimination, with l1, l2 live
+ * its border (k_cov_schur_cam), and the gathers, and nothing more: no
+ * factorization.  rows, n_cols and row_slot as arslam_lm_debug_camera_rows;
+ * the right-hand side entries are 0.  With l1, l2 held rows 1, 2 hold the
+ * pivot 1 alone.  ARSLAM_E_STATE for a problem without a gauge anchor.  The
+ * next solve starts from the loaded state as usual. */
+int arslam_lm_debug_cov_camera_rows(arslam_lm *h, long n_cols, double *rows, int *row_slot);
+
 /* Every stage of one LM step of the loaded problem (one rank; SoA or
  * pointer-keyed; any elimination; with or without a free camera or a reduced
  * system) at its loaded point under the given radius, as solve()'s first step
