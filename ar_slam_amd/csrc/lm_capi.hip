@@ -12,6 +12,8 @@ arslam_lm::~arslam_lm() {
   arslam::selinv_plan_free(cov_sp);
   for (auto e : pair_ev)
     if (e) (void)hipEventDestroy(e);
+  for (auto e : ev_evt)
+    if (e) (void)hipEventDestroy(e);
   arslam::tile_solve_plan_free(cov_tp);
   arslam::llt_plan_free(plan);
   if (comm) (void)ncclCommDestroy(comm);
@@ -88,7 +90,7 @@ int arslam_lm_set_options(arslam_lm *h, const arslam_lm_options *opt) {
             ARSLAM_E_INVALID_ARG, "a handle's device is fixed once it has loaded a problem: create a new handle");
     if (opt->device != h->opt.device || opt->reduced_ordering != h->opt.reduced_ordering ||
         opt->cholesky_skip_zero_tiles != h->opt.cholesky_skip_zero_tiles || opt->elimination != h->opt.elimination)
-      h->loaded = false, h->pk_dirty = true;
+      h->loaded = false, h->pk_dirty = true, h->eval_drop();
     h->opt = *opt;
   });
 }
@@ -110,6 +112,7 @@ int arslam_lm_set_loss(arslam_lm *h, int kind, double a) {
     // resident problem is dropped all the same: one rule for both paths)
     h->loaded = false;
     h->pk_dirty = true;
+    h->eval_drop();
   });
 }
 
@@ -129,6 +132,7 @@ int arslam_lm_set_tag_size(arslam_lm *h, double size) {
     // the resident problem is dropped)
     h->loaded = false;
     h->pk_dirty = true;
+    h->eval_drop();
   });
 }
 
@@ -151,6 +155,7 @@ int arslam_lm_set_camera_model(arslam_lm *h, int model) {
     // other model; so was its last solve, which a kept covariance describes)
     h->loaded = false;
     h->pk_dirty = true;
+    h->eval_drop();
     h->cov_invalidate();
   });
 }
@@ -173,6 +178,7 @@ int arslam_lm_set_estimate_distortion(arslam_lm *h, int on) {
     // had the other set of parameters)
     h->loaded = false;
     h->pk_dirty = true;
+    h->eval_drop();
     h->cov_invalidate();
   });
 }
@@ -404,6 +410,7 @@ int arslam_lm_add_residual_block_sized(arslam_lm *h, const double corners[8], do
       t = ti->second;
     }
     if (ti == h->tag_of.end()) h->pk_appended_only = false;   // a new tag: new reduced rows
+    h->eval_drop();
     h->pk_dirty = true;
     h->pk_obs_cap.push_back(c);
     h->pk_obs_tag.push_back(t);
@@ -419,14 +426,14 @@ int arslam_lm_set_parameter_block_constant(arslam_lm *h, double *block) {
   return arslam::api_guarded([&] {
     fail_if(block != h->camera_ptr && !h->cap_of.count(block) && !h->tag_of.count(block),
             ARSLAM_E_INVALID_ARG, "parameter block is not part of the problem");
-    if (h->constant.insert(block).second) h->pk_dirty = true, h->pk_appended_only = false;
+    if (h->constant.insert(block).second) h->pk_dirty = true, h->pk_appended_only = false, h->eval_drop();
   });
 }
 
 int arslam_lm_set_parameter_block_variable(arslam_lm *h, double *block) {
   if (!h || !block) return ARSLAM_E_INVALID_ARG;
   return arslam::api_guarded([&] {
-    if (h->constant.erase(block)) h->pk_dirty = true, h->pk_appended_only = false;
+    if (h->constant.erase(block)) h->pk_dirty = true, h->pk_appended_only = false, h->eval_drop();
   });
 }
 
@@ -473,6 +480,7 @@ int arslam_lm_solve(arslam_lm *h, arslam_lm_summary *summary) {
       h->pk_dirty = false;    // appended residual blocks within the loaded tile pattern: layout and plan kept
     } else {
       h->reuse_order = h->pk_loaded;   // a grown pointer-keyed problem (not the first load)
+      h->ev_src_set = false;           // (arslam_lm_evaluate: no problem of arslam_lm_load_soa's any more)
       h->load(&p, pk_loss);
       h->reuse_order = false;
       h->pk_loaded = true;
@@ -498,6 +506,7 @@ int arslam_lm_reset(arslam_lm *h) {
     h->constant.clear();
     h->loaded = false;
     h->pk_dirty = true;
+    h->eval_drop();
     h->pk_loaded = false;
     h->order.forget();
   });
@@ -535,7 +544,18 @@ int arslam_lm_load_soa_sized(arslam_lm *h, const arslam_soa_problem *p, const do
     // (the caller's arrays are read during the load only)
     arslam::ObsLoss ol = obs_loss_kind ? arslam::ObsLoss{obs_loss_kind, obs_loss_a} : h->default_obs_loss(p->n_obs);
     ol.size = h->obs_sizes(p, tag_size);
+    h->ev_src_set = false;
     h->load(p, ol);
+    // arslam_lm_evaluate's view of the problem: the caller's arrays (read at the
+    // first evaluate), and a copy of the losses that were given for this call only
+    h->ev_src = *p;
+    h->ev_src_loss_from = obs_loss_kind ? 1 : ol.kind ? 2 : 0;
+    h->ev_src_sized = ol.size != nullptr;
+    if (obs_loss_kind) {
+      h->ev_src_kind.assign(obs_loss_kind, obs_loss_kind + p->n_obs);
+      h->ev_src_a.assign(obs_loss_a, obs_loss_a + p->n_obs);
+    }
+    h->ev_src_set = true;
   });
 }
 
@@ -783,6 +803,7 @@ int arslam_lm_set_comm_callback(arslam_lm *h, int rank, int nranks, arslam_allre
     h->comm_cb_ctx = ctx;
     h->loaded = false;
     h->pk_dirty = true;
+    h->eval_drop();
   });
 }
 
@@ -798,6 +819,7 @@ int arslam_lm_set_comm(arslam_lm *h, int rank, int nranks, const unsigned char i
     h->nranks = nranks;
     h->loaded = false;
     h->pk_dirty = true;
+    h->eval_drop();
     if (h->multi()) {   // (one rank only under arslam_debug_force_multirank)
       ncclUniqueId u;
       std::memcpy(&u, id, sizeof(u));
@@ -846,6 +868,7 @@ int arslam_lm_debug_force_multirank(arslam_lm *h, int on) {
     h->force_multi = on != 0;
     h->loaded = false;
     h->pk_dirty = true;
+    h->eval_drop();
   });
 }
 

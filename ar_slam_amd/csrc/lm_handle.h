@@ -2,13 +2,15 @@
 // own buffers and timers (HIP_CHECK and DevBuf are hip_host.h's), and
 // `struct arslam_lm` with every member.  The methods'
 // bodies live in lm_load.hip (load, upload, append, value reload), lm_solve.hip
-// (the trust-region loop, its stages, the linearization), lm_covariance.hip and
+// (the trust-region loop, its stages, the linearization), lm_covariance.hip,
+// lm_evaluate.hip (arslam_lm_evaluate*, with its own entry points) and
 // lm_capi.hip (the extern "C" entry points); only those include this header.
 #pragma once
 #include "hip_host.h"
 #include "host_threads.h"
 #include "llt_plan.h"
 #include "lm_cov.h"
+#include "lm_evaluate.h"
 #include "lm_launch.h"
 #include "lm_problem.h"
 #include "loss.h"
@@ -583,4 +585,41 @@ struct arslam_lm {
   std::vector<hipEvent_t> pair_ev;   // two per batch, around its solve
   void covariance_pairs(const arslam_lm_cov_pair *pairs, int n_pairs, double *cov, int *status,
                         arslam_lm_cov_info *info, bool lens = false);
+
+  // ---- Evaluate (arslam_lm_evaluate*, lm_evaluate.hip) ----
+  // A path of its own: the problem's structure in the caller's order, its own
+  // buffers, nothing of the solver's device state.  Everything below is
+  // allocated and uploaded at the first evaluate after a load or an added block.
+  // the problem arslam_lm_load_soa* was given, in the caller's roles (load()'s
+  // soa is the device problem's), and its explicit per-observation losses (the
+  // default loss's are soa_loss_*, the sides soa_size)
+  arslam_soa_problem ev_src{};
+  bool ev_src_set = false, ev_src_sized = false;
+  int ev_src_loss_from = 0;   // 0 no loss, 1 ev_src_kind / ev_src_a, 2 soa_loss_kind / soa_loss_a
+  std::vector<unsigned char> ev_src_kind;
+  std::vector<double> ev_src_a;
+  // the device structure (pointers into ev_upload) and what it was built for
+  bool ev_valid = false, ev_pk = false;
+  int ev_nc = 0, ev_nt = 0, ev_nb = 0, ev_mode = 0;   // ev_mode: 0 pinhole, 1 radial held, 2 radial estimated
+  bool ev_loss = false, ev_sized = false, ev_cam_const = false;
+  UploadArena ev_upload;
+  arslam::EvalProblem EV{};
+  DevBuf<double> d_ev_x, d_ev_res, d_ev_obs, d_ev_parts, d_ev_out;
+  PinnedBuf h_ev_x;
+  // options.phase_timing: the last evaluate's upload, k_eval_obs, k_eval_blocks,
+  // k_eval_tree (both launches) and copy back, ms (arslam_lm_debug_evaluate_times)
+  hipEvent_t ev_evt[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  double ev_ms[5] = {0, 0, 0, 0, 0};
+  bool ev_ms_valid = false;
+  // the last arslam_lm_evaluate_blocks' gradient (arslam_lm_gradient_block)
+  bool ev_grad_valid = false;
+  std::vector<double> ev_grad;
+  // whatever drops the loaded problem or changes the blocks drops the structure
+  void eval_drop() {
+    ev_valid = false;
+    ev_grad_valid = false;
+  }
+  void eval_upload_structure(bool pk);
+  void evaluate(bool pk, const arslam_lm_evaluate_options *opt, double *cost, double *residuals, double *sq_norm,
+                double *weight, double *gradient);
 };

@@ -143,6 +143,7 @@ void arslam_lm::load(const arslam_soa_problem *p_in, const arslam::ObsLoss &in_l
   est_check_load(p_in);
   loaded = false;
   cov_invalidate();
+  eval_drop();
   cov_sp_ready = false;
   cov_tp_ready = false;
   // (the process's first HIP call starts the runtime, 0.02-0.2 s: the first

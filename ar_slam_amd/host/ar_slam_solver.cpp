@@ -388,7 +388,25 @@ void ArSlamSolver::addCaptureBlocks(Capture &capture) {   // block loop of :704-
     check(arslam_lm_get_loss(problem_, &loss_kind, &loss_a));
     check(arslam_lm_add_residual_block_sized(problem_, xy, camera_.params.data(), capture.data(), aruco.data(),
                                              aruco.size, loss_kind, loss_a));
+    problem_blocks_.push_back(bh.idx);
   }
+}
+
+// was: problem_.Evaluate(Problem::EvaluateOptions(), &cost, &residuals, nullptr, nullptr), per block
+int ArSlamSolver::evaluate(double *cost, double *sq_norm, double *weight) {
+  const size_t n = problem_blocks_.size();
+  std::vector<double> s(n), w(n);
+  const int rc = arslam_lm_evaluate_blocks(problem_, nullptr, cost, nullptr, s.data(), w.data());
+  if (rc != ARSLAM_OK) return rc;
+  for (size_t b = 0; b < blocks_.size(); ++b) {
+    if (sq_norm) sq_norm[b] = -1.0;
+    if (weight) weight[b] = -1.0;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    if (sq_norm) sq_norm[problem_blocks_[i]] = s[i];
+    if (weight) weight[problem_blocks_[i]] = w[i];
+  }
+  return ARSLAM_OK;
 }
 
 void ArSlamSolver::solveCapture(Capture &capture, std::optional<BlockHandle> init_block) {   // :680-742
@@ -596,7 +614,10 @@ int ArSlamSolver::setArucoSize(const std::string &id, double size) {
   return ARSLAM_OK;
 }
 
-void ArSlamSolver::resetProblem() { check(arslam_lm_reset(problem_)); }   // :1021-1025
+void ArSlamSolver::resetProblem() {   // :1021-1025
+  check(arslam_lm_reset(problem_));
+  problem_blocks_.clear();
+}
 
 std::vector<Transform> ArSlamSolver::getTransforms() const {   // :1028-1075
   std::vector<Transform> out;

@@ -207,6 +207,14 @@ class ArSlamSolver {
   // the first request after it.  Returns ARSLAM_OK, or ARSLAM_E_STATE for a
   // capture the last localizeMany did not cover.  cov and cov_status nullable.
   int localizeCovariance(unsigned cap_idx, double cov[36], int *cov_status);
+  // ceres::Problem::Evaluate on the mapper problem at the current poses
+  // (arslam_lm_evaluate_blocks): *cost = 1/2 sum rho over the residual blocks
+  // in the problem; per block of the data store (numBlocks entries, block
+  // handle order) its |r|^2 and its loss weight rho' under the loss it was
+  // added with, -1 in both for a block that is not in the problem (not yet
+  // added, or localized by localizeMany, which adds none).  All nullable.
+  // Returns arslam_lm_evaluate_blocks' code (ARSLAM_E_STATE: no block added yet).
+  int evaluate(double *cost, double *sq_norm, double *weight);
 
   // data-store builders (protected in the reference; public here so a host
   // or test can assemble a problem without ROS messages)
@@ -229,6 +237,7 @@ class ArSlamSolver {
   std::deque<Capture> captures_;   // stable addresses: the solver keys blocks by pointer
   std::deque<Aruco> arucos_;
   std::vector<Block> blocks_;
+  std::vector<unsigned> problem_blocks_;   // the blocks in problem_, in the order they were added (evaluate)
   std::unordered_map<std::string, unsigned> capture_map_;
   std::unordered_map<std::string, unsigned> aruco_map_;
   // the reference's container and hash (ar_slam_util.hpp:140-145, 492): solveIncremental

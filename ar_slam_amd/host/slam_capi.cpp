@@ -194,6 +194,13 @@ int arslam_slam_localize_covariance(arslam_slam *h, int cap_idx, double cov[36],
   return g ? g : rc;
 }
 
+int arslam_slam_evaluate(arslam_slam *h, double *cost, double *sq_norm, double *weight) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  int rc = ARSLAM_OK;
+  const int g = slam_guarded([&] { rc = h->s.evaluate(cost, sq_norm, weight); });   // (the lm call set the message)
+  return g ? g : rc;
+}
+
 int arslam_slam_num_captures(const arslam_slam *h) { return h ? (int)h->s.numCaptures() : 0; }
 int arslam_slam_num_arucos(const arslam_slam *h) { return h ? (int)h->s.numArucos() : 0; }
 int arslam_slam_num_blocks(const arslam_slam *h) { return h ? (int)h->s.numBlocks() : 0; }

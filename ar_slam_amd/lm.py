@@ -57,6 +57,8 @@ EXPORTS = ["arslam_lm_options_init", "arslam_lm_create", "arslam_lm_destroy",
            "arslam_lm_set_estimate_distortion", "arslam_lm_estimate_distortion",
            "arslam_debug_residual_jacobian_distortion", "arslam_lm_debug_camera_rows",
            "arslam_lm_debug_step_stages",
+           "arslam_lm_evaluate_options_init", "arslam_lm_evaluate", "arslam_lm_evaluate_blocks",
+           "arslam_lm_gradient_block", "arslam_slam_evaluate", "arslam_lm_debug_evaluate_times",
            "arslam_debug_residual_jacobian", "arslam_debug_dense_llt", "arslam_debug_dense_llt_ex",
            "arslam_debug_tile_llt", "arslam_debug_tile_plan",
            "arslam_debug_angle_axis_rotate", "arslam_debug_selinv", "arslam_lm_debug_force_indefinite",
@@ -207,6 +209,11 @@ class StepInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class EvaluateOptions(C.Structure):
+    """arslam_lm_evaluate_options."""
+    _fields_ = [("apply_loss_function", C.c_int)]
+
+
 class SoaProblem(C.Structure):
     _fields_ = [("n_cap", C.c_int), ("n_tag", C.c_int), ("n_obs", C.c_int),
                 ("camera", _dp), ("cap", _dp), ("tag", _dp),
@@ -323,6 +330,13 @@ def lib():
     if hasattr(L, "arslam_lm_debug_step_stages"):   # (likewise)
         L.arslam_lm_debug_step_stages.argtypes = [C.c_void_p, C.c_double, C.POINTER(StepInfo), _dp, _dp, _dp, _dp, _dp,
                                                   _ip, _dp, _dp]
+    if hasattr(L, "arslam_lm_evaluate"):   # (absent from older variant builds under A/B)
+        L.arslam_lm_evaluate_options_init.argtypes = [C.POINTER(EvaluateOptions)]
+        L.arslam_lm_evaluate.argtypes = [C.c_void_p, C.POINTER(EvaluateOptions), _dp, _dp, _dp, _dp, _dp]
+        L.arslam_lm_evaluate_blocks.argtypes = [C.c_void_p, C.POINTER(EvaluateOptions), _dp, _dp, _dp, _dp]
+        L.arslam_lm_gradient_block.argtypes = [C.c_void_p, _dp, _dp]
+        L.arslam_slam_evaluate.argtypes = [C.c_void_p, _dp, _dp, _dp]
+        L.arslam_lm_debug_evaluate_times.argtypes = [C.c_void_p, _dp]
     L.arslam_lm_set_parameter_block_constant.argtypes = [C.c_void_p, _dp]
     L.arslam_lm_set_parameter_block_variable.argtypes = [C.c_void_p, _dp]
     L.arslam_lm_solve.argtypes = [C.c_void_p, C.POINTER(Summary)]
@@ -552,6 +566,13 @@ class _Handle:
         one rank, so set_comm(0, 1, uid) makes a one-rank RCCL communicator on a one-GPU box."""
         _check(lib().arslam_lm_debug_force_multirank(self._h, 1 if on else 0))
 
+    def debug_evaluate_times(self):
+        """The last evaluate()'s device times under phase_timing=1, ms: {upload, k_eval_obs,
+        k_eval_blocks, k_eval_tree, copy_back} (arslam_lm_debug_evaluate_times)."""
+        ms = np.zeros(5)
+        _check(lib().arslam_lm_debug_evaluate_times(self._h, ms.ctypes.data_as(_dp)))
+        return dict(zip(("upload", "k_eval_obs", "k_eval_blocks", "k_eval_tree", "copy_back"), ms.tolist()))
+
     def debug_step_stages(self, radius):
         """Every stage of one LM step of the loaded problem at its loaded point under `radius`
         (arslam_lm_debug_step_stages): a dict of the arslam_lm_step_info fields and
@@ -608,6 +629,28 @@ def comm_unique_id() -> bytes:
     return buf.raw
 
 
+def _evaluate(call, n_cap, n_tag, n_obs, apply_loss, residuals, gradient):
+    """One arslam_lm_evaluate / _evaluate_blocks call (call(opt, cost, residuals, sq_norm, weight[,
+    gradient])) into fresh arrays; the result dict of ResidentProblem.evaluate."""
+    o = EvaluateOptions(1 if apply_loss else 0)
+    cost = C.c_double(0.0)
+    res = np.zeros((n_obs, 8)) if residuals else None
+    sq = np.zeros(n_obs)
+    w = np.zeros(n_obs)
+    args = [C.byref(o), C.byref(cost), res.ctypes.data_as(_dp) if residuals else None, sq.ctypes.data_as(_dp),
+            w.ctypes.data_as(_dp)]
+    out = {"cost": 0.0, "residuals": res, "sq_norm": sq, "weight": w, "gradient": None}
+    if gradient is not None:
+        g = np.zeros(3 + 6 * n_cap + 6 * n_tag) if gradient else None
+        args.append(g.ctypes.data_as(_dp) if gradient else None)
+        if gradient:
+            out["gradient"] = {"camera": g[:3], "cap": g[3:3 + 6 * n_cap].reshape(n_cap, 6),
+                               "tag": g[3 + 6 * n_cap:].reshape(n_tag, 6)}
+    _check(call(*args))
+    out["cost"] = cost.value
+    return out
+
+
 class ResidentProblem(_Handle):
     """SoA problem uploaded once to HBM; ``solve()`` restarts from the loaded state."""
 
@@ -652,6 +695,18 @@ class ResidentProblem(_Handle):
         s = Summary()
         _check(lib().arslam_lm_solve_loaded(self._h, C.byref(s)))
         return s.to_dict()
+
+    def evaluate(self, apply_loss=True, residuals=True, gradient=True):
+        """ceres::Problem::Evaluate at the values ``camera`` / ``cap`` / ``tag`` hold now (the results
+        after a solve, the loaded values before one, anything written there): ``cost`` = 1/2 sum rho,
+        ``residuals`` (n_obs, 8) corrected by sqrt(rho'), ``sq_norm`` (n_obs,) the uncorrected |r|^2,
+        ``weight`` (n_obs,) rho' (1 without a loss; near 0 for a rejected detection) and ``gradient``
+        {camera (3,), cap (n_cap, 6), tag (n_tag, 6)}, exactly 0 for constant and unseen blocks
+        (arslam_lm_evaluate).  apply_loss=False: the plain r, 1/2 sum s and J'r.  residuals / gradient
+        False: that output is not computed back (its key is None)."""
+        n_cap, n_tag, n_obs = self.A.s.n_cap, self.A.s.n_tag, self.A.s.n_obs
+        return _evaluate(lambda *a: lib().arslam_lm_evaluate(self._h, *a), n_cap, n_tag, n_obs, apply_loss, residuals,
+                         gradient)
 
     def covariance(self):
         """Marginal covariances at the point the last ``solve()`` returned (arslam_lm_covariance):
@@ -828,6 +883,25 @@ class Problem(_Handle):
         s = Summary()
         _check(lib().arslam_lm_solve(self._h, C.byref(s)))
         return s.to_dict()
+
+    def evaluate(self, apply_loss=True, residuals=True):
+        """ceres::Problem::Evaluate over the residual blocks in the order they were added, at the
+        values the blocks hold now (arslam_lm_evaluate_blocks): ``cost``, ``residuals`` (n, 8),
+        ``sq_norm`` (n,), ``weight`` (n,) as ResidentProblem.evaluate; the gradient is kept on the
+        handle for ``gradient_block``."""
+        n = self.num_residual_blocks()
+        out = _evaluate(lambda *a: lib().arslam_lm_evaluate_blocks(self._h, *a), 0, 0, n, apply_loss, residuals, None)
+        del out["gradient"]
+        return out
+
+    def gradient_block(self, block):
+        """The block's (3,) or (6,) entries of the gradient of the last ``evaluate()``
+        (arslam_lm_gradient_block); an LMError (STATE) when the problem changed since."""
+        if not (isinstance(block, np.ndarray) and block.dtype == np.float64 and block.size in (3, 6)):
+            raise TypeError("parameter block must be a float64 array of size 3 or 6")
+        out = np.zeros(block.size)
+        _check(lib().arslam_lm_gradient_block(self._h, block.ctypes.data_as(_dp), out.ctypes.data_as(_dp)))
+        return out
 
     def covariance_block(self, block):
         """Covariance::GetCovarianceBlock(block, block) after ``solve()``: (6, 6) for a pose block,
@@ -1602,6 +1676,17 @@ class SlamSolver:
         cov, st = np.zeros((6, 6)), C.c_int(-1)
         _check(lib().arslam_slam_localize_covariance(self._h, int(cap_idx), cov.ctypes.data_as(_dp), C.byref(st)))
         return cov, st.value
+
+    def evaluate(self):
+        """ceres::Problem::Evaluate on the mapper problem at the current poses
+        (arslam_slam_evaluate): {cost, sq_norm (num_blocks,), weight (num_blocks,)}, the block's
+        |r|^2 and loss weight rho' under the loss it was added with; -1 in both for a block that
+        is not in the problem."""
+        n = lib().arslam_slam_num_blocks(self._h)
+        cost = C.c_double(0.0)
+        sq, w = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+        _check(lib().arslam_slam_evaluate(self._h, C.byref(cost), sq.ctypes.data_as(_dp), w.ctypes.data_as(_dp)))
+        return {"cost": cost.value, "sq_norm": sq[:n], "weight": w[:n]}
 
     @property
     def num_captures(self):

@@ -585,6 +585,56 @@ int arslam_lm_covariance_pairs_lens(arslam_lm *h, const arslam_lm_cov_pair *pair
 int arslam_lm_covariance_block_pair_lens(arslam_lm *h, const double *block_a, const double *block_b,
                                          double *cov, int *status);
 
+/* ---- Evaluate (ceres::Problem::Evaluate, Ceres 2.0, default EvaluateOptions) ----
+ * The cost, the residuals, each residual block's loss weight and the gradient
+ * at the values in the caller's memory at the time of the call, as Ceres reads
+ * the user's pointers.  For residual block o, with r its 8 residuals and
+ * s = |r|^2:
+ *   residuals[8 o ..]  the corrected sqrt(rho'(s)) r (r itself without a loss)
+ *   sq_norm[o]         s, uncorrected
+ *   weight[o]          rho'(s); 1 for a block without a loss (a rejected
+ *                      detection shows a weight near 0)
+ *   *cost              1/2 sum rho(s) over all residual blocks
+ *   gradient           J~'r~ over [camera 3 | captures 6 n_cap | tags 6 n_tag]
+ *                      in the caller's indexing.  Exactly 0.0: the entries of
+ *                      a constant block, of a block no residual block touches,
+ *                      and l1, l2 unless the handle is ARSLAM_CAMERA_RADIAL with
+ *                      estimate_distortion on and the camera free.
+ * Every block's loss, its tag's side and the handle's camera model are
+ * honoured.  apply_loss_function = 0: the plain r, 1/2 sum s and J'r, weights 1.
+ * Every output is nullable; what is not asked for is not copied back.
+ * A path of its own: it needs no prior solve, reads nothing of the solver's
+ * state and leaves it untouched (a solve after it returns the bits of a solve
+ * without it), and its results do not depend on options.elimination,
+ * factor_executor or any other solver option.  The problem's structure goes
+ * to the device at the first evaluate after a load or an added block; a call
+ * then uploads the parameter values and runs three kernels.
+ * ARSLAM_E_STATE: no problem loaded / no blocks.  ARSLAM_E_UNSUPPORTED: a
+ * handle of several ranks (arslam_lm_debug_force_multirank included).  No
+ * device: the failure arslam_lm_solve_loaded gives, never a CPU fallback. */
+typedef struct {
+  int apply_loss_function;   /* 1 */
+} arslam_lm_evaluate_options;
+int arslam_lm_evaluate_options_init(arslam_lm_evaluate_options *opt);
+/* The problem loaded by arslam_lm_load_soa*, in that problem's observation
+ * order (residuals[8 n_obs], sq_norm[n_obs], weight[n_obs],
+ * gradient[3 + 6 n_cap + 6 n_tag]).  Reads the SoA arrays given at load time as
+ * they are now: the results after a solve, the initial values before one,
+ * anything the caller wrote to camera, cap or tag.  The problem's other arrays
+ * (obs_cap, obs_tag, corners, the constant flags) must still be the loaded
+ * ones: the first evaluate after a load reads them.  opt NULL: the defaults. */
+int arslam_lm_evaluate(arslam_lm *h, const arslam_lm_evaluate_options *opt, double *cost, double *residuals,
+                       double *sq_norm, double *weight, double *gradient);
+/* The pointer-keyed residual blocks, in the order they were added, at the
+ * values the caller's blocks hold now. */
+int arslam_lm_evaluate_blocks(arslam_lm *h, const arslam_lm_evaluate_options *opt, double *cost, double *residuals,
+                              double *sq_norm, double *weight);
+/* A parameter block's 3 (camera) or 6 gradient entries from the last
+ * arslam_lm_evaluate_blocks, as arslam_lm_covariance_block serves from a kept
+ * result.  ARSLAM_E_STATE if there is none, or if the problem changed since
+ * (a block added, a block set constant or variable, a reset). */
+int arslam_lm_gradient_block(arslam_lm *h, const double *block, double *out);
+
 /* Diagnostics */
 int arslam_device_count(void);
 const char *arslam_lm_last_error(void);

@@ -203,6 +203,12 @@ typedef struct {
 int arslam_lm_debug_step_stages(arslam_lm *h, double radius, arslam_lm_step_info *info, double *g, double *colnorm,
                                 double *scale, double *diag, double *S, int *row_slot, double *y, double *xc);
 
+/* The device times of the handle's last arslam_lm_evaluate / _evaluate_blocks
+ * under options.phase_timing = 1 (HIP events on its stream), ms: the parameter
+ * upload, k_eval_obs, k_eval_blocks, k_eval_tree (both launches), the copy
+ * back.  ARSLAM_E_STATE when there was no such call (tools/evaluate_cost.py). */
+int arslam_lm_debug_evaluate_times(arslam_lm *h, double ms[5]);
+
 /* Host-only symbolic analysis of the reduced system (no device needed): the
  * row layout arslam_lm_load_soa would choose for problem p under the given
  * ordering (0 natural, 1 RCM, 2 nested dissection) and tile pattern

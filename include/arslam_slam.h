@@ -115,6 +115,15 @@ int arslam_slam_localize_many(arslam_slam *h, int first_loc_cap_idx);
  * a capture the last localize_many did not cover (a mapping capture, or no
  * localize_many yet). */
 int arslam_slam_localize_covariance(arslam_slam *h, int cap_idx, double cov[36], int *cov_status);
+/* ceres::Problem::Evaluate on the mapper problem (arslam_lm_evaluate_blocks,
+ * arslam_lm.h): *cost = 1/2 sum rho over the residual blocks in the problem,
+ * and over arslam_slam_num_blocks entries (block index as in arslam_slam_block)
+ * sq_norm = the block's |r|^2 and weight = its rho' at the current poses, under
+ * the loss the block was added with -- which detections a robust solve
+ * rejected (weight near 0).  Blocks that are not in the problem (not yet
+ * added, or localized by arslam_slam_localize_many) get -1 in both arrays.
+ * All nullable.  ARSLAM_E_STATE when no block has been added. */
+int arslam_slam_evaluate(arslam_slam *h, double *cost, double *sq_norm, double *weight);
 
 int arslam_slam_num_captures(const arslam_slam *h);
 int arslam_slam_num_arucos(const arslam_slam *h);
