@@ -58,15 +58,19 @@ namespace {
 // cfg3 k_factor_dag: 3 -> 660.8, 4 -> 665.1, 2 -> 676.1, 1 -> 683.8 us
 // (interleaved, one box): waves 1-3 working beside the earlier panels slow
 // wave 0's diagonal blocks (the same steps alone on the chip cost nothing,
-// tools/pipe_bench.hip).
+// tools/pipe_bench.hip).  Measured again with the round counted before the
+// side work and row block 3 on wave 0 (profiles/potrf_sidework/): 3 -> 558.2,
+// 2 -> 556.5, 1 -> 557.2 us, inside the spread of two copies of one library.
 #ifndef ARSLAM_PIPE_FROM
 #define ARSLAM_PIPE_FROM 3
 #endif
 constexpr int kPipeFrom = ARSLAM_PIPE_FROM;
 #ifndef ARSLAM_PIPE_W2
-#define ARSLAM_PIPE_W2 1
+#define ARSLAM_PIPE_W2 0
 #endif
-constexpr int kPipeW2 = ARSLAM_PIPE_W2;   // the wave (1-3) that also takes row block 3
+// The wave that takes row block 3's early steps: 1-3 beside the last panel after its own row block's, or 0: wave 0
+// itself once the last diagonal block is factored, beside the other waves' steps.
+constexpr int kPipeW2 = ARSLAM_PIPE_W2;
 
 struct DagArgs {
   double *S;
@@ -128,7 +132,7 @@ __device__ __forceinline__ DagRecV lds_rec(const int *s) {
 // claimed continuation's record.  Who writes a slot, who reads it, and what
 // orders the two -- "barrier": a __syncthreads() between the store and the
 // loads; "flag": the slot is the hand-off itself (lds_set / lds_add / lds_wait,
-// llt_tile.h).  Slots 5, 19, 22 and 23 are free.
+// llt_tile.h).  Slots 5, 19, 22 and 23 are free (19, 22, 23: a stamped build's exit times of waves 1-3).
 enum DagShSlot {
   kShTicket = 0,      // thread 0: the ticket it drew; all, between the two barriers at the top of the loop
   kShBad = 1,         // blocked_potrf64_async's `bad`: its waves 0 (diag16); all, after its closing barrier
@@ -395,12 +399,34 @@ __global__ __launch_bounds__(256, kDagWorkgroupsPerCu) void k_factor_dag(DagArgs
       bool third_done = false;
       // The fused solve's first steps beside the last panel: once the whole
       // tile is in X, waves 1-3 apply the solve's column steps 0-2 while wave 0
-      // factors the last diagonal block (wave w takes row block w - 1, and wave
-      // kPipeW2 row block 3 as well), so only step 3 remains after the factorization (the
-      // same products in the same order).  Beside the earlier panels they slow
-      // the factorization more than they save (kPipeFrom).
+      // factors the last diagonal block (wave w takes row block w - 1), so only
+      // step 3 remains after the factorization (the same products in the same
+      // order).  Row block 3's steps are wave 0's own, once that block is
+      // factored (kPipeW2 == 0): on a second wave they came behind that wave's
+      // own row block, 48 dependent MFMAs in a row, and wave 0 stood 2.4 us at
+      // the closing barrier on every prefetched link -- its three round waits
+      // together are 0.2 us (profiles/potrf_sidework/stretch_parent.txt).  Now
+      // the four waves reach the barrier within 0.2 us of each other.  Beside
+      // the earlier panels the steps slow the factorization more than they
+      // save (kPipeFrom).
       int sdone = 0;
+#ifdef ARSLAM_DAG_SUBSTAMPS
+      // the waves' own stamps inside the POTRF (PfStamp) go straight to the ticket's trace words (zeroed by the host)
+      unsigned long long *const ws = a.trace ? a.trace + kDagTraceWords * (long)t + kTrPfStamp0 : nullptr;
+#else
+      unsigned long long *const ws = nullptr;
+#endif
       const bool ok = blocked_potrf64_async(D, inv, LTd, sh + kShBad, sh + kShPipe0, tid, colx, [&](int p, int wv, int ln) {
+        if (wv == 0) {
+          // wave 0, the last diagonal block factored (p == 4): row block 3's steps 0-2 (kPipeW2 == 0), if the
+          // tile is in X by now -- else wave 3 runs them after the barrier, as without the prefetch
+          if (kPipeW2 == 0 && kPipeFrom <= 3 && pf_src && lds_get(sh + kShThirds) >= 3) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            for (int st = 0; st < 3; ++st) trsm_step(X, D, LTd, 3, st, ln);
+            if (ln == 0) sh[kShSolveStep0 + 3] = 3;
+          }
+          return;
+        }
         auto fetch_third = [&]() {
         auto poll = [&]() {
           if (!pf_src || pw1 - pw0 > 64) return false;
@@ -499,7 +525,12 @@ __global__ __launch_bounds__(256, kDagWorkgroupsPerCu) void k_factor_dag(DagArgs
             if (wv == kPipeW2) sh[kShSolveStep0 + 3] = sdone;
           }
         }
-      }, X, fold_in, sh + kShFoldCnt);   // (fold_in, not a null test of the LDS pointer: hipcc mis-selects that null check)
+#ifdef ARSLAM_DAG_SUBSTAMPS
+        // back from the last panel's side work: the clock's low word into a free slot (19, 22, 23), thread 0
+        // copies it to the trace after the closing barrier (a 64-bit store from here spills an eighth VGPR)
+        if (p == 3 && ln == 0) *as_lds(sh + (wv == 1 ? 19 : 20 + wv)) = (int)realtime();
+#endif
+      }, X, fold_in, sh + kShFoldCnt, ws);   // (fold_in, not a null test of the LDS pointer: hipcc mis-selects that null check)
       // A fused solve whose tile is already in X has no wait: the CU's flag
       // stays up through it too (the solve is the link's next stretch of the
       // chain; cfg3 k_factor_dag 621.9 -> 604.2 us, same-box A/B)
@@ -507,6 +538,13 @@ __global__ __launch_bounds__(256, kDagWorkgroupsPerCu) void k_factor_dag(DagArgs
       if (tid == 0 && !keep_flag)
         __hip_atomic_store(cu_flag + cu_key, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (a.trace && tid == 0) a.trace[kDagTraceWords * (long)t + kTrFactored] = realtime();
+#ifdef ARSLAM_DAG_SUBSTAMPS
+      if (a.trace && tid == 0) {
+        a.trace[kDagTraceWords * (long)t + kTrPfStamp0 + kPsIdle1] = (unsigned)sh[19];
+        a.trace[kDagTraceWords * (long)t + kTrPfStamp0 + kPsIdle1 + 1] = (unsigned)sh[22];
+        a.trace[kDagTraceWords * (long)t + kTrPfStamp0 + kPsIdle1 + 2] = (unsigned)sh[23];
+      }
+#endif
       if (!ok && tid == 0) {
         int first = 0;
         while (first < T64 && D[first * LQ + first] > 0.0) ++first;

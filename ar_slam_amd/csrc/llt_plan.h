@@ -78,7 +78,15 @@ enum DagTraceWord {
   kTrWantKnown = 9,      // the claim's ticket count, started count and reservation are in hand
   kTrSolved = 10,        // every wave's solve steps are done (the barrier after them)
   kTrAcked = 11,         // the solved tile's stores are acknowledged (the barrier before its publish)
+#ifdef ARSLAM_DAG_SUBSTAMPS
+  // a stamped build only (the default library's trace keeps 12 words and its kernel its addressing): the waves'
+  // own stamps inside the POTRF, blocked_potrf64_async's PfStamp words in their order -- wave 0 before and after
+  // each of its three round waits, wave 0 at the closing barrier, waves 1-3 back from the last panel's side work
+  kTrPfStamp0 = 12,      // .. + 9
+  kDagTraceWords = 22
+#else
   kDagTraceWords = 12
+#endif
 };
 constexpr int kDagTraceFileWords = 8;   // the words of a ticket in the trace file's main block
 constexpr int kDagTraceSubWords = kDagTraceWords - kDagTraceFileWords;

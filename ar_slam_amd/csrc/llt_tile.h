@@ -365,8 +365,9 @@ __device__ __forceinline__ void lds_wait(const int *f, int v) {
 // (p+1, p+1) -> diag16(p+1) ...; waves 1-3 apply the blocks further down and
 // do the trailing updates of each panel (and the optional fold F F^T) beside
 // it, synchronised through the LDS counters fl[kPf*] (PotrfFlag below).
-// idle(p, w, lane) runs on waves 1-3 after round p (as beside panel p in the
-// barrier version).
+// idle(p, w, lane) runs on waves 1-3 after round p's updates (as beside panel
+// p in the barrier version), behind the wave's round count (kPfCountFirst);
+// idle(4, 0, lane) on wave 0 after diag16(3), before the closing barrier.
 //
 // With the fold, wave 0's first apply and lookahead need only blocks (1, 0)
 // and (1, 1) folded -- the first blocks waves 1 and 2 fold -- not the whole
@@ -385,10 +386,55 @@ enum PotrfFlag {
 };
 // (*fcnt: blocks (1, 0) and (1, 1) of the fold done -- waves 1 and 2 add, wave 0 waits for 2; all four flags, *fcnt
 // and *bad are zeroed by thread 0 before the start barrier)
+//
+// The round count and the side work (kPfCountFirst).  A wave's round count says that its share of the round's
+// updates of D is done; wave 0 waits for it after diag16(p) and needs nothing of what idle(p) does.  Counted after
+// idle(p) (0, the order this pipeline had), everything the caller does there -- loads it waits for, counter
+// polls -- stands on wave 0's chain; counted before it (1), the side work has the next kPfPanel as a soft
+// deadline instead.  No access of idle relies on the count coming after it:
+//   * k_factor_dag's thirds are stored into X from idle(1) on, and X may hold the fold's operand F.  idle(1) comes
+//     after lds_wait(fl + kPfPanel, 1), which wave 0 sets after its own fold block and diag16(0), and -- with the
+//     early fold -- after lds_wait(fl + kPfRound, 3), every wave's count *behind* its fold blocks in either
+//     order; without fcnt wave 0 itself waits for round 0 before it sets kPfPanel.
+//   * its trsm_step(st) beside panel p reads LTd[st] and blocks (st, c), c < st <= p - 1, of D: final since
+//     kPfPanel >= p and kPfApplied >= 3 p, which the wave awaited before the round's updates.  Wave 0, now up
+//     to one panel ahead (it still needs round p + 1, counted after idle(p) returns), writes blocks (p + 1, p),
+//     (p + 1, p + 1), inv and LTd[p + 1] meanwhile: none of those.
+//   * what idle leaves in LDS for after the factorization is ordered by the closing barrier as before, and the
+//     thirds by their own count (kPfCaller).
+// The products and their order are the same either way.
+#ifndef ARSLAM_PF_COUNT_FIRST
+#define ARSLAM_PF_COUNT_FIRST 1
+#endif
+constexpr bool kPfCountFirst = ARSLAM_PF_COUNT_FIRST != 0;
+//
+// ws (a build with -DARSLAM_DAG_SUBSTAMPS only; else unused): kPsStamps words of global memory, or null, for
+// wave 0's own s_memrealtime stamps (PfStamp), written by its lane 0 -- where wave 0 waits for waves 1-3
+// (tools/potrf_cont.py).  k_factor_dag points it at the ticket's trace words and fills kPsIdle1 .. itself.
+enum PfStamp {
+  kPsWait0 = 0,   // .. + 5: wave 0 before (2p) and after (2p + 1) its wait for round p, p = 0 .. 2
+  kPsClose = 6,   // wave 0 at the closing barrier (diag16(3) and idle(4, 0) done)
+  kPsIdle1 = 7,   // .. + 2: the caller's: wave 1 + i back from idle(3) (the clock's low 32 bits)
+  kPsStamps = 10
+};
+#ifdef ARSLAM_DAG_SUBSTAMPS
+#define PF_WSTAMP(ws, i, lane)                                                                \
+  do {                                                                                        \
+    if (ws) {                                                                                 \
+      __builtin_amdgcn_sched_barrier(0);                                                      \
+      unsigned long long _t;                                                                  \
+      asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t)::"memory");         \
+      if ((lane) == 0) ((__attribute__((address_space(1))) unsigned long long *)(ws))[i] = _t;  \
+      __builtin_amdgcn_sched_barrier(0);                                                      \
+    }                                                                                         \
+  } while (0)
+#else
+#define PF_WSTAMP(ws, i, lane) do {} while (0)
+#endif
 template <class Idle>
 __device__ bool blocked_potrf64_async(double *D, double *inv, double *LTd, int *bad, int *fl, int tid,
                                       double *colx, Idle &&idle, const double *F = nullptr, bool fold = false,
-                                      int *fcnt = nullptr) {
+                                      int *fcnt = nullptr, unsigned long long *ws = nullptr) {
   const int w = tid >> 6, lane = tid & 63;
   const bool early = fold && fcnt;
   if (tid == 0) {
@@ -409,8 +455,10 @@ __device__ bool blocked_potrf64_async(double *D, double *inv, double *LTd, int *
       diag16(D, b0, inv, LTd + p * 16 * LI, bad, lane, colx);
       STAMP(33 + 6 * p);
       if (p < 3) {
+        PF_WSTAMP(ws, kPsWait0 + 2 * p, lane);
         if (p == 0 && early) lds_wait(fcnt, 2);   // blocks (1, 0) and (1, 1) folded
         else lds_wait(fl + kPfRound, 3 * (p + 1));      // round p: block (p+1, p) has panel p-1's update
+        PF_WSTAMP(ws, kPsWait0 + 2 * p + 1, lane);
         STAMP(34 + 6 * p);
         // The block below the diagonal solved transposed, Y = L_pp^{-1} A^T
         // (the same products as A L_pp^{-T}, operands swapped: bit-identical),
@@ -440,6 +488,8 @@ __device__ bool blocked_potrf64_async(double *D, double *inv, double *LTd, int *
         for (int reg = 0; reg < 4; ++reg) Cd[(lk + 4 * reg) * LQ + li] = cd[reg] - g[reg];
       }
     }
+    idle(4, 0, lane);   // wave 0's own side work, diag16(3) done: waves 1-3 are still in idle(3)
+    PF_WSTAMP(ws, kPsClose, lane);
   } else {
     if (fold) {
       // the fold's lower blocks 1..9 in row order (I, C), I >= C: (1,0) (1,1) (2,0) (2,1) ...
@@ -451,8 +501,9 @@ __device__ bool blocked_potrf64_async(double *D, double *inv, double *LTd, int *
         if (early && t <= 2) lds_add(fcnt, lane);   // (1, 0) by wave 1, (1, 1) by wave 2
       }
     }
+    if (kPfCountFirst) lds_add(fl + kPfRound, lane);
     idle(0, w, lane);
-    lds_add(fl + kPfRound, lane);
+    if (!kPfCountFirst) lds_add(fl + kPfRound, lane);
     for (int p = 0; p < 3; ++p) {
       const int b0 = 16 * p;
       if (p == 0 && early) lds_wait(fl + kPfRound, 3);   // every block folded (wave 0 no longer awaits it)
@@ -470,8 +521,9 @@ __device__ bool blocked_potrf64_async(double *D, double *inv, double *LTd, int *
         const int bi = 16 * (p + 1 + I), bc = 16 * (p + 1 + C);
         wave_gemm16_sub(D + bi * LQ + bc, D + bi * LQ + b0, D + bc * LQ + b0, 16, lane);
       }
+      if (kPfCountFirst) lds_add(fl + kPfRound, lane);
       idle(p + 1, w, lane);
-      lds_add(fl + kPfRound, lane);
+      if (!kPfCountFirst) lds_add(fl + kPfRound, lane);
     }
   }
   __syncthreads();

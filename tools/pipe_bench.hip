@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256) void k_bench(const double *A, const double *Xg
       // applies, so column step q-1 of the solve is possible there; wave 1
       // takes row blocks 0 and 3, waves 2 and 3 one each
       auto pipe = [&](int q, int wv, int ln) {
-        if (q == 0) return;
+        if (q == 0 || wv == 0) return;   // (wave 0's own call after the last diagonal block: nothing here)
         if (wv == 1) {
           trsm_step(X, D, LTd, 0, q - 1, ln);
           trsm_step(X, D, LTd, 3, q - 1, ln);

@@ -86,9 +86,41 @@ for t in last:
 # own at the end of the file): L_kk published -> every wave at the solve -> the claim's prelude answered -> solve
 # steps done (barrier) -> the solved tile's stores acknowledged (barrier) -> its publish
 # (all zero unless the library was built with -DARSLAM_DAG_SUBSTAMPS)
-raw = f.read(32 * n)
-if len(raw) == 32 * n and np.frombuffer(raw, np.uint64).any():
-    ss = (np.frombuffer(raw, np.uint64).reshape(n, 4).astype(np.int64) - t0) / 100.0
+raw = f.read()
+nsub = len(raw) // (8 * n) if n else 0   # 4 words a ticket, or 14 with the waves' own stamps inside the POTRF
+if nsub >= 4 and len(raw) == 8 * nsub * n and np.frombuffer(raw, np.uint64).any():
+    allsub = np.frombuffer(raw, np.uint64).reshape(n, nsub).astype(np.int64)
+    if nsub >= 14:
+        # inside the POTRF (blocked_potrf64_async's PfStamp words): how long wave 0 stood in each of its three round
+        # waits (after diag16(p), before it may apply block (p + 1, p)) and at the closing barrier (diag16(3) done
+        # -> factored), and when each of waves 1-3 came back from the last panel's side work, as time before (-) or
+        # after (+) wave 0 reached the closing barrier.  A wait that was met on arrival reads the stamp pair's own
+        # cost (the floor column of the summary).
+        ws = allsub[:, 4:14]
+        print("   k  +potrf   wait0  wait1  wait2  close   sum    idle3: w1     w2     w3 (vs wave 0 at the barrier)"
+              "  flags cont")
+        wrows = []
+        for t in last:
+            w = ws[t]
+            if not w[6]:
+                continue
+            u = us[t]
+            d = [(w[2 * p + 1] - w[2 * p]) / 100.0 for p in range(3)] + [u[5] - (w[6] - t0) / 100.0]
+            # (the waves' exits are the clock's low 32 bits: a signed 32-bit difference to wave 0's stamp)
+            idl = [(((int(w[7 + i]) - int(w[6]) + 2**31) % 2**32 - 2**31) / 100.0 if w[7 + i] else float("nan"))
+                   for i in range(3)]
+            wrows.append((int(flags[t]), sub[t, 0] >= 0, [u[5] - u[4]] + d + [sum(d)] + idl))
+            print(f"{tasks[t, 1]:4d} {u[5] - u[4]:6.2f}  {d[0]:6.2f} {d[1]:6.2f} {d[2]:6.2f} {d[3]:6.2f} {sum(d):6.2f}"
+                  f"         {idl[0]:+6.2f} {idl[1]:+6.2f} {idl[2]:+6.2f}   {int(flags[t]):05b}  {'c' if t in cont else '-'}")
+        for nm, pick in (("pref", lambda fl_, fu: fu and fl_ & 4), ("not pref", lambda fl_, fu: fu and not fl_ & 4),
+                         ("no fused tile", lambda fl_, fu: not fu)):
+            sel = np.array([d for fl_, fu, d in wrows if pick(fl_, fu)])
+            if len(sel):
+                print(f"mean {nm:13s} n={len(sel):3d} " + " ".join(f"{v:6.2f}" for v in sel.mean(axis=0)) +
+                      "   median " + " ".join(f"{v:6.2f}" for v in np.median(sel, axis=0)))
+        if wrows:
+            print("floor (smallest wait seen, a stamp pair's own cost): %.2f" % min(min(d[1:4]) for _, _, d in wrows))
+    ss = (allsub[:, :4] - t0) / 100.0
     rows = []
     print("   k  publ->top  ->want  ->solved  ->acked  ->subpub   total  flags(premet,AkkD,pref,next_met,claim) cont")
     for t in last:
