@@ -228,6 +228,7 @@ int arslam_lm_debug_cov_camera_rows(arslam_lm *h, long n_cols, double *rows, int
     fail_if(!h->has_f || h->P.cam_row < 0, ARSLAM_E_STATE, "cov_camera_rows: a problem loaded with a free camera");
     fail_if(n_cols != h->nR + 1, ARSLAM_E_INVALID_ARG, "cov_camera_rows: n_cols must be the reduced row count + 1");
     h->cov_valid = false;
+    h->cov_anch_valid = false;
     // the covariance's linearization, elimination, border and gathers, the rows read before the factorization
     arslam_lm::CovFactor cf;
     h->cov_factor(cf, true, true);
@@ -755,6 +756,105 @@ int arslam_lm_covariance_block_pair_lens(arslam_lm *h, const double *block_a, co
   });
 }
 
+}  // extern "C"
+
+namespace {
+// the caller's {kind, index} of a pointer-keyed block (the camera: index 0); throws for a pointer that is no block
+void pk_block(const arslam_lm *h, const double *block, int *kind, int *index) {
+  double *key = const_cast<double *>(block);
+  const auto ci = h->cap_of.find(key);
+  const auto ti = h->tag_of.find(key);
+  fail_if(key != h->camera_ptr && ci == h->cap_of.end() && ti == h->tag_of.end(), ARSLAM_E_INVALID_ARG,
+          "parameter block is not part of the problem");
+  *kind = key == h->camera_ptr ? ARSLAM_BLOCK_CAMERA : ci != h->cap_of.end() ? ARSLAM_BLOCK_CAPTURE : ARSLAM_BLOCK_TAG;
+  *index = *kind == ARSLAM_BLOCK_CAMERA ? 0 : *kind == ARSLAM_BLOCK_CAPTURE ? ci->second : ti->second;
+}
+// the anchor of a pointer-keyed anchored form: null is none, the camera is refused
+arslam_lm::CovAnchor pk_anchor(const arslam_lm *h, const double *anchor) {
+  arslam_lm::CovAnchor an;
+  if (!anchor) return an;
+  pk_block(h, anchor, &an.kind, &an.index);
+  fail_if(an.kind == ARSLAM_BLOCK_CAMERA, ARSLAM_E_INVALID_ARG, "the anchor must be a pose block, not the camera");
+  return an;
+}
+}  // namespace
+
+extern "C" {
+
+int arslam_lm_covariance_anchored(arslam_lm *h, int anchor_kind, int anchor_index, double *cov_cap, double *cov_tag,
+                                  double *cov_cam, int *cap_status, int *tag_status, int *cam_status,
+                                  arslam_lm_cov_info *info) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return arslam::api_guarded([&] {
+    const arslam_lm::CovAnchor an{anchor_kind, anchor_index};
+    h->covariance(true, &an);
+    if (cov_cap && !h->cov_cap.empty()) std::memcpy(cov_cap, h->cov_cap.data(), h->cov_cap.size() * sizeof(double));
+    if (cov_tag && !h->cov_tag.empty()) std::memcpy(cov_tag, h->cov_tag.data(), h->cov_tag.size() * sizeof(double));
+    if (cov_cam) std::memcpy(cov_cam, h->cov_cam, 9 * sizeof(double));
+    if (cap_status && !h->cov_cap_status.empty())
+      std::memcpy(cap_status, h->cov_cap_status.data(), h->cov_cap_status.size() * sizeof(int));
+    if (tag_status && !h->cov_tag_status.empty())
+      std::memcpy(tag_status, h->cov_tag_status.data(), h->cov_tag_status.size() * sizeof(int));
+    if (cam_status) *cam_status = h->cov_cam_status;
+    if (info) *info = h->cov_info;
+  });
+}
+
+int arslam_lm_covariance_pairs_anchored(arslam_lm *h, int anchor_kind, int anchor_index,
+                                        const arslam_lm_cov_pair *pairs, int n_pairs, double *cov, int *status,
+                                        arslam_lm_cov_info *info) {
+  if (!h || n_pairs < 0 || (n_pairs > 0 && (!pairs || !cov))) return ARSLAM_E_INVALID_ARG;
+  return arslam::api_guarded([&] {
+    const arslam_lm::CovAnchor an{anchor_kind, anchor_index};
+    h->covariance_pairs(pairs, n_pairs, cov, status, info, true, &an);
+  });
+}
+
+int arslam_lm_covariance_block_anchored(arslam_lm *h, const double *anchor, const double *block, double *cov,
+                                        int *status) {
+  if (!h || !block || !cov) return ARSLAM_E_INVALID_ARG;
+  return arslam::api_guarded([&] {
+    int kind = 0, i = 0;
+    pk_block(h, block, &kind, &i);
+    const arslam_lm::CovAnchor an = pk_anchor(h, anchor);
+    fail_if(!h->pk_loaded || h->pk_dirty, ARSLAM_E_STATE,
+            "covariance_block_anchored: no completed arslam_lm_solve of the problem as it stands");
+    if (!h->cov_anch_valid || !(h->cov_anch == an)) h->covariance(true, &an);
+    if (kind == ARSLAM_BLOCK_CAMERA) {
+      std::memcpy(cov, h->cov_cam, 9 * sizeof(double));
+      if (status) *status = h->cov_cam_status;
+      return;
+    }
+    const bool is_cap = kind == ARSLAM_BLOCK_CAPTURE;
+    const std::vector<double> &c = is_cap ? h->cov_cap : h->cov_tag;
+    const std::vector<int> &st = is_cap ? h->cov_cap_status : h->cov_tag_status;
+    fail_if((size_t)i >= st.size(), ARSLAM_E_STATE, "covariance_block_anchored: the block is not part of the solved problem");
+    std::memcpy(cov, c.data() + 36L * i, 36 * sizeof(double));
+    if (status) *status = st[i];
+  });
+}
+
+int arslam_lm_covariance_block_pair_anchored(arslam_lm *h, const double *anchor, const double *block_a,
+                                             const double *block_b, double *cov, int *status) {
+  if (!h || !block_a || !block_b || !cov) return ARSLAM_E_INVALID_ARG;
+  return arslam::api_guarded([&] {
+    arslam_lm_cov_pair pr{};
+    pk_block(h, block_a, &pr.kind_a, &pr.index_a);
+    pk_block(h, block_b, &pr.kind_b, &pr.index_b);
+    const arslam_lm::CovAnchor an = pk_anchor(h, anchor);
+    fail_if(!h->pk_loaded || h->pk_dirty, ARSLAM_E_STATE,
+            "covariance_block_pair_anchored: no completed arslam_lm_solve of the problem as it stands");
+    double c[36];
+    int st = ARSLAM_COV_UNAVAILABLE;
+    h->covariance_pairs(&pr, 1, c, &st, nullptr, true, &an);
+    // Ceres' shapes: rows of a by columns of b, the camera block 3 wide -- the top-left of the 6x6
+    const int ra = pr.kind_a == ARSLAM_BLOCK_CAMERA ? 3 : 6, cb = pr.kind_b == ARSLAM_BLOCK_CAMERA ? 3 : 6;
+    for (int r = 0; r < ra; ++r)
+      for (int q = 0; q < cb; ++q) cov[cb * r + q] = st == ARSLAM_COV_OK ? c[6 * r + q] : -1.0;
+    if (status) *status = st;
+  });
+}
+
 int arslam_lm_debug_reduced_rows(arslam_lm *h, int *cap_row, int *tag_row, int *cam_row) {
   if (!h) return ARSLAM_E_INVALID_ARG;
   return arslam::api_guarded([&] {
@@ -926,3 +1026,14 @@ const char *arslam_lm_last_error(void) { return g_last_error.c_str(); }
 const char *arslam_lm_version(void) { return "arslam_lm 0.2 (gfx950, fp64) build " ARSLAM_BUILD_ID; }
 
 }  // extern "C"
+
+namespace arslam {
+// For the host mirror (ar_slam_solver.cpp), not part of the C-ABI: the info of
+// the result an _anchored pointer-keyed call keeps on the handle; false when
+// none is kept.
+bool kept_anchored_cov_info(const arslam_lm *h, arslam_lm_cov_info *info) {
+  if (!h || !h->cov_anch_valid) return false;
+  if (info) *info = h->cov_info;
+  return true;
+}
+}  // namespace arslam

@@ -2,7 +2,8 @@
 // inverse of the factored reduced system and the marginal blocks (selinv.hip),
 // the multi-right-hand-side tile solve and the cross-covariance blocks
 // (cov_pairs.hip), and the border and block kernels of a problem whose l1, l2
-// are estimated (cov_lens.hip).  Called by lm_covariance.hip, and by
+// are estimated (cov_lens.hip), and the local systems of a mixed e-block
+// set's direct groups (cov_direct.hip).  Called by lm_covariance.hip, and by
 // debug_tiles.hip for the component tests.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -129,5 +130,12 @@ void launch_cov_pair_rhs_lens(const DevProblem &P, const double *Gb, const doubl
 void launch_cov_pair_blocks_lens(const DevProblem &P, const double *X, const double *scale, const double *Gb,
                                  const double *Rb, const double *Glb, const CovPairTask *tasks, int n_tasks,
                                  double *out, int *status, const int *flag, hipStream_t s);
+
+// ---- cov_direct.hip ----
+// The mixed e-block set's direct groups (groups[0 .. n_groups), device; kind
+// kMixDirect), after launch_cov_schur on the same stream: each group's plain
+// F'F over [f | its tag blocks | its own pose | rhs = 0] into its slot of
+// P.slab, whole.  scale: the own pose's comes from its f-block's slots.
+void launch_cov_direct(const DevProblem &P, const double *scale, const int *groups, int n_groups, hipStream_t s);
 
 }  // namespace arslam

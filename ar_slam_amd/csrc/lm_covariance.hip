@@ -1,17 +1,63 @@
-// lm_covariance.hip -- arslam_lm_covariance and arslam_lm_covariance_pairs on the LM handle (lm_handle.h).
+// lm_covariance.hip -- arslam_lm_covariance and arslam_lm_covariance_pairs on the LM handle (lm_handle.h),
+// their _lens forms and their _anchored forms (a pose block held fixed for the call; any e-block set).
 #include "lm_handle.h"
 
 #include <map>
 
-void arslam_lm::cov_check_state(const char *who, bool lens) const {
+void arslam_lm::cov_check_state(const char *who, bool lens, bool anchored) const {
   const std::string w(who);
   fail_if(!lens && est_active(), ARSLAM_E_UNSUPPORTED,
           w + ": not supported while estimate_distortion is on (its camera output is one scalar: use the _lens form)");
   fail_if(!loaded || solve_state == 0, ARSLAM_E_STATE, w + ": no completed solve of the loaded problem");
   fail_if(solve_state == 2, ARSLAM_E_STATE, w + ": the last solve ended with rule EVAL_FAILED");
   fail_if(multi(), ARSLAM_E_UNSUPPORTED, w + ": single-rank only");
-  fail_if(elim_used == ARSLAM_ELIM_MIXED, ARSLAM_E_UNSUPPORTED,
-          w + ": the mixed e-block set is not supported (ARSLAM_ELIM_CAPTURES or _TAGS)");
+  fail_if(!anchored && elim_used == ARSLAM_ELIM_MIXED, ARSLAM_E_UNSUPPORTED,
+          w + ": the mixed e-block set is not supported (ARSLAM_ELIM_CAPTURES or _TAGS, or the _anchored form)");
+}
+
+arslam_lm::CovRoles arslam_lm::cov_roles() const {
+  CovRoles ro;
+  const auto size = [&](int n_cap, int n_tag) {
+    ro.n_cap = n_cap;
+    ro.n_tag = n_tag;
+    ro.cap_role.assign(n_cap, arslam::kCovF);
+    ro.cap_idx.assign(n_cap, -1);
+    ro.tag_role.assign(n_tag, arslam::kCovF);
+    ro.tag_idx.assign(n_tag, -1);
+    ro.e_node.assign(nc, -1);
+    ro.f_node.assign(nt, -1);
+  };
+  const auto put = [&](bool cap, int i, int role, int idx) {
+    (cap ? ro.cap_role : ro.tag_role)[i] = role;
+    (cap ? ro.cap_idx : ro.tag_idx)[i] = idx;
+    (role == arslam::kCovE ? ro.e_node : ro.f_node)[idx] = cap ? i : ro.n_cap + i;
+  };
+  if (elim_used == ARSLAM_ELIM_MIXED) {
+    size(mx.src_n_cap, mx.src_n_tag);
+    for (int f = 0; f < nt; ++f) put(mx.f_is_cap[f] != 0, mx.f_src[f], arslam::kCovF, f);
+    for (int g = 0; g < nc; ++g) {
+      if (mx.kind[g] == arslam::kMixDirect) ro.e_node[g] = mx.group_src[g];   // (its capture: an f-block)
+      else put(mx.kind[g] == arslam::kMixCap, mx.group_src[g], arslam::kCovE, g);
+    }
+  } else if (elim_used == ARSLAM_ELIM_TAGS) {   // e-blocks: the tags, f-blocks: the captures
+    size(nt, nc);
+    for (int t = 0; t < nc; ++t) put(false, t, arslam::kCovE, t);
+    for (int c = 0; c < nt; ++c) put(true, c, arslam::kCovF, c);
+  } else {
+    size(nc, nt);
+    for (int c = 0; c < nc; ++c) put(true, c, arslam::kCovE, c);
+    for (int t = 0; t < nt; ++t) put(false, t, arslam::kCovF, t);
+  }
+  return ro;
+}
+
+void arslam_lm::cov_check_anchor(const char *who, const CovAnchor &an, const CovRoles &ro) const {
+  const std::string w(who);
+  fail_if(an.kind != ARSLAM_BLOCK_NONE && an.kind != ARSLAM_BLOCK_CAPTURE && an.kind != ARSLAM_BLOCK_TAG,
+          ARSLAM_E_INVALID_ARG, w + ": the anchor's kind must be ARSLAM_BLOCK_CAPTURE, _TAG or _NONE");
+  if (an.none()) return;
+  const int nblk = an.kind == ARSLAM_BLOCK_CAPTURE ? ro.n_cap : ro.n_tag;
+  fail_if(an.index < 0 || an.index >= nblk, ARSLAM_E_INVALID_ARG, w + ": the anchor's index is out of range");
 }
 
 // The structural gauge check on the host, then one linearization at the point
@@ -22,9 +68,29 @@ void arslam_lm::cov_check_state(const char *who, bool lens) const {
 // are live: they are rows of H like f -- k_cov_schur_cam's border and the LM
 // step's border gather put them into the reduced system (cov_lens.hip).
 // assemble_only (arslam_lm_debug_cov_camera_rows): stop before the factorization.
-void arslam_lm::cov_factor(CovFactor &cf, bool lens, bool assemble_only) {
+//
+// an (the _anchored entry points): the call's anchor is held fixed without an
+// elimination of its own.  Every covariance kernel reads a copy of the Jacobi
+// scale with 0 on the anchor's six slots: an anchored e-block takes the
+// constant e-block's path (Q = 0, G = 0), an anchored f-block's columns vanish
+// and the gather's diagonal 1 makes its rows decoupled identity rows; the
+// callers override the anchor's outputs.  Under a mixed e-block set the copy
+// is 0 on the direct groups' slots too -- k_cov_schur then leaves them no Q, G
+// or R -- and k_cov_direct stores their local systems (cov_direct.hip).
+void arslam_lm::cov_factor(CovFactor &cf, bool lens, bool assemble_only, const CovAnchor *an) {
   ensure_stream();
   cf.live = lens && est_loaded;
+  cf.roles = cov_roles();
+  cf.scale = d_scale.p;
+  const CovRoles &ro = cf.roles;
+  if (an && !an->none()) {
+    const bool cap = an->kind == ARSLAM_BLOCK_CAPTURE;
+    cf.anchor_role = ro.role(cap, an->index);
+    cf.anchor_idx = ro.idx(cap, an->index);
+    cf.anchor_slot = cf.anchor_role == arslam::kCovE ? 3 + 6L * cf.anchor_idx : 3 + 6L * nc + 6L * cf.anchor_idx;
+  }
+  std::vector<double> h_scale(an ? n : 0);
+  if (an) HIP_CHECK(hipMemcpyAsync(h_scale.data(), d_scale.p, n * sizeof(double), hipMemcpyDeviceToHost, stream));
   // the device problem's structure (its host copy is not kept after a load)
   std::vector<int> &h_cs = cf.cap_start;
   h_cs.assign(nc + 1, 0);
@@ -36,31 +102,39 @@ void arslam_lm::cov_factor(CovFactor &cf, bool lens, bool assemble_only) {
   if (nb) HIP_CHECK(hipMemcpyAsync(h_act.data(), u_obs_active, nb, hipMemcpyDeviceToHost, stream));
   HIP_CHECK(hipMemcpyAsync(&n_blk, u_cap_blk_start + nc, sizeof(int), hipMemcpyDeviceToHost, stream));
   HIP_CHECK(hipStreamSynchronize(stream));
-  // Gauge: every connected component of the e-block / f-block graph over the
-  // active observations that holds a free block must hold a constant one
+  // Gauge: every connected component of the caller's capture / tag graph over
+  // the active observations that holds a free block must hold a constant one
+  // (the call's anchor counts as constant).  An observation joins the caller's
+  // blocks of its group and its f-block (CovRoles: a direct group's is its
+  // capture, no block of its own), so the outcome does not depend on the
+  // e-block set.
   bool deficient = false;
   {
-    std::vector<int> par(nc + nt);
-    for (int i = 0; i < nc + nt; ++i) par[i] = i;
+    const int nn = ro.n_cap + ro.n_tag;
+    std::vector<int> par(nn);
+    for (int i = 0; i < nn; ++i) par[i] = i;
     const auto find = [&](int a) {
       while (par[a] != a) a = par[a] = par[par[a]];
       return a;
     };
-    std::vector<unsigned char> used(nc + nt, 0);
+    std::vector<unsigned char> used(nn, 0);
     for (int c = 0; c < nc; ++c)
       for (int q = h_cs[c]; q < h_cs[c + 1]; ++q) {
         if (!h_act[q]) continue;
-        used[c] = used[nc + h_ot[q]] = 1;
-        const int a = find(c), b = find(nc + h_ot[q]);
+        const int ne = ro.e_node[c], nf = ro.f_node[h_ot[q]];
+        used[ne] = used[nf] = 1;
+        const int a = find(ne), b = find(nf);
         if (a != b) par[a] = b;
       }
-    std::vector<unsigned char> anchored(nc + nt, 0), needs(nc + nt, 0);
-    for (int i = 0; i < nc + nt; ++i) {
-      const bool fr = i < nc ? cov_e_free(i) : cov_f_free(i - nc);
+    std::vector<unsigned char> anchored(nn, 0), needs(nn, 0);
+    for (int i = 0; i < nn; ++i) {
+      const bool cap = i < ro.n_cap;
+      const int role = ro.role(cap, cap ? i : i - ro.n_cap), idx = ro.idx(cap, cap ? i : i - ro.n_cap);
+      const bool fr = (role == arslam::kCovE ? cov_e_free(idx) : cov_f_free(idx)) && !cf.is_anchor(role, idx);
       if (fr) needs[find(i)] = 1;
       else if (used[i]) anchored[find(i)] = 1;
     }
-    for (int i = 0; i < nc + nt; ++i) deficient = deficient || (needs[i] && !anchored[i]);
+    for (int i = 0; i < nn; ++i) deficient = deficient || (needs[i] && !anchored[i]);
   }
   cf.deficient = deficient;
   cf.factored = false;
@@ -89,15 +163,39 @@ void arslam_lm::cov_factor(CovFactor &cf, bool lens, bool assemble_only) {
   std::vector<double> dg(n);
   for (long i = 0; i < n; ++i) dg[i] = slot_free[i] ? 0.0 : 1.0;
   dg[1] = dg[2] = cf.live ? 0.0 : 1.0;
+  // an anchored call: its scale copy (0 on the anchor and on the direct groups'
+  // copies of their captures' slots), the diagonal 1 on the anchor's slots
+  std::vector<int> direct;
+  if (an) {
+    if (cf.anchor_slot >= 0)
+      for (int j = 0; j < 6; ++j) {
+        h_scale[cf.anchor_slot + j] = 0.0;
+        dg[cf.anchor_slot + j] = 1.0;
+      }
+    if (elim_used == ARSLAM_ELIM_MIXED)
+      for (int g = 0; g < nc; ++g)
+        if (mx.kind[g] == arslam::kMixDirect) {
+          direct.push_back(g);
+          std::fill(h_scale.begin() + 3 + 6L * g, h_scale.begin() + 9 + 6L * g, 0.0);
+        }
+    d_cov_scale.alloc(n);
+    d_cov_scale.upload(h_scale.data(), n, stream);
+    cf.scale = d_cov_scale.p;
+    if (!direct.empty()) {
+      d_cov_direct.alloc(direct.size());
+      d_cov_direct.upload(direct.data(), direct.size(), stream);
+    }
+  }
   d_cov_diag.alloc(n);
   HIP_CHECK(hipMemcpyAsync(d_cov_diag.p, dg.data(), n * sizeof(double), hipMemcpyHostToDevice, stream));
   d_cov_Q.alloc(std::max(48L * nb, 1L));
   d_cov_Y.alloc(std::max(6L * (nc + 6L * n_blk), 1L));
   d_cov_R.alloc(std::max(36L * nc, 1L));
-  arslam::launch_cov_schur(P, d_scale.p, d_cov_Q.p, d_cov_Y.p, d_cov_R.p, has_f, stream);
+  arslam::launch_cov_schur(P, cf.scale, d_cov_Q.p, d_cov_Y.p, d_cov_R.p, has_f, stream);
+  if (has_f && !direct.empty()) arslam::launch_cov_direct(P, cf.scale, d_cov_direct.p, (int)direct.size(), stream);
   if (cf.live) {
     d_cov_Gl.alloc(12L * std::max(nc, 1));
-    arslam::launch_cov_schur_cam(P, CL, d_scale.p, d_cov_Q.p, d_cov_Y.p, d_cov_Gl.p, stream);
+    arslam::launch_cov_schur_cam(P, CL, cf.scale, d_cov_Q.p, d_cov_Y.p, d_cov_Gl.p, stream);
   }
   if (has_f) {
     const bool dag = opt.factor_executor == 1;
@@ -144,6 +242,7 @@ void arslam_lm::cov_numeric_test(CovFactor &cf) {
       for (long r = 0; r < (has_f ? nR : 0); ++r) {
         const int sl = lay.row_slot[r];
         if (sl < 0 || (!cf.live && (sl == 1 || sl == 2))) continue;
+        if (cf.anchor_slot >= 0 && sl >= cf.anchor_slot && sl < cf.anchor_slot + 6) continue;   // (identity rows)
         const double l = ld[(size_t)(r >> 6) * 4096 + (r & 63) * 65];
         const double p2 = l * l;
         if (first || !(p2 >= mp)) mp = p2;   // (a NaN pivot stays)
@@ -162,11 +261,16 @@ void arslam_lm::cov_numeric_test(CovFactor &cf) {
 // order.  lens: arslam_lm_covariance_lens -- with l1, l2 live the lens
 // instances of the block kernels and the camera's 3x3; held, the same launches
 // as without it, var(f) at [0] of the 3x3.
-void arslam_lm::covariance(bool lens) {
-  cov_check_state(lens ? "covariance_lens" : "covariance", lens);
+// an: arslam_lm_covariance_anchored -- cov_factor's anchored path, every block
+// kernel on the call's scale copy, the anchor's outputs overridden here.
+void arslam_lm::covariance(bool lens, const CovAnchor *an) {
+  const char *who = an ? "covariance_anchored" : lens ? "covariance_lens" : "covariance";
+  cov_check_state(who, lens, an != nullptr);
+  if (an) cov_check_anchor(who, *an, cov_roles());
   cov_valid = false;
+  cov_anch_valid = false;
   CovFactor cf;
-  cov_factor(cf, lens);
+  cov_factor(cf, lens, false, an);
   arslam_lm_cov_info &info = cf.info;
   const int n_cam = cf.live ? 9 : 1;   // the tail of d_cov_out: the camera's 3x3, or var(f)
   std::vector<double> out(36L * nc + 36L * nt + n_cam, -1.0);
@@ -187,11 +291,11 @@ void arslam_lm::covariance(bool lens) {
     d_cov_out.alloc(out.size());
     d_cov_status.alloc(std::max(nc, 1));
     if (cf.live)
-      arslam::launch_cov_blocks_lens(P, d_cov_Z.p, d_scale.p, d_cov_Y.p, d_cov_R.p, d_cov_Gl.p, d_cov_out.p,
+      arslam::launch_cov_blocks_lens(P, d_cov_Z.p, cf.scale, d_cov_Y.p, d_cov_R.p, d_cov_Gl.p, d_cov_out.p,
                                      d_cov_status.p, d_cov_out.p + 36L * nc, d_cov_out.p + 36L * nc + 36L * nt, d_flag.p,
                                      stream);
     else
-      arslam::launch_cov_blocks(P, has_f ? d_cov_Z.p : nullptr, d_scale.p, d_cov_Y.p, d_cov_R.p, d_cov_out.p, d_cov_status.p,
+      arslam::launch_cov_blocks(P, has_f ? d_cov_Z.p : nullptr, cf.scale, d_cov_Y.p, d_cov_R.p, d_cov_out.p, d_cov_status.p,
                                 d_cov_out.p + 36L * nc, d_cov_out.p + 36L * nc + 36L * nt, d_flag.p, stream);
     HIP_CHECK(hipEventRecord(cov_ev[4], stream));
     HIP_CHECK(hipMemcpyAsync(out.data(), d_cov_out.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -206,19 +310,29 @@ void arslam_lm::covariance(bool lens) {
   }
   const bool deficient = cf.deficient;
   if (deficient) std::fill(out.begin(), out.end(), -1.0);
-  // statuses in the device problem's order, then the caller's arrays (tag
-  // elimination: the e-blocks are the caller's tags)
+  // statuses in the device problem's order, then the caller's arrays, each
+  // block from its role in the device problem (CovRoles; a mixed set's direct
+  // groups are nobody's block); the call's anchor is UNAVAILABLE, -1 in its values
   std::vector<int> se(nc), sf(nt);
   for (int c = 0; c < nc; ++c)
     se[c] = !cov_e_free(c) ? ARSLAM_COV_UNAVAILABLE : (deficient || st_e[c] == 2) ? ARSLAM_COV_RANK_DEFICIENT : ARSLAM_COV_OK;
   for (int t = 0; t < nt; ++t)
     sf[t] = !cov_f_free(t) ? ARSLAM_COV_UNAVAILABLE : deficient ? ARSLAM_COV_RANK_DEFICIENT : ARSLAM_COV_OK;
-  const bool swapped = elim_used == ARSLAM_ELIM_TAGS;
-  std::vector<double> ce(out.begin(), out.begin() + 36L * nc), cf_(out.begin() + 36L * nc, out.begin() + 36L * (nc + nt));
-  cov_cap = swapped ? cf_ : ce;
-  cov_tag = swapped ? ce : cf_;
-  cov_cap_status = swapped ? sf : se;
-  cov_tag_status = swapped ? se : sf;
+  const CovRoles &ro = cf.roles;
+  const auto to_caller = [&](bool cap, std::vector<double> &cv, std::vector<int> &sv) {
+    const int nblk = cap ? ro.n_cap : ro.n_tag;
+    cv.assign(36L * nblk, -1.0);
+    sv.assign(nblk, ARSLAM_COV_UNAVAILABLE);
+    for (int i = 0; i < nblk; ++i) {
+      const int role = ro.role(cap, i), idx = ro.idx(cap, i);
+      if (idx < 0 || cf.is_anchor(role, idx)) continue;
+      const double *src = out.data() + (role == arslam::kCovE ? 36L * idx : 36L * nc + 36L * idx);
+      sv[i] = role == arslam::kCovE ? se[idx] : sf[idx];
+      if (sv[i] == ARSLAM_COV_OK) std::copy(src, src + 36, cv.begin() + 36L * i);
+    }
+  };
+  to_caller(true, cov_cap, cov_cap_status);
+  to_caller(false, cov_tag, cov_tag_status);
   // the camera: its 3x3 over [f, l1, l2] (held l1, l2: their rows and columns 0), and var(f)
   const double *tail = out.data() + 36L * (nc + nt);
   const bool cam_free = has_f && P.cam_row >= 0;
@@ -234,7 +348,9 @@ void arslam_lm::covariance(bool lens) {
   cov_var_f = cf.live ? cov_cam[0] : tail[0];
   cov_from_lens = lens;
   cov_info = info;
-  cov_valid = true;
+  cov_valid = an == nullptr;
+  cov_anch_valid = an != nullptr;
+  if (an) cov_anch = *an;
 }
 
 // Cross-covariance blocks of the same matrix (arslam_lm.h): cov_factor, then
@@ -255,11 +371,13 @@ void arslam_lm::covariance(bool lens) {
 // with l1, l2 live its right-hand side is three unit columns and the lens
 // instances of the two small kernels run (cov_lens.hip).
 void arslam_lm::covariance_pairs(const arslam_lm_cov_pair *pairs, int n_pairs, double *cov, int *status,
-                                 arslam_lm_cov_info *info_out, bool lens) {
-  cov_check_state(lens ? "covariance_pairs_lens" : "covariance_pairs", lens);
-  const bool swapped = elim_used == ARSLAM_ELIM_TAGS;
-  const int n_caller_cap = swapped ? nt : nc, n_caller_tag = swapped ? nc : nt;
-  // the caller's block in the device problem: {role, idx} (tag elimination: the e-blocks are the caller's tags)
+                                 arslam_lm_cov_info *info_out, bool lens, const CovAnchor *an) {
+  const char *who = an ? "covariance_pairs_anchored" : lens ? "covariance_pairs_lens" : "covariance_pairs";
+  cov_check_state(who, lens, an != nullptr);
+  const CovRoles ro = cov_roles();
+  if (an) cov_check_anchor(who, *an, ro);
+  const int n_caller_cap = ro.n_cap, n_caller_tag = ro.n_tag;
+  // the caller's block in the device problem: {role, idx} (CovRoles: per block, under any e-block set)
   struct Blk {
     int role, idx;
     long key() const { return role == arslam::kCovFocal ? 0L : role == arslam::kCovF ? 1L + idx : (1L << 40) + idx; }
@@ -274,7 +392,7 @@ void arslam_lm::covariance_pairs(const arslam_lm_cov_pair *pairs, int n_pairs, d
     const bool cap = kind == ARSLAM_BLOCK_CAPTURE;
     fail_if(index < 0 || index >= (cap ? n_caller_cap : n_caller_tag), ARSLAM_E_INVALID_ARG,
             "covariance_pairs: block index out of range");
-    return Blk{cap != swapped ? arslam::kCovE : arslam::kCovF, index};
+    return Blk{ro.role(cap, index), ro.idx(cap, index)};
   };
   std::vector<Blk> blk(2L * n_pairs);
   for (int i = 0; i < n_pairs; ++i) {
@@ -282,10 +400,11 @@ void arslam_lm::covariance_pairs(const arslam_lm_cov_pair *pairs, int n_pairs, d
     blk[2L * i + 1] = device_block(pairs[i].kind_b, pairs[i].index_b);
   }
   CovFactor cf;
-  cov_factor(cf, lens);
+  cov_factor(cf, lens, false, an);
   const bool live = cf.live;
   const auto available = [&](const Blk &b) {
     if (b.role == arslam::kCovFocal) return has_f && P.cam_row >= 0;
+    if (cf.is_anchor(b.role, b.idx)) return false;   // (held fixed for this call)
     if (b.role == arslam::kCovF)
       return has_f && cov_f_free(b.idx) && (size_t)b.idx < lay.tag_row.size() && lay.tag_row[b.idx] >= 0;
     return cov_e_free(b.idx) && cf.cap_start[b.idx + 1] > cf.cap_start[b.idx];
@@ -409,10 +528,10 @@ void arslam_lm::covariance_pairs(const arslam_lm_cov_pair *pairs, int n_pairs, d
           info.n_selinv_products += arslam::tile_solve_products(plan, cov_tp, active + m0 + (size_t)p * T, needed + m0 + (size_t)p * T);
       }
       if (live)
-        arslam::launch_cov_pair_blocks_lens(P, d_pair_B.p, d_scale.p, d_cov_Y.p, d_cov_R.p, d_cov_Gl.p, d_pair_tasks.p + t0,
+        arslam::launch_cov_pair_blocks_lens(P, d_pair_B.p, cf.scale, d_cov_Y.p, d_cov_R.p, d_cov_Gl.p, d_pair_tasks.p + t0,
                                             t1 - t0, d_pair_out.p, d_pair_status.p, d_flag.p, stream);
       else
-        arslam::launch_cov_pair_blocks(P, has_f ? d_pair_B.p : nullptr, d_scale.p, d_cov_Y.p, d_cov_R.p, d_pair_tasks.p + t0,
+        arslam::launch_cov_pair_blocks(P, has_f ? d_pair_B.p : nullptr, cf.scale, d_cov_Y.p, d_cov_R.p, d_pair_tasks.p + t0,
                                        t1 - t0, d_pair_out.p, d_pair_status.p, d_flag.p, stream);
       t0 = t1;
     }

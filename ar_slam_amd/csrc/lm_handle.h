@@ -546,11 +546,45 @@ struct arslam_lm {
   int cov_cam_status = ARSLAM_COV_UNAVAILABLE;
   bool cov_from_lens = false;
   arslam_lm_cov_info cov_info{};
-  void covariance(bool lens = false);
+  // The anchored forms (arslam_lm_covariance_anchored): the pose block held
+  // fixed for one call besides the constant ones (kind ARSLAM_BLOCK_CAPTURE,
+  // _TAG or _NONE, the caller's index).  Their kept result lives in the same
+  // arrays under a flag of its own (cov_anch_valid, with the anchor it was
+  // computed for): the other pointer-keyed forms never serve it, nor it theirs.
+  struct CovAnchor {
+    int kind = ARSLAM_BLOCK_NONE, index = 0;
+    bool none() const { return kind == ARSLAM_BLOCK_NONE; }
+    bool operator==(const CovAnchor &o) const { return kind == o.kind && (none() || index == o.index); }
+  };
+  bool cov_anch_valid = false;
+  CovAnchor cov_anch{};
+  // allocated at the first anchored call: the call's copy of the Jacobi scale
+  // (0 on the anchor's slots and on the direct groups' copies) and, under a
+  // mixed e-block set, its direct groups
+  DevBuf<double> d_cov_scale;
+  DevBuf<int> d_cov_direct;
+  void covariance(bool lens = false, const CovAnchor *an = nullptr);
   void cov_invalidate() {
     solve_state = 0;
     cov_valid = false;
+    cov_anch_valid = false;
   }
+  // The caller's blocks in the device problem: per capture and tag the role
+  // (arslam::kCovE: a group's eliminated block, kCovF: an f-block) and the
+  // index there, from elim_used (whole sides) or mx (a mixed set: kind,
+  // group_src, f_src, f_is_cap); a reduced capture is kCovF.  e_node / f_node:
+  // the caller's block (capture c: c, tag t: n_cap + t) of each group and
+  // f-block -- a direct group's is its capture's, the block its f-block is.
+  struct CovRoles {
+    int n_cap = 0, n_tag = 0;
+    std::vector<int> cap_role, cap_idx, tag_role, tag_idx;
+    std::vector<int> e_node, f_node;
+    int role(bool cap, int i) const { return cap ? cap_role[i] : tag_role[i]; }
+    int idx(bool cap, int i) const { return cap ? cap_idx[i] : tag_idx[i]; }
+  };
+  CovRoles cov_roles() const;
+  // the anchor as the calls accept it (throws ARSLAM_E_INVALID_ARG otherwise)
+  void cov_check_anchor(const char *who, const CovAnchor &an, const CovRoles &ro) const;
   // What covariance() and covariance_pairs() share (lm_covariance.hip):
   // cov_check_state: the calls' preconditions.  cov_factor: the structural
   // gauge check, then -- unless it fails -- the linearization at xbest,
@@ -564,11 +598,23 @@ struct arslam_lm {
     bool factored = false;        // the device work was enqueued
     bool live = false;            // a _lens call on a problem whose l1, l2 are estimated: they are rows of H
     arslam_lm_cov_info info{};
+    CovRoles roles;
+    // the Jacobi scale every covariance kernel of the call reads: the handle's,
+    // or an anchored call's copy (d_cov_scale)
+    const double *scale = nullptr;
+    // an anchored call's anchor in the device problem: its role, index and
+    // first slot; role -1: none
+    int anchor_role = -1, anchor_idx = -1;
+    long anchor_slot = -1;
+    bool is_anchor(int role, int idx) const { return anchor_role >= 0 && role == anchor_role && idx == anchor_idx; }
   };
   bool cov_e_free(int c) const { return slot_free[3 + 6L * c] != 0; }
   bool cov_f_free(int t) const { return slot_free[3 + 6L * nc + 6L * t] != 0; }
-  void cov_check_state(const char *who, bool lens = false) const;
-  void cov_factor(CovFactor &cf, bool lens = false, bool assemble_only = false);
+  // (anchored: the anchored forms take the mixed e-block set too)
+  void cov_check_state(const char *who, bool lens = false, bool anchored = false) const;
+  // (an: an anchored form's call, its anchor possibly NONE -- the call's scale
+  // copy, the direct groups' kernel and the anchor held fixed)
+  void cov_factor(CovFactor &cf, bool lens = false, bool assemble_only = false, const CovAnchor *an = nullptr);
   void cov_numeric_test(CovFactor &cf);
 
   // ---- cross-covariance blocks (arslam_lm_covariance_pairs) ----
@@ -584,7 +630,7 @@ struct arslam_lm {
   DevBuf<int> d_pair_status;
   std::vector<hipEvent_t> pair_ev;   // two per batch, around its solve
   void covariance_pairs(const arslam_lm_cov_pair *pairs, int n_pairs, double *cov, int *status,
-                        arslam_lm_cov_info *info, bool lens = false);
+                        arslam_lm_cov_info *info, bool lens = false, const CovAnchor *an = nullptr);
 
   // ---- Evaluate (arslam_lm_evaluate*, lm_evaluate.hip) ----
   // A path of its own: the problem's structure in the caller's order, its own

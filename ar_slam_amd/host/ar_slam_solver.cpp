@@ -217,6 +217,7 @@ void ArSlamSolver::loadYaml(const std::string &fn) {
 }
 
 void ArSlamSolver::loadYamlString(const std::string &text) {   // :304-384
+  dropCovariance();
   const yaml::Node doc = yaml::parse(text);
   if (const yaml::Node *caps = doc.find("captures")) {
     for (const auto &kv : caps->map) {
@@ -320,6 +321,7 @@ void ArSlamSolver::saveYaml(std::ostream &y) const {   // :387-465 (yaml-cpp emi
 }
 
 std::optional<CaptureHandle> ArSlamSolver::addDetections(const Detections &d) {   // :591-627
+  dropCovariance();
   if (d.detections.empty()) return std::nullopt;
   const ImageSize image_size{(int)d.image_width, (int)d.image_height};
   if (camera_.size) {
@@ -342,6 +344,7 @@ std::optional<CaptureHandle> ArSlamSolver::addDetections(const Detections &d) { 
 }
 
 void ArSlamSolver::solveIncremental() {   // :629-678
+  dropCovariance();
   // make sure at least one capture is solved: the seed is the set's begin()
   // (libstdc++ bucket order, as in the reference)
   if (!unsolved_captures_.empty() && unsolved_captures_.size() == captures_.size()) {
@@ -370,6 +373,7 @@ void ArSlamSolver::solveIncremental() {   // :629-678
 }
 
 void ArSlamSolver::addCaptureBlocks(Capture &capture) {   // block loop of :704-735 / :826-843
+  dropCovariance();
   for (BlockHandle bh : capture.blocks) {
     Block &block = at(bh);
     Aruco &aruco = at(block.aruco);
@@ -409,6 +413,115 @@ int ArSlamSolver::evaluate(double *cost, double *sq_norm, double *weight) {
   return ARSLAM_OK;
 }
 
+bool kept_anchored_cov_info(const arslam_lm *h, arslam_lm_cov_info *info);   // lm_capi.hip
+
+void ArSlamSolver::problemMembers(std::vector<char> &caps, std::vector<char> &arucos) const {
+  caps.assign(captures_.size(), 0);
+  arucos.assign(arucos_.size(), 0);
+  for (unsigned b : problem_blocks_) {
+    caps[blocks_[b].capture.idx] = 1;
+    arucos[blocks_[b].aruco.idx] = 1;
+  }
+}
+
+// was: problem_.SetParameterBlockConstant(anchor); ceres::Covariance::Compute; GetCovarianceBlock(p, p) per block
+int ArSlamSolver::covariance(int anchor_aruco, arslam_lm_cov_info *info) {
+  cov_valid_ = false;
+  if (problem_blocks_.empty()) return ARSLAM_E_STATE;
+  std::vector<char> in_cap, in_ar;
+  problemMembers(in_cap, in_ar);
+  if (anchor_aruco < 0 || anchor_aruco >= (int)arucos_.size() || !in_ar[anchor_aruco]) return ARSLAM_E_INVALID_ARG;
+  const double *anchor = arucos_[anchor_aruco].data();
+  // the first request computes on the device and keeps every block on the lm
+  // handle; the others are served from it (the same anchor)
+  int rc = arslam_lm_covariance_block_anchored(problem_, anchor, camera_.params.data(), cov_cam_, &cov_cam_status_);
+  if (rc != ARSLAM_OK) return rc;
+  cov_cap_.assign(36 * captures_.size(), -1.0);
+  cov_aruco_.assign(36 * arucos_.size(), -1.0);
+  cov_cap_status_.assign(captures_.size(), ARSLAM_COV_UNAVAILABLE);
+  cov_aruco_status_.assign(arucos_.size(), ARSLAM_COV_UNAVAILABLE);
+  for (size_t c = 0; c < captures_.size(); ++c) {
+    if (!in_cap[c]) continue;
+    rc = arslam_lm_covariance_block_anchored(problem_, anchor, captures_[c].data(), &cov_cap_[36 * c], &cov_cap_status_[c]);
+    if (rc != ARSLAM_OK) return rc;
+  }
+  for (size_t a = 0; a < arucos_.size(); ++a) {
+    if (!in_ar[a]) continue;
+    rc = arslam_lm_covariance_block_anchored(problem_, anchor, arucos_[a].data(), &cov_aruco_[36 * a], &cov_aruco_status_[a]);
+    if (rc != ARSLAM_OK) return rc;
+  }
+  if (info && !kept_anchored_cov_info(problem_, info)) return ARSLAM_E_STATE;
+  cov_valid_ = true;
+  return ARSLAM_OK;
+}
+
+int ArSlamSolver::arucoCovariance(int a, double cov[36], int *status) const {
+  if (a < 0 || a >= (int)arucos_.size()) return ARSLAM_E_INVALID_ARG;
+  if (!cov_valid_ || (size_t)a >= cov_aruco_status_.size()) return ARSLAM_E_STATE;
+  if (cov) std::copy(cov_aruco_.begin() + 36 * a, cov_aruco_.begin() + 36 * a + 36, cov);
+  if (status) *status = cov_aruco_status_[a];
+  return ARSLAM_OK;
+}
+
+int ArSlamSolver::captureCovariance(int c, double cov[36], int *status) const {
+  if (c < 0 || c >= (int)captures_.size()) return ARSLAM_E_INVALID_ARG;
+  if (!cov_valid_ || (size_t)c >= cov_cap_status_.size()) return ARSLAM_E_STATE;
+  if (cov) std::copy(cov_cap_.begin() + 36 * c, cov_cap_.begin() + 36 * c + 36, cov);
+  if (status) *status = cov_cap_status_[c];
+  return ARSLAM_OK;
+}
+
+int ArSlamSolver::cameraCovariance(double cov[9], int *status) const {
+  if (!cov_valid_) return ARSLAM_E_STATE;
+  if (cov) std::copy(cov_cam_, cov_cam_ + 9, cov);
+  if (status) *status = cov_cam_status_;
+  return ARSLAM_OK;
+}
+
+// was: Compute({{a, b}}) + GetCovarianceBlock(a, b) with the anchor held constant
+int ArSlamSolver::covariancePair(int anchor_aruco, int kind_a, int idx_a, int kind_b, int idx_b, double cov[36],
+                                 int *status) {
+  if (problem_blocks_.empty()) return ARSLAM_E_STATE;
+  std::vector<char> in_cap, in_ar;
+  problemMembers(in_cap, in_ar);
+  if (anchor_aruco < 0 || anchor_aruco >= (int)arucos_.size() || !in_ar[anchor_aruco]) return ARSLAM_E_INVALID_ARG;
+  const double *ptr[2] = {nullptr, nullptr};
+  int width[2] = {6, 6};
+  bool present = true;
+  const int kind[2] = {kind_a, kind_b}, idx[2] = {idx_a, idx_b};
+  for (int s = 0; s < 2; ++s) {
+    if (kind[s] == ARSLAM_BLOCK_CAMERA) {
+      if (idx[s] != 0) return ARSLAM_E_INVALID_ARG;
+      ptr[s] = camera_.params.data();
+      width[s] = 3;
+    } else if (kind[s] == ARSLAM_BLOCK_CAPTURE) {
+      if (idx[s] < 0 || idx[s] >= (int)captures_.size()) return ARSLAM_E_INVALID_ARG;
+      ptr[s] = captures_[idx[s]].data();
+      present = present && in_cap[idx[s]];
+    } else if (kind[s] == ARSLAM_BLOCK_TAG) {
+      if (idx[s] < 0 || idx[s] >= (int)arucos_.size()) return ARSLAM_E_INVALID_ARG;
+      ptr[s] = arucos_[idx[s]].data();
+      present = present && in_ar[idx[s]];
+    } else {
+      return ARSLAM_E_INVALID_ARG;
+    }
+  }
+  int st = ARSLAM_COV_UNAVAILABLE;
+  double c[36];
+  std::fill(c, c + 36, -1.0);
+  if (present) {
+    const int rc = arslam_lm_covariance_block_pair_anchored(problem_, arucos_[anchor_aruco].data(), ptr[0], ptr[1], c, &st);
+    if (rc != ARSLAM_OK) return rc;
+  }
+  if (cov) {
+    std::fill(cov, cov + 36, st == ARSLAM_COV_OK ? 0.0 : -1.0);
+    if (st == ARSLAM_COV_OK)   // (Ceres' shape, width[0] x width[1], into the top-left of the 6x6)
+      for (int r = 0; r < width[0]; ++r) std::copy(c + width[1] * r, c + width[1] * r + width[1], cov + 6 * r);
+  }
+  if (status) *status = st;
+  return ARSLAM_OK;
+}
+
 void ArSlamSolver::solveCapture(Capture &capture, std::optional<BlockHandle> init_block) {   // :680-742
   if (init_block) {
     const Block &block = at(*init_block);
@@ -420,6 +533,7 @@ void ArSlamSolver::solveCapture(Capture &capture, std::optional<BlockHandle> ini
 }
 
 void ArSlamSolver::solve() {   // :744-866
+  dropCovariance();
   if (captures_.empty()) return;
   std::deque<CaptureHandle> open_captures;
   unsigned best_cap_idx = 0;
@@ -460,6 +574,7 @@ void ArSlamSolver::addConnectedCaptures(const Capture &base, std::deque<CaptureH
 }
 
 void ArSlamSolver::localizeMany(unsigned first_loc_cap_idx) {   // :888-901, each query as localizeOne :903-979
+  dropCovariance();
   // Every localizeOne resets the problem and holds the tags and the camera
   // constant, so the queries are independent: they run as one device batch.
   const unsigned n = (unsigned)captures_.size();
@@ -549,6 +664,7 @@ int ArSlamSolver::localizeCovariance(unsigned cap_idx, double cov[36], int *cov_
 }
 
 void ArSlamSolver::optimize(const Capture &capture) {   // :1001-1018
+  dropCovariance();
   arslam_lm_options o = options_;
   o.max_num_iterations = 50;                      // :1004
   // DENSE_SCHUR (:1011) eliminates Ceres' own e-block set: ARSLAM_ELIM_MIXED
@@ -566,7 +682,10 @@ void ArSlamSolver::optimize(const Capture &capture) {   // :1001-1018
   solve_log_.push_back(std::move(rec));
 }
 
-int ArSlamSolver::setLoss(int kind, double a) { return arslam_lm_set_loss(problem_, kind, a); }
+int ArSlamSolver::setLoss(int kind, double a) {
+  dropCovariance();
+  return arslam_lm_set_loss(problem_, kind, a);
+}
 
 int ArSlamSolver::setLocalizeLoss(int kind, double a) {
   if (!loss_valid(kind, a)) return ARSLAM_E_INVALID_ARG;
@@ -583,6 +702,7 @@ int ArSlamSolver::setCameraModel(int model) {
   const int rc = arslam_lm_set_camera_model(problem_, model);
   if (rc != ARSLAM_OK) return rc;
   camera_model_ = model;
+  dropCovariance();
   dropLocalizer();   // (the last localizeMany's batch was solved under the other model)
   return ARSLAM_OK;
 }
@@ -615,6 +735,7 @@ int ArSlamSolver::setArucoSize(const std::string &id, double size) {
 }
 
 void ArSlamSolver::resetProblem() {   // :1021-1025
+  dropCovariance();
   check(arslam_lm_reset(problem_));
   problem_blocks_.clear();
 }

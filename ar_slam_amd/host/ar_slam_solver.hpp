@@ -215,6 +215,28 @@ class ArSlamSolver {
   // added, or localized by localizeMany, which adds none).  All nullable.
   // Returns arslam_lm_evaluate_blocks' code (ARSLAM_E_STATE: no block added yet).
   int evaluate(double *cost, double *sq_norm, double *weight);
+  // The mapper problem's covariance in the gauge of one aruco (the reference
+  // holds no block constant): SetParameterBlockConstant(anchor) +
+  // ceres::Covariance::Compute over every block, without touching the problem
+  // (arslam_lm_covariance_block_anchored, which works under the mixed e-block
+  // set the solves run).  Valid after solve() or solveIncremental().
+  // covariance() computes and keeps the 6x6 block of every capture and aruco
+  // and the camera's 3x3; the getters serve the kept result.  anchor_aruco must
+  // be an aruco with residual blocks in the problem: else ARSLAM_E_INVALID_ARG.
+  // A capture or aruco that is not in the problem (not yet added, or localized
+  // by localizeMany) is ARSLAM_COV_UNAVAILABLE, -1 in its values, as is the
+  // anchor itself.  Whatever changes the problem or its values (addDetections,
+  // a solve, localizeMany, a loss, the camera model, a map file, the pose
+  // setters: dropCovariance) drops the kept result; the getters then return
+  // ARSLAM_E_STATE.  covariancePair: block (a, b) in that gauge, kinds
+  // ARSLAM_BLOCK_CAMERA (index 0), _CAPTURE, _TAG (an aruco), 36 values as
+  // arslam_lm_covariance_pairs_anchored lays them out; computes on every call.
+  int covariance(int anchor_aruco, arslam_lm_cov_info *info);
+  int arucoCovariance(int a, double cov[36], int *status) const;
+  int captureCovariance(int c, double cov[36], int *status) const;
+  int cameraCovariance(double cov[9], int *status) const;
+  int covariancePair(int anchor_aruco, int kind_a, int idx_a, int kind_b, int idx_b, double cov[36], int *status);
+  void dropCovariance() { cov_valid_ = false; }
 
   // data-store builders (protected in the reference; public here so a host
   // or test can assemble a problem without ROS messages)
@@ -257,6 +279,14 @@ class ArSlamSolver {
   unsigned loc_first_ = 0, loc_count_ = 0;
   std::vector<double> loc_cov_;
   std::vector<int> loc_cov_status_;
+  // covariance(): the kept result, by capture and aruco index
+  bool cov_valid_ = false;
+  std::vector<double> cov_cap_, cov_aruco_;
+  std::vector<int> cov_cap_status_, cov_aruco_status_;
+  double cov_cam_[9] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};
+  int cov_cam_status_ = ARSLAM_COV_UNAVAILABLE;
+  // the captures and arucos with residual blocks in problem_ (1 per index)
+  void problemMembers(std::vector<char> &caps, std::vector<char> &arucos) const;
 };
 
 // initialisers (ar_slam_util.cpp:41-128)

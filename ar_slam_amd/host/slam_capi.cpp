@@ -194,6 +194,51 @@ int arslam_slam_localize_covariance(arslam_slam *h, int cap_idx, double cov[36],
   return g ? g : rc;
 }
 
+int arslam_slam_covariance(arslam_slam *h, int anchor_aruco, arslam_lm_cov_info *info) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  int rc = ARSLAM_OK;
+  const int g = slam_guarded([&] { rc = h->s.covariance(anchor_aruco, info); });
+  if (!g && rc == ARSLAM_E_INVALID_ARG)
+    arslam::set_last_error("covariance: the anchor must be an aruco with residual blocks in the mapper problem");
+  if (!g && rc == ARSLAM_E_STATE && h->s.numBlocks() == 0)
+    arslam::set_last_error("covariance: no residual block has been added: solve first");
+  return g ? g : rc;   // (otherwise the lm call set the message)
+}
+
+namespace {
+int kept_cov_code(int rc) {
+  if (rc == ARSLAM_E_STATE)
+    arslam::set_last_error("no kept covariance: call arslam_slam_covariance after the last change of the problem");
+  return rc;
+}
+}  // namespace
+
+int arslam_slam_aruco_covariance(const arslam_slam *h, int a, double cov[36], int *status) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return kept_cov_code(h->s.arucoCovariance(a, cov, status));
+}
+
+int arslam_slam_capture_covariance(const arslam_slam *h, int c, double cov[36], int *status) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return kept_cov_code(h->s.captureCovariance(c, cov, status));
+}
+
+int arslam_slam_camera_covariance(const arslam_slam *h, double cov[9], int *status) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  return kept_cov_code(h->s.cameraCovariance(cov, status));
+}
+
+int arslam_slam_covariance_pair(arslam_slam *h, int anchor_aruco, int kind_a, int idx_a, int kind_b, int idx_b,
+                                double cov[36], int *status) {
+  if (!h) return ARSLAM_E_INVALID_ARG;
+  int rc = ARSLAM_OK;
+  const int g = slam_guarded([&] { rc = h->s.covariancePair(anchor_aruco, kind_a, idx_a, kind_b, idx_b, cov, status); });
+  if (!g && rc == ARSLAM_E_INVALID_ARG)
+    arslam::set_last_error("covariance_pair: an anchor aruco with residual blocks in the mapper problem, kinds "
+                           "ARSLAM_BLOCK_CAMERA (index 0), _CAPTURE or _TAG, indices in range");
+  return g ? g : rc;
+}
+
 int arslam_slam_evaluate(arslam_slam *h, double *cost, double *sq_norm, double *weight) {
   if (!h) return ARSLAM_E_INVALID_ARG;
   int rc = ARSLAM_OK;
@@ -247,6 +292,7 @@ int arslam_slam_capture(const arslam_slam *h, int c, char *uid, int cap, double 
 int arslam_slam_set_capture_pose(arslam_slam *h, int c, const double inv_pose[6]) {
   if (!h || !inv_pose || c < 0 || c >= (int)h->s.numCaptures()) return ARSLAM_E_INVALID_ARG;
   std::memcpy(h->s.at(arslam::CaptureHandle{(unsigned)c}).data(), inv_pose, 6 * sizeof(double));
+  h->s.dropCovariance();
   return ARSLAM_OK;
 }
 
@@ -262,6 +308,7 @@ int arslam_slam_aruco(const arslam_slam *h, int a, char *id, int cap, double pos
 int arslam_slam_set_aruco_pose(arslam_slam *h, int a, const double pose[6]) {
   if (!h || !pose || a < 0 || a >= (int)h->s.numArucos()) return ARSLAM_E_INVALID_ARG;
   std::memcpy(h->s.at(arslam::ArucoHandle{(unsigned)a}).data(), pose, 6 * sizeof(double));
+  h->s.dropCovariance();
   return ARSLAM_OK;
 }
 
@@ -288,6 +335,7 @@ int arslam_slam_camera(const arslam_slam *h, double params[3], int *width, int *
 int arslam_slam_set_camera(arslam_slam *h, const double params[3]) {
   if (!h || !params) return ARSLAM_E_INVALID_ARG;
   std::memcpy(h->s.camera().params.data(), params, 3 * sizeof(double));
+  h->s.dropCovariance();
   return ARSLAM_OK;
 }
 

@@ -36,6 +36,7 @@ DEFAULT_TAG_SIZE = 0.0635   # arslam_lm.h ARSLAM_DEFAULT_TAG_SIZE: the side of a
 CAMERA_PINHOLE, CAMERA_RADIAL = 0, 1
 COV_OK, COV_UNAVAILABLE, COV_RANK_DEFICIENT = 0, 1, 2   # arslam_lm.h, arslam_localize.h ARSLAM_COV_*
 BLOCK_CAMERA, BLOCK_CAPTURE, BLOCK_TAG = 0, 1, 2         # arslam_lm.h ARSLAM_BLOCK_* (covariance_pairs)
+BLOCK_NONE = -1                                          # arslam_lm.h ARSLAM_BLOCK_NONE (no call-time anchor)
 LOC_SKIPPED = -1                                         # arslam_localize.h ARSLAM_LOC_SKIPPED
 
 P = C.POINTER
@@ -262,6 +263,10 @@ SIGNATURES = {
     "arslam_lm_covariance_block_pair": [_vp, _dp, _dp, _dp, _ip],
     "arslam_lm_covariance_pairs_lens": [_vp, P(CovPair), _i, _dp, _ip, P(CovInfo)],
     "arslam_lm_covariance_block_pair_lens": [_vp, _dp, _dp, _dp, _ip],
+    "arslam_lm_covariance_anchored": [_vp, _i, _i, _dp, _dp, _dp, _ip, _ip, _ip, P(CovInfo)],
+    "arslam_lm_covariance_pairs_anchored": [_vp, _i, _i, P(CovPair), _i, _dp, _ip, P(CovInfo)],
+    "arslam_lm_covariance_block_anchored": [_vp, _dp, _dp, _dp, _ip],
+    "arslam_lm_covariance_block_pair_anchored": [_vp, _dp, _dp, _dp, _dp, _ip],
     "arslam_lm_evaluate_options_init": [P(EvaluateOptions)],
     "arslam_lm_evaluate": [_vp, P(EvaluateOptions), _dp, _dp, _dp, _dp, _dp],
     "arslam_lm_evaluate_blocks": [_vp, P(EvaluateOptions), _dp, _dp, _dp, _dp],
@@ -347,6 +352,11 @@ SIGNATURES = {
     "arslam_slam_solve_incremental": [_vp],
     "arslam_slam_localize_many": [_vp, _i],
     "arslam_slam_localize_covariance": [_vp, _i, _dp, _ip],
+    "arslam_slam_covariance": [_vp, _i, P(CovInfo)],
+    "arslam_slam_aruco_covariance": [_vp, _i, _dp, _ip],
+    "arslam_slam_capture_covariance": [_vp, _i, _dp, _ip],
+    "arslam_slam_camera_covariance": [_vp, _dp, _ip],
+    "arslam_slam_covariance_pair": [_vp, _i, _i, _i, _i, _i, _dp, _ip],
     "arslam_slam_evaluate": [_vp, _dp, _dp, _dp],
     "arslam_slam_num_captures": [_vp],
     "arslam_slam_num_arucos": [_vp],

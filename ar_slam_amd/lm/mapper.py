@@ -6,9 +6,12 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import (ALLREDUCE_FN, COMM_ID_BYTES, COV_OK, ITER_CB, SOLVER_ABORT, SOLVER_CONTINUE, CovInfo, CovPair,
+from ._abi import (ALLREDUCE_FN, BLOCK_NONE, COMM_ID_BYTES, COV_OK, ITER_CB, SOLVER_ABORT, SOLVER_CONTINUE, CovInfo, CovPair,
                    EvaluateOptions, Iteration, Options, SoaProblem, StepInfo, Summary, _check, _dp, _f64, _load, _Owner,
                    _ptr, lib, make_options)
+
+
+_NOT_ANCHORED = object()   # _covariance: the form is not an _anchored one (None is "anchored, no anchor")
 
 
 class _Soa:
@@ -275,7 +278,7 @@ class ResidentProblem(_Handle):
         return _evaluate(lambda *a: lib().arslam_lm_evaluate(self._h, *a), n_cap, n_tag, n_obs, apply_loss, residuals,
                          gradient)
 
-    def _covariance(self, lens):
+    def _covariance(self, lens, anchor=_NOT_ANCHORED):
         n_cap, n_tag = self.A.s.n_cap, self.A.s.n_tag
         cap = np.zeros((n_cap, 6, 6))
         tag = np.zeros((n_tag, 6, 6))
@@ -286,8 +289,11 @@ class ResidentProblem(_Handle):
         if lens:
             cam = np.zeros((3, 3))
             cam_st = C.c_int(0)
-            _check(lib().arslam_lm_covariance_lens(self._h, _ptr(cap), _ptr(tag), _ptr(cam), _ptr(cs), _ptr(ts),
-                                                   C.byref(cam_st), C.byref(info)))
+            args = (_ptr(cap), _ptr(tag), _ptr(cam), _ptr(cs), _ptr(ts), C.byref(cam_st), C.byref(info))
+            if anchor is _NOT_ANCHORED:
+                _check(lib().arslam_lm_covariance_lens(self._h, *args))
+            else:
+                _check(lib().arslam_lm_covariance_anchored(self._h, *_anchor(anchor), *args))
             out.update(cam=cam, var_f=cam[0, 0] if cam_st.value == COV_OK else -1.0, cam_status=cam_st.value)
         else:
             var_f = C.c_double(0.0)
@@ -334,6 +340,20 @@ class ResidentProblem(_Handle):
         (arslam_lm_covariance_pairs_lens): BLOCK_CAMERA is the 3-wide block [f, l1, l2] -- rows 0..2
         of the (6, 6) as a, columns 0..2 as b, the top-left (3, 3) against itself, 0 elsewhere."""
         return self._covariance_pairs(lib().arslam_lm_covariance_pairs_lens, pairs)
+
+    def covariance_anchored(self, anchor):
+        """``covariance_lens()`` in the gauge of ``anchor``: None, or (kind, index) of a capture or a
+        tag (BLOCK_CAPTURE / BLOCK_TAG) held fixed for this call besides the constant blocks
+        (arslam_lm_covariance_anchored) -- what the handle would return had that block been constant.
+        The anchor's own status is COV_UNAVAILABLE.  Works under every e-block set, ELIM_MIXED
+        included; the loaded problem and a later solve are untouched."""
+        return self._covariance(lens=True, anchor=anchor)
+
+    def covariance_pairs_anchored(self, anchor, pairs):
+        """``covariance_pairs_lens()`` in the gauge of ``anchor`` (as ``covariance_anchored``;
+        arslam_lm_covariance_pairs_anchored).  A pair that names the anchor is COV_UNAVAILABLE."""
+        kind, index = _anchor(anchor)
+        return self._covariance_pairs(lambda h, *a: lib().arslam_lm_covariance_pairs_anchored(h, kind, index, *a), pairs)
 
     def _camera_rows(self, call):
         cam = self.debug_reduced_rows()[2]
@@ -389,6 +409,14 @@ class ResidentProblem(_Handle):
     @property
     def tag(self):
         return self.A.tag
+
+
+def _anchor(anchor):
+    """(kind, index) of an anchored covariance form's anchor; None: (BLOCK_NONE, 0)."""
+    if anchor is None:
+        return BLOCK_NONE, 0
+    kind, index = anchor
+    return int(kind), int(index)
 
 
 def _block(a, n=None):
@@ -482,6 +510,19 @@ class Problem(_Handle):
         """``covariance_block_pair`` with the camera block's three rows / columns [f, l1, l2]
         (arslam_lm_covariance_block_pair_lens); works under ``set_estimate_distortion``."""
         return self._covariance_block(lib().arslam_lm_covariance_block_pair_lens, a, b)
+
+    def covariance_block_anchored(self, anchor, block):
+        """``covariance_block_lens`` in the gauge of ``anchor``, a pose block of the problem held fixed
+        for the call, or None (arslam_lm_covariance_block_anchored): SetParameterBlockConstant(anchor)
+        + Covariance::Compute without touching the problem.  Served from the kept result while the
+        anchor stays the same.  Works under every e-block set, ELIM_MIXED included."""
+        pa = None if anchor is None else _block(anchor, 6)
+        return self._covariance_block(lambda h, *a: lib().arslam_lm_covariance_block_anchored(h, pa, *a), block)
+
+    def covariance_block_pair_anchored(self, anchor, a, b):
+        """``covariance_block_pair_lens`` in the gauge of ``anchor`` (arslam_lm_covariance_block_pair_anchored)."""
+        pa = None if anchor is None else _block(anchor, 6)
+        return self._covariance_block(lambda h, *x: lib().arslam_lm_covariance_block_pair_anchored(h, pa, *x), a, b)
 
     def reset(self):
         _check(lib().arslam_lm_reset(self._h))

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import Summary, Transform, _check, _f64, _Owner, _ptr, lib
+from ._abi import CovInfo, Summary, Transform, _check, _f64, _Owner, _ptr, lib
 
 
 class SlamSolver(_Owner):
@@ -92,6 +92,37 @@ class SlamSolver(_Owner):
         (Localizer.covariance); LMError -7 (STATE) for any other capture."""
         cov, st = np.zeros((6, 6)), C.c_int(-1)
         _check(lib().arslam_slam_localize_covariance(self._h, int(cap_idx), _ptr(cov), C.byref(st)))
+        return cov, st.value
+
+    def covariance(self, anchor):
+        """The mapper problem's covariance in the gauge of aruco ``anchor`` (an index; it must have
+        residual blocks in the problem), after solve() or solve_incremental()
+        (arslam_slam_covariance and its getters): {cap (n, 6, 6), cap_status, aruco (n, 6, 6),
+        aruco_status, cam (3, 3), cam_status, info}.  A capture or aruco that is not in the mapper
+        problem (localized by localize_many, or not yet added) and the anchor itself are
+        COV_UNAVAILABLE, -1 in their values."""
+        info = CovInfo()
+        _check(lib().arslam_slam_covariance(self._h, int(anchor), C.byref(info)))
+        nc, na = self.num_captures, self.num_arucos
+        cap, aruco, cam = np.zeros((nc, 6, 6)), np.zeros((na, 6, 6)), np.zeros((3, 3))
+        cs, ast, st = np.zeros(nc, np.int32), np.zeros(na, np.int32), C.c_int(-1)
+        for c in range(nc):
+            _check(lib().arslam_slam_capture_covariance(self._h, c, _ptr(cap[c]), C.byref(st)))
+            cs[c] = st.value
+        for a in range(na):
+            _check(lib().arslam_slam_aruco_covariance(self._h, a, _ptr(aruco[a]), C.byref(st)))
+            ast[a] = st.value
+        _check(lib().arslam_slam_camera_covariance(self._h, _ptr(cam), C.byref(st)))
+        return {"cap": cap, "cap_status": cs, "aruco": aruco, "aruco_status": ast, "cam": cam, "cam_status": st.value,
+                "info": info.to_dict()}
+
+    def covariance_pair(self, anchor, a, b):
+        """(cov (6, 6), status): block (a, b) of the same matrix, a and b (kind, index) with kind
+        BLOCK_CAMERA (index 0), BLOCK_CAPTURE or BLOCK_TAG (an aruco); rows of a by columns of b,
+        the camera three wide (arslam_slam_covariance_pair)."""
+        cov, st = np.zeros((6, 6)), C.c_int(-1)
+        _check(lib().arslam_slam_covariance_pair(self._h, int(anchor), int(a[0]), int(a[1]), int(b[0]), int(b[1]),
+                                                 _ptr(cov), C.byref(st)))
         return cov, st.value
 
     def evaluate(self):

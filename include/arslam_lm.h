@@ -443,7 +443,9 @@ int arslam_lm_set_iteration_callback(arslam_lm *h, arslam_iteration_callback fn,
  * switch), with several ranks (arslam_lm_debug_force_multirank
  * included) and when the loaded problem's elimination_used is
  * ARSLAM_ELIM_MIXED; ARSLAM_ELIM_CAPTURES, _TAGS, and _AUTO or _MIXED
- * resolving to one whole side are supported.  The call changes nothing a
+ * resolving to one whole side are supported (arslam_lm_covariance_anchored
+ * is the form that works under a mixed set, with or without a call-time
+ * anchor).  The call changes nothing a
  * later solve returns, repeated calls give the same bits, and nothing is
  * allocated or launched for it before the first call. */
 #define ARSLAM_COV_OK 0
@@ -547,7 +549,7 @@ int arslam_lm_covariance_block_lens(arslam_lm *h, const double *block, double *c
  * Preconditions and errors as arslam_lm_covariance: ARSLAM_E_STATE without a
  * completed solve, ARSLAM_E_UNSUPPORTED with several ranks, under
  * arslam_lm_set_estimate_distortion and under ARSLAM_ELIM_MIXED (so not for the SLAM mirror, which runs MIXED and holds no
- * block constant); an earlier arslam_lm_covariance call is neither needed nor
+ * block constant: arslam_lm_covariance_pairs_anchored is the form for it); an earlier arslam_lm_covariance call is neither needed nor
  * in the way.  ARSLAM_E_INVALID_ARG for a bad kind or index or n_pairs < 0;
  * n_pairs == 0 is OK.  Nothing is allocated or launched for this before its
  * first call. */
@@ -584,6 +586,57 @@ int arslam_lm_covariance_pairs_lens(arslam_lm *h, const arslam_lm_cov_pair *pair
  * camera pointer's rows or columns are the three of [f, l1, l2]. */
 int arslam_lm_covariance_block_pair_lens(arslam_lm *h, const double *block_a, const double *block_b,
                                          double *cov, int *status);
+
+/* ---- covariance in a chosen anchor's gauge, under any e-block set ----
+ * The _lens forms with one more pose block held fixed for the length of the
+ * call: the anchor, a capture or a tag named by {anchor_kind, anchor_index}
+ * (ARSLAM_BLOCK_CAPTURE or _TAG with the caller's index; ARSLAM_BLOCK_NONE:
+ * the constant blocks alone) or by its pointer (NULL: none).  In Ceres' terms:
+ * SetParameterBlockConstant(anchor), Covariance::Compute,
+ * SetParameterBlockVariable(anchor) -- without touching the problem, so the
+ * loaded problem, the handle's Jacobi scale and LM diagonal stay, and a later
+ * solve returns the bits it would have returned without the call.
+ *
+ * H = J~'J~ is arslam_lm_covariance_lens' (loss-corrected rows at the point
+ * the last solve returned, no LM diagonal, l1 and l2 live only when
+ * estimated) with the anchor's six rows and columns deleted; C = H^-1 is the
+ * covariance in that block's gauge, equal to what the same handle would return
+ * at the same point had the block been constant.  The anchor's own status is
+ * ARSLAM_COV_UNAVAILABLE with -1 in its values (so is a pair that names it),
+ * the structural gauge check counts it as constant, and min_pivot leaves its
+ * rows out.  An anchor that is already constant changes nothing.
+ *
+ * Unlike every form above these are not refused when elimination_used is
+ * ARSLAM_ELIM_MIXED (Ceres' exact e-block set, what ARSLAM_ELIM_AUTO and the
+ * SLAM mirror run), also after an append (ARSLAM_SETUP_APPEND): a mixed set's
+ * direct groups -- residuals of two reduced blocks -- enter the reduced system
+ * as their plain normal-equation blocks.  Several ranks stay
+ * ARSLAM_E_UNSUPPORTED.  With an estimated lens they work on one whole side
+ * (the load refuses a mixed set of both sides under the switch).
+ *
+ * Output shapes, the camera's 3x3 (three wide in a pair), nullability and the
+ * error rules are the _lens forms'.  ARSLAM_E_INVALID_ARG for anchor_kind
+ * ARSLAM_BLOCK_CAMERA (or any other value), an anchor_index out of range, or
+ * an anchor pointer that is no pose block of the problem.  Repeated calls with
+ * the same anchor give the same bits; (a, b) and (b, a) are transposes of the
+ * same bits.  Nothing is allocated or launched for these forms before their
+ * first call. */
+#define ARSLAM_BLOCK_NONE (-1)
+int arslam_lm_covariance_anchored(arslam_lm *h, int anchor_kind, int anchor_index, double *cov_cap,
+                                  double *cov_tag, double *cov_cam /* [9] */, int *cap_status, int *tag_status,
+                                  int *cam_status, arslam_lm_cov_info *info);
+int arslam_lm_covariance_pairs_anchored(arslam_lm *h, int anchor_kind, int anchor_index,
+                                        const arslam_lm_cov_pair *pairs, int n_pairs, double *cov, int *status,
+                                        arslam_lm_cov_info *info);
+/* arslam_lm_covariance_block_lens in the gauge of `anchor` (nullable).
+ * Computes on the first request after a solve and serves later requests from
+ * the kept result while the anchor is the same; another anchor recomputes. */
+int arslam_lm_covariance_block_anchored(arslam_lm *h, const double *anchor, const double *block, double *cov,
+                                        int *status);
+/* arslam_lm_covariance_block_pair_lens in the gauge of `anchor` (nullable).
+ * Computes on every call. */
+int arslam_lm_covariance_block_pair_anchored(arslam_lm *h, const double *anchor, const double *block_a,
+                                             const double *block_b, double *cov, int *status);
 
 /* ---- Evaluate (ceres::Problem::Evaluate, Ceres 2.0, default EvaluateOptions) ----
  * The cost, the residuals, each residual block's loss weight and the gradient

@@ -115,6 +115,41 @@ int arslam_slam_localize_many(arslam_slam *h, int first_loc_cap_idx);
  * a capture the last localize_many did not cover (a mapping capture, or no
  * localize_many yet). */
 int arslam_slam_localize_covariance(arslam_slam *h, int cap_idx, double cov[36], int *cov_status);
+/* The mapper problem's covariance in the gauge of one aruco.  The mirror, like
+ * the reference, holds no block constant and solves under Ceres' exact (mixed)
+ * e-block set, so the anchor is named at the call: what
+ * SetParameterBlockConstant(aruco) + ceres::Covariance::Compute over every
+ * block would give, without touching the problem
+ * (arslam_lm_covariance_block_anchored, arslam_lm.h: the matrix, the point, the
+ * statuses, unit-variance residuals).  Valid after arslam_slam_solve or
+ * arslam_slam_solve_incremental.
+ *
+ * arslam_slam_covariance computes and keeps the 6x6 block of every capture and
+ * aruco and the camera's 3x3 (var(f) at [0], l1 / l2 rows and columns 0); info
+ * (nullable) as in arslam_lm_covariance.  anchor_aruco must be an aruco with
+ * residual blocks in the mapper problem: anything else is ARSLAM_E_INVALID_ARG.
+ * ARSLAM_E_STATE before the first solve.  The three getters serve the kept
+ * result (cov and status nullable; index out of range: ARSLAM_E_INVALID_ARG).
+ * A capture or aruco that is not in the mapper problem -- not yet added, or
+ * localized by arslam_slam_localize_many, which adds no block -- is
+ * ARSLAM_COV_UNAVAILABLE with -1 in its values, as is the anchor itself.
+ * Whatever changes the problem or its values (add_detections, a solve,
+ * localize_many, load_yaml, set_loss, set_camera_model, the pose and camera
+ * setters) drops the kept result: the getters then return ARSLAM_E_STATE.
+ *
+ * arslam_slam_covariance_pair: block (a, b) in the same gauge, computed on
+ * every call (arslam_lm_covariance_block_pair_anchored).  kind is
+ * ARSLAM_BLOCK_CAMERA (index 0), ARSLAM_BLOCK_CAPTURE or ARSLAM_BLOCK_TAG (an
+ * aruco); cov is a 6x6 row-major as arslam_lm_covariance_pairs_anchored lays
+ * it out (the camera three wide, the rest 0).  A block that is not in the
+ * mapper problem, or the anchor: ARSLAM_COV_UNAVAILABLE and -1.  A bad kind,
+ * index or anchor: ARSLAM_E_INVALID_ARG. */
+int arslam_slam_covariance(arslam_slam *h, int anchor_aruco, arslam_lm_cov_info *info);
+int arslam_slam_aruco_covariance(const arslam_slam *h, int a, double cov[36], int *status);
+int arslam_slam_capture_covariance(const arslam_slam *h, int c, double cov[36], int *status);
+int arslam_slam_camera_covariance(const arslam_slam *h, double cov[9], int *status);
+int arslam_slam_covariance_pair(arslam_slam *h, int anchor_aruco, int kind_a, int idx_a, int kind_b, int idx_b,
+                                double cov[36], int *status);
 /* ceres::Problem::Evaluate on the mapper problem (arslam_lm_evaluate_blocks,
  * arslam_lm.h): *cost = 1/2 sum rho over the residual blocks in the problem,
  * and over arslam_slam_num_blocks entries (block index as in arslam_slam_block)
