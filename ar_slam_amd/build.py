@@ -16,7 +16,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.environ.get("ARSLAM_LIB") or os.path.join(HERE, "libarslam_lm.so")   # (override: variant builds)
 SOURCES = ["lm_linearize.hip", "lm_schur.hip", "lm_schur_cam.hip", "lm_step.hip", "lm_reduce.hip", "lm_exchange.hip", "llt_levels.hip", "llt_dag.hip",
-           "lm_load.hip", "lm_solve.hip", "lm_covariance.hip", "lm_evaluate.hip", "lm_capi.hip", "llt_plan.cpp", "host_ordering.cpp", "host_eblocks.cpp",
+           "lm_load.hip", "lm_solve.hip", "lm_covariance.hip", "lm_evaluate.hip", "lm_capi.hip", "lm_cov_capi.hip", "llt_plan.cpp", "host_ordering.cpp", "host_eblocks.cpp",
            "host_problem.cpp", "host_layout.cpp", "host_gather.cpp", "localize.hip",
            "localize_capi.hip", "selinv.hip", "cov_pairs.hip", "cov_lens.hip", "cov_direct.hip", "debug_rows.hip", "debug_tiles.hip", "debug_plans.cpp",
            "debug_fingerprint.hip"]

@@ -1,6 +1,7 @@
 // lm_capi.hip -- the C-ABI of include/arslam_lm.h over the LM handle
 // (lm_handle.h): argument checks, the pointer-keyed problem's staging, and
-// the translation of exceptions into error codes (api_guarded).
+// the translation of exceptions into error codes (api_guarded).  The
+// covariance entry points are lm_cov_capi.hip's.
 #include "lm_handle.h"
 
 arslam_lm::~arslam_lm() {
@@ -221,58 +222,21 @@ int arslam_lm_debug_camera_rows(arslam_lm *h, double radius, long n_cols, double
   });
 }
 
-int arslam_lm_debug_cov_camera_rows(arslam_lm *h, long n_cols, double *rows, int *row_slot) {
-  if (!h || !rows) return ARSLAM_E_INVALID_ARG;
-  return arslam::api_guarded([&] {
-    h->cov_check_state("cov_camera_rows", true);
-    fail_if(!h->has_f || h->P.cam_row < 0, ARSLAM_E_STATE, "cov_camera_rows: a problem loaded with a free camera");
-    fail_if(n_cols != h->nR + 1, ARSLAM_E_INVALID_ARG, "cov_camera_rows: n_cols must be the reduced row count + 1");
-    h->cov_valid = false;
-    h->cov_anch_valid = false;
-    // the covariance's linearization, elimination, border and gathers, the rows read before the factorization
-    arslam_lm::CovFactor cf;
-    h->cov_factor(cf, true, true);
-    fail_if(!cf.factored, ARSLAM_E_STATE, "cov_camera_rows: the problem has no gauge anchor");
-    DevBuf<double> d_out;
-    d_out.alloc(3 * n_cols);
-    arslam::debug_cam_rows(h->P, h->Sp, d_out.p, h->stream);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(rows, d_out.p, 3 * n_cols * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    if (row_slot)
-      for (int b = 0; b < 3; ++b) row_slot[b] = h->lay.row_slot[h->P.cam_row + b];
-  });
-}
-
 }  // extern "C"
 
 namespace {
 // the caller's slot (camera 3, captures 6 each, tags 6 each) of each slot of the
 // loaded device problem, -1 for a direct group's copy of its capture; returns
 // the caller's slot count
-long caller_slots(const arslam_lm *h, std::vector<long> &map, int *n_cap, int *n_tag) {
-  const int nc = h->nc, nt = h->nt;
+long caller_slots(const arslam_lm *h, const arslam_lm::BlockMap &bm, std::vector<long> &map) {
   map.assign(h->n, -1);
   for (int j = 0; j < 3; ++j) map[j] = j;
-  const auto put = [&](long dev_block, long caller_block) {
-    for (int j = 0; j < 6; ++j) map[3 + 6 * dev_block + j] = 3 + 6 * caller_block + j;
-  };
-  if (h->elim_used == ARSLAM_ELIM_MIXED) {
-    const arslam::MixedProblem &m = h->mx;
-    *n_cap = m.src_n_cap, *n_tag = m.src_n_tag;
-    for (int g = 0; g < nc; ++g)
-      if (m.kind[g] != arslam::kMixDirect)
-        put(g, m.kind[g] == arslam::kMixTag ? (long)m.src_n_cap + m.group_src[g] : m.group_src[g]);
-    for (int f = 0; f < nt; ++f) put((long)nc + f, m.f_is_cap[f] ? m.f_src[f] : (long)m.src_n_cap + m.f_src[f]);
-  } else if (h->elim_used == ARSLAM_ELIM_TAGS) {   // e-blocks: the tags, f-blocks: the captures
-    *n_cap = nt, *n_tag = nc;
-    for (int t = 0; t < nc; ++t) put(t, (long)nt + t);
-    for (int c = 0; c < nt; ++c) put((long)nc + c, c);
-  } else {
-    *n_cap = nc, *n_tag = nt;
-    for (long b = 0; b < (long)nc + nt; ++b) put(b, b);
+  for (long b = 0; b < (long)bm.n_cap + bm.n_tag; ++b) {   // the caller's blocks: captures, then tags
+    const bool cap = b < bm.n_cap;
+    const long dev = bm.device_block(cap, (int)(cap ? b : b - bm.n_cap), h->nc);
+    for (int j = 0; j < 6 && dev >= 0; ++j) map[3 + 6 * dev + j] = 3 + 6 * b + j;
   }
-  return 3 + 6L * (*n_cap + *n_tag);
+  return 3 + 6L * (bm.n_cap + bm.n_tag);
 }
 }  // namespace
 
@@ -286,8 +250,11 @@ int arslam_lm_debug_step_stages(arslam_lm *h, double radius, arslam_lm_step_info
     h->ensure_stream();
     h->cov_invalidate();
     std::memset(info, 0, sizeof(*info));
+    const arslam_lm::BlockMap bm = h->block_map();
     std::vector<long> map;
-    info->n = caller_slots(h, map, &info->n_cap, &info->n_tag);
+    info->n = caller_slots(h, bm, map);
+    info->n_cap = bm.n_cap;
+    info->n_tag = bm.n_tag;
     info->n_reduced = h->has_f ? h->nR : 0;
     info->n_padded = h->has_f ? h->P.N : 0;
     info->cam_row = h->has_f ? h->P.cam_row : -1;
@@ -582,300 +549,21 @@ int arslam_lm_solve_soa(arslam_soa_problem *p, const arslam_lm_options *opt,
   return rc;
 }
 
-int arslam_lm_covariance(arslam_lm *h, double *cov_cap, double *cov_tag, double *var_f, int *cap_status,
-                         int *tag_status, arslam_lm_cov_info *info) {
-  if (!h) return ARSLAM_E_INVALID_ARG;
-  return arslam::api_guarded([&] {
-    h->covariance();
-    if (cov_cap && !h->cov_cap.empty()) std::memcpy(cov_cap, h->cov_cap.data(), h->cov_cap.size() * sizeof(double));
-    if (cov_tag && !h->cov_tag.empty()) std::memcpy(cov_tag, h->cov_tag.data(), h->cov_tag.size() * sizeof(double));
-    if (var_f) *var_f = h->cov_var_f;
-    if (cap_status && !h->cov_cap_status.empty())
-      std::memcpy(cap_status, h->cov_cap_status.data(), h->cov_cap_status.size() * sizeof(int));
-    if (tag_status && !h->cov_tag_status.empty())
-      std::memcpy(tag_status, h->cov_tag_status.data(), h->cov_tag_status.size() * sizeof(int));
-    if (info) *info = h->cov_info;
-  });
-}
-
-int arslam_lm_covariance_block(arslam_lm *h, const double *block, double *cov, int *status) {
-  if (!h || !block || !cov) return ARSLAM_E_INVALID_ARG;
-  return arslam::api_guarded([&] {
-    double *key = const_cast<double *>(block);
-    const auto ci = h->cap_of.find(key);
-    const auto ti = h->tag_of.find(key);
-    fail_if(key != h->camera_ptr && ci == h->cap_of.end() && ti == h->tag_of.end(), ARSLAM_E_INVALID_ARG,
-            "parameter block is not part of the problem");
-    fail_if(!h->pk_loaded || h->pk_dirty, ARSLAM_E_STATE,
-            "covariance_block: no completed arslam_lm_solve of the problem as it stands");
-    if (!h->cov_valid || h->cov_from_lens) h->covariance();   // (a kept _lens result is not this form's)
-    if (key == h->camera_ptr) {
-      std::fill(cov, cov + 9, 0.0);
-      cov[0] = h->cov_var_f;
-      const bool ok = h->cov_var_f >= 0.0;
-      if (!ok) std::fill(cov, cov + 9, -1.0);
-      if (status)
-        *status = ok ? ARSLAM_COV_OK
-                     : h->cov_info.status == ARSLAM_COV_RANK_DEFICIENT && !h->constant.count(key) ? ARSLAM_COV_RANK_DEFICIENT
-                                                                                                   : ARSLAM_COV_UNAVAILABLE;
-      return;
-    }
-    const bool is_cap = ci != h->cap_of.end();
-    const int i = is_cap ? ci->second : ti->second;
-    const std::vector<double> &c = is_cap ? h->cov_cap : h->cov_tag;
-    const std::vector<int> &st = is_cap ? h->cov_cap_status : h->cov_tag_status;
-    fail_if((size_t)i >= st.size(), ARSLAM_E_STATE, "covariance_block: the block is not part of the solved problem");
-    std::memcpy(cov, c.data() + 36L * i, 36 * sizeof(double));
-    if (status) *status = st[i];
-  });
-}
-
-int arslam_lm_covariance_pairs(arslam_lm *h, const arslam_lm_cov_pair *pairs, int n_pairs, double *cov, int *status,
-                               arslam_lm_cov_info *info) {
-  if (!h || n_pairs < 0 || (n_pairs > 0 && (!pairs || !cov))) return ARSLAM_E_INVALID_ARG;
-  return arslam::api_guarded([&] { h->covariance_pairs(pairs, n_pairs, cov, status, info); });
-}
-
-int arslam_lm_covariance_block_pair(arslam_lm *h, const double *block_a, const double *block_b, double *cov,
-                                    int *status) {
-  if (!h || !block_a || !block_b || !cov) return ARSLAM_E_INVALID_ARG;
-  return arslam::api_guarded([&] {
-    arslam_lm_cov_pair pr{};
-    int size[2] = {6, 6};
-    const double *blocks[2] = {block_a, block_b};
-    for (int s = 0; s < 2; ++s) {
-      double *key = const_cast<double *>(blocks[s]);
-      const auto ci = h->cap_of.find(key);
-      const auto ti = h->tag_of.find(key);
-      fail_if(key != h->camera_ptr && ci == h->cap_of.end() && ti == h->tag_of.end(), ARSLAM_E_INVALID_ARG,
-              "parameter block is not part of the problem");
-      const int kind = key == h->camera_ptr ? ARSLAM_BLOCK_CAMERA : ci != h->cap_of.end() ? ARSLAM_BLOCK_CAPTURE : ARSLAM_BLOCK_TAG;
-      const int index = kind == ARSLAM_BLOCK_CAMERA ? 0 : kind == ARSLAM_BLOCK_CAPTURE ? ci->second : ti->second;
-      if (kind == ARSLAM_BLOCK_CAMERA) size[s] = 3;
-      (s == 0 ? pr.kind_a : pr.kind_b) = kind;
-      (s == 0 ? pr.index_a : pr.index_b) = index;
-    }
-    fail_if(!h->pk_loaded || h->pk_dirty, ARSLAM_E_STATE,
-            "covariance_block_pair: no completed arslam_lm_solve of the problem as it stands");
-    double c[36];
-    int st = ARSLAM_COV_UNAVAILABLE;
-    h->covariance_pairs(&pr, 1, c, &st, nullptr);
-    // Ceres' shapes: rows of a by columns of b, the camera block 3 wide (l1 / l2 rows and columns 0)
-    const int ra = size[0], cb = size[1];
-    if (st != ARSLAM_COV_OK) {
-      std::fill(cov, cov + ra * cb, -1.0);
-    } else {
-      std::fill(cov, cov + ra * cb, 0.0);
-      if (ra == 6 && cb == 6) std::copy(c, c + 36, cov);
-      else if (ra == 3 && cb == 6) std::copy(c, c + 6, cov);                    // row 0: cov(f, b)
-      else if (ra == 6 && cb == 3) for (int r = 0; r < 6; ++r) cov[3 * r] = c[r];   // column 0: cov(a, f)
-      else cov[0] = c[0];
-    }
-    if (status) *status = st;
-  });
-}
-
-int arslam_lm_covariance_lens(arslam_lm *h, double *cov_cap, double *cov_tag, double *cov_cam, int *cap_status,
-                              int *tag_status, int *cam_status, arslam_lm_cov_info *info) {
-  if (!h) return ARSLAM_E_INVALID_ARG;
-  return arslam::api_guarded([&] {
-    h->covariance(true);
-    if (cov_cap && !h->cov_cap.empty()) std::memcpy(cov_cap, h->cov_cap.data(), h->cov_cap.size() * sizeof(double));
-    if (cov_tag && !h->cov_tag.empty()) std::memcpy(cov_tag, h->cov_tag.data(), h->cov_tag.size() * sizeof(double));
-    if (cov_cam) std::memcpy(cov_cam, h->cov_cam, 9 * sizeof(double));
-    if (cap_status && !h->cov_cap_status.empty())
-      std::memcpy(cap_status, h->cov_cap_status.data(), h->cov_cap_status.size() * sizeof(int));
-    if (tag_status && !h->cov_tag_status.empty())
-      std::memcpy(tag_status, h->cov_tag_status.data(), h->cov_tag_status.size() * sizeof(int));
-    if (cam_status) *cam_status = h->cov_cam_status;
-    if (info) *info = h->cov_info;
-  });
-}
-
-int arslam_lm_covariance_block_lens(arslam_lm *h, const double *block, double *cov, int *status) {
-  if (!h || !block || !cov) return ARSLAM_E_INVALID_ARG;
-  return arslam::api_guarded([&] {
-    double *key = const_cast<double *>(block);
-    const auto ci = h->cap_of.find(key);
-    const auto ti = h->tag_of.find(key);
-    fail_if(key != h->camera_ptr && ci == h->cap_of.end() && ti == h->tag_of.end(), ARSLAM_E_INVALID_ARG,
-            "parameter block is not part of the problem");
-    fail_if(!h->pk_loaded || h->pk_dirty, ARSLAM_E_STATE,
-            "covariance_block_lens: no completed arslam_lm_solve of the problem as it stands");
-    if (!h->cov_valid || !h->cov_from_lens) h->covariance(true);
-    if (key == h->camera_ptr) {
-      std::memcpy(cov, h->cov_cam, 9 * sizeof(double));
-      if (status) *status = h->cov_cam_status;
-      return;
-    }
-    const bool is_cap = ci != h->cap_of.end();
-    const int i = is_cap ? ci->second : ti->second;
-    const std::vector<double> &c = is_cap ? h->cov_cap : h->cov_tag;
-    const std::vector<int> &st = is_cap ? h->cov_cap_status : h->cov_tag_status;
-    fail_if((size_t)i >= st.size(), ARSLAM_E_STATE, "covariance_block_lens: the block is not part of the solved problem");
-    std::memcpy(cov, c.data() + 36L * i, 36 * sizeof(double));
-    if (status) *status = st[i];
-  });
-}
-
-int arslam_lm_covariance_pairs_lens(arslam_lm *h, const arslam_lm_cov_pair *pairs, int n_pairs, double *cov,
-                                    int *status, arslam_lm_cov_info *info) {
-  if (!h || n_pairs < 0 || (n_pairs > 0 && (!pairs || !cov))) return ARSLAM_E_INVALID_ARG;
-  return arslam::api_guarded([&] { h->covariance_pairs(pairs, n_pairs, cov, status, info, true); });
-}
-
-int arslam_lm_covariance_block_pair_lens(arslam_lm *h, const double *block_a, const double *block_b, double *cov,
-                                         int *status) {
-  if (!h || !block_a || !block_b || !cov) return ARSLAM_E_INVALID_ARG;
-  return arslam::api_guarded([&] {
-    arslam_lm_cov_pair pr{};
-    int size[2] = {6, 6};
-    const double *blocks[2] = {block_a, block_b};
-    for (int s = 0; s < 2; ++s) {
-      double *key = const_cast<double *>(blocks[s]);
-      const auto ci = h->cap_of.find(key);
-      const auto ti = h->tag_of.find(key);
-      fail_if(key != h->camera_ptr && ci == h->cap_of.end() && ti == h->tag_of.end(), ARSLAM_E_INVALID_ARG,
-              "parameter block is not part of the problem");
-      const int kind = key == h->camera_ptr ? ARSLAM_BLOCK_CAMERA : ci != h->cap_of.end() ? ARSLAM_BLOCK_CAPTURE : ARSLAM_BLOCK_TAG;
-      const int index = kind == ARSLAM_BLOCK_CAMERA ? 0 : kind == ARSLAM_BLOCK_CAPTURE ? ci->second : ti->second;
-      if (kind == ARSLAM_BLOCK_CAMERA) size[s] = 3;
-      (s == 0 ? pr.kind_a : pr.kind_b) = kind;
-      (s == 0 ? pr.index_a : pr.index_b) = index;
-    }
-    fail_if(!h->pk_loaded || h->pk_dirty, ARSLAM_E_STATE,
-            "covariance_block_pair_lens: no completed arslam_lm_solve of the problem as it stands");
-    double c[36];
-    int st = ARSLAM_COV_UNAVAILABLE;
-    h->covariance_pairs(&pr, 1, c, &st, nullptr, true);
-    // Ceres' shapes: rows of a by columns of b, the camera block 3 wide -- the top-left of the 6x6
-    const int ra = size[0], cb = size[1];
-    for (int r = 0; r < ra; ++r)
-      for (int q = 0; q < cb; ++q) cov[cb * r + q] = st == ARSLAM_COV_OK ? c[6 * r + q] : -1.0;
-    if (status) *status = st;
-  });
-}
-
-}  // extern "C"
-
-namespace {
-// the caller's {kind, index} of a pointer-keyed block (the camera: index 0); throws for a pointer that is no block
-void pk_block(const arslam_lm *h, const double *block, int *kind, int *index) {
-  double *key = const_cast<double *>(block);
-  const auto ci = h->cap_of.find(key);
-  const auto ti = h->tag_of.find(key);
-  fail_if(key != h->camera_ptr && ci == h->cap_of.end() && ti == h->tag_of.end(), ARSLAM_E_INVALID_ARG,
-          "parameter block is not part of the problem");
-  *kind = key == h->camera_ptr ? ARSLAM_BLOCK_CAMERA : ci != h->cap_of.end() ? ARSLAM_BLOCK_CAPTURE : ARSLAM_BLOCK_TAG;
-  *index = *kind == ARSLAM_BLOCK_CAMERA ? 0 : *kind == ARSLAM_BLOCK_CAPTURE ? ci->second : ti->second;
-}
-// the anchor of a pointer-keyed anchored form: null is none, the camera is refused
-arslam_lm::CovAnchor pk_anchor(const arslam_lm *h, const double *anchor) {
-  arslam_lm::CovAnchor an;
-  if (!anchor) return an;
-  pk_block(h, anchor, &an.kind, &an.index);
-  fail_if(an.kind == ARSLAM_BLOCK_CAMERA, ARSLAM_E_INVALID_ARG, "the anchor must be a pose block, not the camera");
-  return an;
-}
-}  // namespace
-
-extern "C" {
-
-int arslam_lm_covariance_anchored(arslam_lm *h, int anchor_kind, int anchor_index, double *cov_cap, double *cov_tag,
-                                  double *cov_cam, int *cap_status, int *tag_status, int *cam_status,
-                                  arslam_lm_cov_info *info) {
-  if (!h) return ARSLAM_E_INVALID_ARG;
-  return arslam::api_guarded([&] {
-    const arslam_lm::CovAnchor an{anchor_kind, anchor_index};
-    h->covariance(true, &an);
-    if (cov_cap && !h->cov_cap.empty()) std::memcpy(cov_cap, h->cov_cap.data(), h->cov_cap.size() * sizeof(double));
-    if (cov_tag && !h->cov_tag.empty()) std::memcpy(cov_tag, h->cov_tag.data(), h->cov_tag.size() * sizeof(double));
-    if (cov_cam) std::memcpy(cov_cam, h->cov_cam, 9 * sizeof(double));
-    if (cap_status && !h->cov_cap_status.empty())
-      std::memcpy(cap_status, h->cov_cap_status.data(), h->cov_cap_status.size() * sizeof(int));
-    if (tag_status && !h->cov_tag_status.empty())
-      std::memcpy(tag_status, h->cov_tag_status.data(), h->cov_tag_status.size() * sizeof(int));
-    if (cam_status) *cam_status = h->cov_cam_status;
-    if (info) *info = h->cov_info;
-  });
-}
-
-int arslam_lm_covariance_pairs_anchored(arslam_lm *h, int anchor_kind, int anchor_index,
-                                        const arslam_lm_cov_pair *pairs, int n_pairs, double *cov, int *status,
-                                        arslam_lm_cov_info *info) {
-  if (!h || n_pairs < 0 || (n_pairs > 0 && (!pairs || !cov))) return ARSLAM_E_INVALID_ARG;
-  return arslam::api_guarded([&] {
-    const arslam_lm::CovAnchor an{anchor_kind, anchor_index};
-    h->covariance_pairs(pairs, n_pairs, cov, status, info, true, &an);
-  });
-}
-
-int arslam_lm_covariance_block_anchored(arslam_lm *h, const double *anchor, const double *block, double *cov,
-                                        int *status) {
-  if (!h || !block || !cov) return ARSLAM_E_INVALID_ARG;
-  return arslam::api_guarded([&] {
-    int kind = 0, i = 0;
-    pk_block(h, block, &kind, &i);
-    const arslam_lm::CovAnchor an = pk_anchor(h, anchor);
-    fail_if(!h->pk_loaded || h->pk_dirty, ARSLAM_E_STATE,
-            "covariance_block_anchored: no completed arslam_lm_solve of the problem as it stands");
-    if (!h->cov_anch_valid || !(h->cov_anch == an)) h->covariance(true, &an);
-    if (kind == ARSLAM_BLOCK_CAMERA) {
-      std::memcpy(cov, h->cov_cam, 9 * sizeof(double));
-      if (status) *status = h->cov_cam_status;
-      return;
-    }
-    const bool is_cap = kind == ARSLAM_BLOCK_CAPTURE;
-    const std::vector<double> &c = is_cap ? h->cov_cap : h->cov_tag;
-    const std::vector<int> &st = is_cap ? h->cov_cap_status : h->cov_tag_status;
-    fail_if((size_t)i >= st.size(), ARSLAM_E_STATE, "covariance_block_anchored: the block is not part of the solved problem");
-    std::memcpy(cov, c.data() + 36L * i, 36 * sizeof(double));
-    if (status) *status = st[i];
-  });
-}
-
-int arslam_lm_covariance_block_pair_anchored(arslam_lm *h, const double *anchor, const double *block_a,
-                                             const double *block_b, double *cov, int *status) {
-  if (!h || !block_a || !block_b || !cov) return ARSLAM_E_INVALID_ARG;
-  return arslam::api_guarded([&] {
-    arslam_lm_cov_pair pr{};
-    pk_block(h, block_a, &pr.kind_a, &pr.index_a);
-    pk_block(h, block_b, &pr.kind_b, &pr.index_b);
-    const arslam_lm::CovAnchor an = pk_anchor(h, anchor);
-    fail_if(!h->pk_loaded || h->pk_dirty, ARSLAM_E_STATE,
-            "covariance_block_pair_anchored: no completed arslam_lm_solve of the problem as it stands");
-    double c[36];
-    int st = ARSLAM_COV_UNAVAILABLE;
-    h->covariance_pairs(&pr, 1, c, &st, nullptr, true, &an);
-    // Ceres' shapes: rows of a by columns of b, the camera block 3 wide -- the top-left of the 6x6
-    const int ra = pr.kind_a == ARSLAM_BLOCK_CAMERA ? 3 : 6, cb = pr.kind_b == ARSLAM_BLOCK_CAMERA ? 3 : 6;
-    for (int r = 0; r < ra; ++r)
-      for (int q = 0; q < cb; ++q) cov[cb * r + q] = st == ARSLAM_COV_OK ? c[6 * r + q] : -1.0;
-    if (status) *status = st;
-  });
-}
-
 int arslam_lm_debug_reduced_rows(arslam_lm *h, int *cap_row, int *tag_row, int *cam_row) {
   if (!h) return ARSLAM_E_INVALID_ARG;
   return arslam::api_guarded([&] {
     fail_if(!h->loaded || h->multi(), ARSLAM_E_STATE, "reduced_rows: a problem loaded on one rank");
     if (cam_row) *cam_row = h->has_f ? h->P.cam_row : -1;
-    if (h->elim_used == ARSLAM_ELIM_MIXED) {   // the f-blocks are tags and captures; the groups have no rows
-      const arslam::MixedProblem &m = h->mx;
-      for (int c = 0; c < m.src_n_cap && cap_row; ++c) cap_row[c] = -1;
-      for (int t = 0; t < m.src_n_tag && tag_row; ++t) tag_row[t] = -1;
-      for (int f = 0; f < h->nt; ++f) {
-        int *row = m.f_is_cap[f] ? cap_row : tag_row;
-        if (row) row[m.f_src[f]] = (size_t)f < h->lay.tag_row.size() ? h->lay.tag_row[f] : -1;
+    // a caller's block has a row when it is an f-block (no reduced system: the layout has no rows)
+    const arslam_lm::BlockMap bm = h->block_map();
+    const auto rows = [&](bool cap, int n, int *row) {
+      for (int i = 0; i < n && row; ++i) {
+        const int f = bm.role(cap, i) == arslam::kCovF ? bm.idx(cap, i) : -1;
+        row[i] = f >= 0 && (size_t)f < h->lay.tag_row.size() ? h->lay.tag_row[f] : -1;
       }
-      return;
-    }
-    const bool swapped = h->elim_used == ARSLAM_ELIM_TAGS;
-    // (the device problem's e-blocks nc, f-blocks nt; no reduced system: the layout has no rows)
-    int *e_row = swapped ? tag_row : cap_row, *f_row = swapped ? cap_row : tag_row;
-    for (int c = 0; c < h->nc && e_row; ++c) e_row[c] = -1;
-    for (int t = 0; t < h->nt && f_row; ++t) f_row[t] = (size_t)t < h->lay.tag_row.size() ? h->lay.tag_row[t] : -1;
-    if (cam_row) *cam_row = h->has_f ? h->P.cam_row : -1;
+    };
+    rows(true, bm.n_cap, cap_row);
+    rows(false, bm.n_tag, tag_row);
   });
 }
 
@@ -1026,14 +714,3 @@ const char *arslam_lm_last_error(void) { return g_last_error.c_str(); }
 const char *arslam_lm_version(void) { return "arslam_lm 0.2 (gfx950, fp64) build " ARSLAM_BUILD_ID; }
 
 }  // extern "C"
-
-namespace arslam {
-// For the host mirror (ar_slam_solver.cpp), not part of the C-ABI: the info of
-// the result an _anchored pointer-keyed call keeps on the handle; false when
-// none is kept.
-bool kept_anchored_cov_info(const arslam_lm *h, arslam_lm_cov_info *info) {
-  if (!h || !h->cov_anch_valid) return false;
-  if (info) *info = h->cov_info;
-  return true;
-}
-}  // namespace arslam

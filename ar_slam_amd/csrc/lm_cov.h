@@ -3,8 +3,9 @@
 // the multi-right-hand-side tile solve and the cross-covariance blocks
 // (cov_pairs.hip), and the border and block kernels of a problem whose l1, l2
 // are estimated (cov_lens.hip), and the local systems of a mixed e-block
-// set's direct groups (cov_direct.hip).  Called by lm_covariance.hip, and by
-// debug_tiles.hip for the component tests.
+// set's direct groups (cov_direct.hip).  Called by lm_covariance.hip (the
+// entry points, lm_cov_capi.hip, launch nothing), and by debug_tiles.hip for
+// the component tests.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>

@@ -362,18 +362,15 @@ int arslam_lm_debug_evaluate_times(arslam_lm *h, double ms[5]) {
 int arslam_lm_gradient_block(arslam_lm *h, const double *block, double *out) {
   if (!h || !block || !out) return ARSLAM_E_INVALID_ARG;
   return arslam::api_guarded([&] {
-    double *key = const_cast<double *>(block);
-    const auto ci = h->cap_of.find(key);
-    const auto ti = h->tag_of.find(key);
-    fail_if(key != h->camera_ptr && ci == h->cap_of.end() && ti == h->tag_of.end(), ARSLAM_E_INVALID_ARG,
-            "parameter block is not part of the problem");
+    int kind = 0, i = 0;
+    h->pk_block(block, &kind, &i);
     fail_if(!h->ev_grad_valid, ARSLAM_E_STATE,
             "gradient_block: no arslam_lm_evaluate_blocks of the problem as it stands");
-    if (key == h->camera_ptr) {
+    if (kind == ARSLAM_BLOCK_CAMERA) {
       std::memcpy(out, h->ev_grad.data(), 3 * sizeof(double));
       return;
     }
-    const long at = ci != h->cap_of.end() ? 3 + 6L * ci->second : 3 + 6L * h->ev_nc + 6L * ti->second;
+    const long at = kind == ARSLAM_BLOCK_CAPTURE ? 3 + 6L * i : 3 + 6L * h->ev_nc + 6L * i;
     fail_if((size_t)at + 6 > h->ev_grad.size(), ARSLAM_E_STATE, "gradient_block: the block is not part of the evaluated problem");
     std::memcpy(out, h->ev_grad.data() + at, 6 * sizeof(double));
   });

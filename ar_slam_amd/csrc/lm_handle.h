@@ -3,8 +3,9 @@
 // `struct arslam_lm` with every member.  The methods'
 // bodies live in lm_load.hip (load, upload, append, value reload), lm_solve.hip
 // (the trust-region loop, its stages, the linearization), lm_covariance.hip,
-// lm_evaluate.hip (arslam_lm_evaluate*, with its own entry points) and
-// lm_capi.hip (the extern "C" entry points); only those include this header.
+// lm_evaluate.hip (arslam_lm_evaluate*, with its own entry points),
+// lm_cov_capi.hip (the covariance entry points) and lm_capi.hip (the other
+// extern "C" entry points); only those include this header.
 #pragma once
 #include "hip_host.h"
 #include "host_threads.h"
@@ -251,6 +252,16 @@ struct arslam_lm {
     return soa_size.data();
   }
   std::unordered_set<double *> constant;
+  // the caller's {kind, index} of a pointer-keyed block (the camera: index 0); throws for a pointer that is no block
+  void pk_block(const double *block, int *kind, int *index) const {
+    double *key = const_cast<double *>(block);
+    const auto ci = cap_of.find(key);
+    const auto ti = tag_of.find(key);
+    fail_if(key != camera_ptr && ci == cap_of.end() && ti == tag_of.end(), ARSLAM_E_INVALID_ARG,
+            "parameter block is not part of the problem");
+    *kind = key == camera_ptr ? ARSLAM_BLOCK_CAMERA : ci != cap_of.end() ? ARSLAM_BLOCK_CAPTURE : ARSLAM_BLOCK_TAG;
+    *index = *kind == ARSLAM_BLOCK_CAMERA ? 0 : *kind == ARSLAM_BLOCK_CAPTURE ? ci->second : ti->second;
+  }
   // The pointer-keyed structure (blocks, residuals, constants) changed since
   // the last load: arslam_lm_solve reloads; otherwise it reuses the resident
   // problem, plan and buffers and uploads only the parameter values.
@@ -534,71 +545,84 @@ struct arslam_lm {
   DevBuf<double> d_cov_Gl;
   DevBuf<int> d_cov_status;
   hipEvent_t cov_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  // the kept result, in the caller's block order (arslam_lm_covariance_block serves it)
-  bool cov_valid = false;
-  std::vector<double> cov_cap, cov_tag;
-  std::vector<int> cov_cap_status, cov_tag_status;
-  double cov_var_f = -1.0;
-  // the camera's 3x3 over [f, l1, l2] and its status; cov_from_lens: the kept
-  // result is arslam_lm_covariance_lens' (the pointer-keyed forms serve only
-  // their own kind's)
-  double cov_cam[9] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};
-  int cov_cam_status = ARSLAM_COV_UNAVAILABLE;
-  bool cov_from_lens = false;
-  arslam_lm_cov_info cov_info{};
   // The anchored forms (arslam_lm_covariance_anchored): the pose block held
   // fixed for one call besides the constant ones (kind ARSLAM_BLOCK_CAPTURE,
-  // _TAG or _NONE, the caller's index).  Their kept result lives in the same
-  // arrays under a flag of its own (cov_anch_valid, with the anchor it was
-  // computed for): the other pointer-keyed forms never serve it, nor it theirs.
+  // _TAG or _NONE, the caller's index).
   struct CovAnchor {
     int kind = ARSLAM_BLOCK_NONE, index = 0;
     bool none() const { return kind == ARSLAM_BLOCK_NONE; }
     bool operator==(const CovAnchor &o) const { return kind == o.kind && (none() || index == o.index); }
   };
-  bool cov_anch_valid = false;
-  CovAnchor cov_anch{};
+  // The form of a covariance call and of the kept result: plain, _lens (the
+  // camera's block is [f, l1, l2]) or _anchored (a _lens form with an anchor,
+  // possibly NONE; it takes the mixed e-block set too).  Equal forms serve each
+  // other's kept result: plain only plain, lens only lens, anchored the same anchor.
+  struct CovForm {
+    bool lens = false, anchored = false;
+    CovAnchor anchor{};
+    static CovForm with_lens() { return CovForm{true, false, CovAnchor{}}; }
+    static CovForm anchored_at(const CovAnchor &an) { return CovForm{true, true, an}; }
+    bool operator==(const CovForm &o) const {
+      return lens == o.lens && anchored == o.anchored && (!anchored || anchor == o.anchor);
+    }
+    // the entry point of this form in messages: "covariance" -> "covariance_lens", ...
+    std::string name(const char *stem) const { return std::string(stem) + (anchored ? "_anchored" : lens ? "_lens" : ""); }
+  };
+  // the kept result of covariance(), in the caller's block order, and the form
+  // it was computed for (the pointer-keyed block forms serve it to that form alone)
+  bool cov_kept = false;
+  CovForm cov_form{};
+  std::vector<double> cov_cap, cov_tag;
+  std::vector<int> cov_cap_status, cov_tag_status;
+  double cov_var_f = -1.0;
+  double cov_cam[9] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};   // the camera's 3x3 over [f, l1, l2] and its status
+  int cov_cam_status = ARSLAM_COV_UNAVAILABLE;
+  arslam_lm_cov_info cov_info{};
   // allocated at the first anchored call: the call's copy of the Jacobi scale
   // (0 on the anchor's slots and on the direct groups' copies) and, under a
   // mixed e-block set, its direct groups
   DevBuf<double> d_cov_scale;
   DevBuf<int> d_cov_direct;
-  void covariance(bool lens = false, const CovAnchor *an = nullptr);
+  void covariance(const CovForm &form);
   void cov_invalidate() {
     solve_state = 0;
-    cov_valid = false;
-    cov_anch_valid = false;
+    cov_kept = false;
   }
-  // The caller's blocks in the device problem: per capture and tag the role
-  // (arslam::kCovE: a group's eliminated block, kCovF: an f-block) and the
-  // index there, from elim_used (whole sides) or mx (a mixed set: kind,
-  // group_src, f_src, f_is_cap); a reduced capture is kCovF.  e_node / f_node:
-  // the caller's block (capture c: c, tag t: n_cap + t) of each group and
+  // The one map between the caller's blocks and the device problem's: per
+  // capture and tag the role (arslam::kCovE: a group's eliminated block, kCovF:
+  // an f-block) and the index there, from elim_used (whole sides) or mx (a mixed
+  // set: kind, group_src, f_src, f_is_cap); a reduced capture is kCovF.  e_node /
+  // f_node: the caller's block (capture c: c, tag t: n_cap + t) of each group and
   // f-block -- a direct group's is its capture's, the block its f-block is.
-  struct CovRoles {
+  // Derived per call (block_map), never kept: load and try_append change it.
+  struct BlockMap {
     int n_cap = 0, n_tag = 0;
     std::vector<int> cap_role, cap_idx, tag_role, tag_idx;
     std::vector<int> e_node, f_node;
     int role(bool cap, int i) const { return cap ? cap_role[i] : tag_role[i]; }
     int idx(bool cap, int i) const { return cap ? cap_idx[i] : tag_idx[i]; }
+    // the device problem's block (e-blocks, then f-blocks) of a caller's block; -1: none
+    long device_block(bool cap, int i, int nc) const {
+      return idx(cap, i) < 0 ? -1 : role(cap, i) == arslam::kCovE ? idx(cap, i) : (long)nc + idx(cap, i);
+    }
   };
-  CovRoles cov_roles() const;
-  // the anchor as the calls accept it (throws ARSLAM_E_INVALID_ARG otherwise)
-  void cov_check_anchor(const char *who, const CovAnchor &an, const CovRoles &ro) const;
+  BlockMap block_map() const;
+  // the form's anchor as the calls accept it (throws ARSLAM_E_INVALID_ARG otherwise)
+  void cov_check_anchor(const std::string &who, const CovForm &form, const BlockMap &bm) const;
   // What covariance() and covariance_pairs() share (lm_covariance.hip):
-  // cov_check_state: the calls' preconditions.  cov_factor: the structural
-  // gauge check, then -- unless it fails -- the linearization at xbest,
-  // k_cov_schur, the gather with the covariance's diagonal and the
-  // factorization, all enqueued (cov_ev[0..2] around them); S then holds the
-  // factor itself.  cov_numeric_test: after the caller's own launches, the
-  // one stream sync, the flag and the min_pivot test; fills the times.
+  // cov_check_state: the calls' preconditions.  cov_factor: the device
+  // problem's structure read back, the structural gauge check on the host, then
+  // -- unless it fails -- the linearization at xbest, k_cov_schur, the gather
+  // with the covariance's diagonal and the factorization, all enqueued
+  // (cov_ev[0..2] around them); S then holds the factor itself.
+  // cov_numeric_test: after the caller's own launches, the one stream sync, the
+  // flag and the min_pivot test; fills the times.
   struct CovFactor {
     std::vector<int> cap_start;   // the device problem's e-block CSR
     bool deficient = false;
     bool factored = false;        // the device work was enqueued
     bool live = false;            // a _lens call on a problem whose l1, l2 are estimated: they are rows of H
     arslam_lm_cov_info info{};
-    CovRoles roles;
     // the Jacobi scale every covariance kernel of the call reads: the handle's,
     // or an anchored call's copy (d_cov_scale)
     const double *scale = nullptr;
@@ -610,11 +634,13 @@ struct arslam_lm {
   };
   bool cov_e_free(int c) const { return slot_free[3 + 6L * c] != 0; }
   bool cov_f_free(int t) const { return slot_free[3 + 6L * nc + 6L * t] != 0; }
-  // (anchored: the anchored forms take the mixed e-block set too)
-  void cov_check_state(const char *who, bool lens = false, bool anchored = false) const;
-  // (an: an anchored form's call, its anchor possibly NONE -- the call's scale
-  // copy, the direct groups' kernel and the anchor held fixed)
-  void cov_factor(CovFactor &cf, bool lens = false, bool assemble_only = false, const CovAnchor *an = nullptr);
+  void cov_check_state(const std::string &who, const CovForm &form) const;
+  // cov_factor's stages: what it reads back of the device problem (and, for an
+  // anchored form, of the Jacobi scale), and the enqueue after the gauge check
+  struct CovStructure;
+  void cov_read_structure(CovFactor &cf, const CovForm &form, CovStructure &st);
+  void cov_enqueue(CovFactor &cf, const CovForm &form, CovStructure &st, bool assemble_only);
+  void cov_factor(CovFactor &cf, const CovForm &form, const BlockMap &bm, bool assemble_only = false);
   void cov_numeric_test(CovFactor &cf);
 
   // ---- cross-covariance blocks (arslam_lm_covariance_pairs) ----
@@ -629,8 +655,13 @@ struct arslam_lm {
   DevBuf<arslam::CovPairTask> d_pair_tasks;
   DevBuf<int> d_pair_status;
   std::vector<hipEvent_t> pair_ev;   // two per batch, around its solve
-  void covariance_pairs(const arslam_lm_cov_pair *pairs, int n_pairs, double *cov, int *status,
-                        arslam_lm_cov_info *info, bool lens = false, const CovAnchor *an = nullptr);
+  void covariance_pairs(const CovForm &form, const arslam_lm_cov_pair *pairs, int n_pairs, double *cov, int *status,
+                        arslam_lm_cov_info *info);
+  // its plan (the pairs resolved, the distinct tasks; host functions of
+  // lm_covariance.hip fill it) and the two stages that use the device
+  struct CovPairPlan;
+  void cov_pair_masks(const CovFactor &cf, CovPairPlan &pp);
+  void cov_pair_batches(CovFactor &cf, CovPairPlan &pp);
 
   // ---- Evaluate (arslam_lm_evaluate*, lm_evaluate.hip) ----
   // A path of its own: the problem's structure in the caller's order, its own

@@ -3,6 +3,7 @@
 #include "ar_slam_solver.hpp"
 
 #include "yaml_lite.hpp"
+#include "lm_cov_host.h"
 #include "loss.h"
 
 #include <algorithm>
@@ -412,8 +413,6 @@ int ArSlamSolver::evaluate(double *cost, double *sq_norm, double *weight) {
   }
   return ARSLAM_OK;
 }
-
-bool kept_anchored_cov_info(const arslam_lm *h, arslam_lm_cov_info *info);   // lm_capi.hip
 
 void ArSlamSolver::problemMembers(std::vector<char> &caps, std::vector<char> &arucos) const {
   caps.assign(captures_.size(), 0);
