@@ -238,6 +238,115 @@ long caller_slots(const arslam_lm *h, const arslam_lm::BlockMap &bm, std::vector
   }
   return 3 + 6L * (bm.n_cap + bm.n_tag);
 }
+
+// ... and of a sharded handle's: its captures are own_caps (the ranks eliminate
+// captures), every tag is loaded on every rank
+long caller_slots_sharded(const arslam_lm *h, std::vector<long> &map) {
+  const long t0 = 3 + 6L * h->nc, t0_full = 3 + 6L * h->nc_full;
+  map.assign(h->n, -1);
+  for (int j = 0; j < 3; ++j) map[j] = j;
+  for (long c = 0; c < h->nc; ++c)
+    for (int j = 0; j < 6; ++j) map[3 + 6 * c + j] = 3 + 6L * h->own_caps[c] + j;
+  for (long sl = t0; sl < h->n; ++sl) map[sl] = t0_full + (sl - t0);
+  return t0_full + 6L * h->nt;
+}
+
+// The body of arslam_lm_debug_step_stages and _sharded: the launches of
+// solve()'s iteration 0 and first step from the loaded point, the copy of S
+// before the factorization, and the outputs by the caller's slots (map; rows:
+// the layout's row_slot).  info's n, n_cap, n_tag, elimination_used and n_direct
+// are the caller's.  lin_ride (a sharded handle): iteration 0's sums are final
+// (the packed exchange) as in solve(); with it a linearization at the same point
+// is enqueued again as after an accepted step, and its top-tag sums and camera
+// partials ride in front of the top tiles, its cost and norms with the step's
+// scalars (enqueue_step's path when a step follows).
+void step_stages(arslam_lm *h, double radius, bool lin_ride, const std::vector<long> &map, const std::vector<int> &rows,
+                 arslam_lm_step_info *info, double *g, double *colnorm, double *scale, double *diag, double *S,
+                 int *row_slot, double *y, double *xc) {
+  const bool sharded = h->multi();
+  info->n_reduced = h->has_f ? h->nR : 0;
+  info->n_padded = h->has_f ? h->P.N : 0;
+  info->cam_row = h->has_f ? h->P.cam_row : -1;
+  info->n_groups = h->nc;
+  info->n_big_groups = h->P.n_big_caps;
+  info->n_chunk_groups = h->P.n_chunk_caps;
+  info->n_split_dest = h->has_f ? h->P.n_splits : 0;
+  info->max_contrib = h->has_f ? h->sg.max_contrib : 0;
+  info->n_tiles = h->has_f ? h->plan.n_tiles : 0;
+  info->n_assembled_tiles = h->has_f ? h->plan.n_assembled : 0;
+  // as solve()'s iteration 0 ...
+  h->norms_pending = h->lin_xpending = false;
+  h->x = h->d_xa.p;
+  h->xc = h->d_xb.p;
+  h->xbest = h->x;
+  HIP_CHECK(hipMemcpyAsync(h->x, h->u_x0, h->n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  for (auto &t : h->timers) t.on = false;
+  double gmax, gnorm, xnorm;
+  h->linearize(&info->cost, &info->fixed_cost, &gmax, &gnorm, &xnorm);
+  const arslam::LmDiagArgs ld{h->n, h->d_scale.p, h->d_colnorm.p, h->opt.min_lm_diagonal, h->opt.max_lm_diagonal,
+                              h->d_diag.p};
+  arslam::launch_scale(h->P, h->d_colnorm.p, h->opt.jacobi_scaling, h->d_scale.p, h->stream, &ld);
+  struct DiagInLin {   // (as solve()'s guard)
+    arslam_lm *h;
+    ~DiagInLin() { h->diag_in_lin = false; }
+  } diag_in_lin_guard{h};
+  if (sharded && lin_ride) {
+    h->diag_in_lin = true;
+    h->linearize_launch();
+  }
+  // ... and enqueue_step's launches for its first step, every tile cleared,
+  // with the copy of S between the assembly and the factorization
+  arslam::ExecReset er{};
+  const bool reset_in_schur = h->prepare_step(false, &er);
+  if (h->lin_xpending && !(h->has_f && h->opt.factor_executor == 1 && !h->env.dag_trace)) h->complete_pending_lin();
+  DevBuf<double> d_dense;
+  const long N = info->n_padded;
+  if (h->has_f) {
+    arslam::launch_schur(h->P, h->x, h->d_scale.p, h->d_diag.p, radius, h->Sp, h->stream, !sharded, h->plan.n_tiles,
+                         reset_in_schur ? &er : nullptr);
+    if (h->est_loaded) arslam::launch_schur_cam(h->P, h->CL, h->d_scale.p, h->d_diag.p, radius, h->Sp, h->stream);
+    if (sharded) arslam::launch_prep_reduced(h->P, h->d_diag.p, radius, h->Sp, h->stream, 0);
+    if (S) {
+      d_dense.alloc(N * N);
+      arslam::debug_reduced_dense(h->P, h->Sp, d_dense.p, h->stream);
+    }
+    h->factor_reduced(LONG_MAX, false, radius);
+  }
+  h->back_substitute(radius);
+  const double seq = h->reduce_step_scalars();
+  HIP_CHECK(hipGetLastError());
+  h->flag_sync(h->h_step.p + arslam::kHostSeq, seq);
+  const double *red = h->h_step.p;
+  if (red[arslam::NPART + 3] != 0.0)
+    throw Error(ARSLAM_E_DEVICE, executor_fault_message((int)red[arslam::NPART + 4], h->rank, 0, h->plan, h->stream));
+  info->model_cost_change = red[arslam::P_MODEL];
+  info->candidate_cost = red[arslam::P_COST];
+  info->candidate_fixed_cost = red[arslam::P_FIXED];
+  info->e_step2 = red[arslam::P_STEP2];
+  info->f_step2 = red[arslam::NPART];
+  info->e_step_bad = red[arslam::P_YBAD] != 0.0;
+  info->candidate_bad = red[arslam::P_CBAD] != 0.0;
+  info->f_step_bad = red[arslam::NPART + 1] != 0.0;
+  info->indefinite = red[arslam::NPART + 2] != 0.0;
+  // the device vectors by the caller's slots
+  std::vector<double> tmp(h->n);
+  const struct { const double *src; double *dst; } vecs[5] = {
+      {h->d_g.p, g}, {h->d_colnorm.p, colnorm}, {h->d_scale.p, scale}, {h->d_diag.p, diag}, {h->xc, xc}};
+  for (const auto &v : vecs) {
+    if (!v.dst) continue;
+    HIP_CHECK(hipMemcpyAsync(tmp.data(), v.src, h->n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    std::fill(v.dst, v.dst + info->n, 0.0);
+    for (long i = 0; i < h->n; ++i)
+      if (map[i] >= 0) v.dst[map[i]] = tmp[i];
+  }
+  if (h->has_f) {
+    if (S) HIP_CHECK(hipMemcpyAsync(S, d_dense.p, N * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (y) HIP_CHECK(hipMemcpyAsync(y, h->d_yF.p, h->nR * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    for (long r = 0; r < h->nR && row_slot; ++r) row_slot[r] = rows[r] < 0 ? -1 : (int)map[rows[r]];
+  }
+}
 }  // namespace
 
 extern "C" {
@@ -255,80 +364,57 @@ int arslam_lm_debug_step_stages(arslam_lm *h, double radius, arslam_lm_step_info
     info->n = caller_slots(h, bm, map);
     info->n_cap = bm.n_cap;
     info->n_tag = bm.n_tag;
-    info->n_reduced = h->has_f ? h->nR : 0;
-    info->n_padded = h->has_f ? h->P.N : 0;
-    info->cam_row = h->has_f ? h->P.cam_row : -1;
     info->elimination_used = h->elim_used;
-    info->n_groups = h->nc;
     info->n_direct = h->elim_used == ARSLAM_ELIM_MIXED ? h->mx.n_direct : 0;
-    info->n_big_groups = h->P.n_big_caps;
-    info->n_chunk_groups = h->P.n_chunk_caps;
-    info->n_split_dest = h->has_f ? h->P.n_splits : 0;
-    info->max_contrib = h->has_f ? h->sg.max_contrib : 0;
-    info->n_tiles = h->has_f ? h->plan.n_tiles : 0;
-    info->n_assembled_tiles = h->has_f ? h->plan.n_assembled : 0;
-    // as solve()'s iteration 0 ...
-    h->x = h->d_xa.p;
-    h->xc = h->d_xb.p;
-    h->xbest = h->x;
-    HIP_CHECK(hipMemcpyAsync(h->x, h->u_x0, h->n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    for (auto &t : h->timers) t.on = false;
-    double gmax, gnorm, xnorm;
-    h->linearize(&info->cost, &info->fixed_cost, &gmax, &gnorm, &xnorm);
-    const arslam::LmDiagArgs ld{h->n, h->d_scale.p, h->d_colnorm.p, h->opt.min_lm_diagonal, h->opt.max_lm_diagonal,
-                                h->d_diag.p};
-    arslam::launch_scale(h->P, h->d_colnorm.p, h->opt.jacobi_scaling, h->d_scale.p, h->stream, &ld);
-    // ... and enqueue_step's launches for its first step, every tile cleared,
-    // with the copy of S between the assembly and the factorization
-    arslam::ExecReset er{};
-    const bool reset_in_schur = h->prepare_step(false, &er);
-    DevBuf<double> d_dense;
-    const long N = info->n_padded;
+    step_stages(h, radius, false, map, h->lay.row_slot, info, g, colnorm, scale, diag, S, row_slot, y, xc);
+  });
+}
+
+int arslam_lm_debug_step_stages_sharded(arslam_lm *h, double radius, int lin_exchange, arslam_lm_step_info *info,
+                                        int shard[8], double *g, double *colnorm, double *scale, double *diag,
+                                        unsigned char *held, double *S, int *row_slot, int *row_class, double *y,
+                                        double *xc) {
+  if (!h || !info || !shard || !(radius > 0.0) || (lin_exchange != 0 && lin_exchange != 1)) return ARSLAM_E_INVALID_ARG;
+  return arslam::api_guarded([&] {
+    fail_if(!h->loaded || !h->multi(), ARSLAM_E_STATE, "step_stages_sharded: a problem loaded on a sharded handle");
+    h->ensure_stream();
+    h->cov_invalidate();
+    std::memset(info, 0, sizeof(*info));
+    std::vector<long> map;
+    info->n = caller_slots_sharded(h, map);
+    info->n_cap = h->nc_full;
+    info->n_tag = h->nt;
+    info->elimination_used = h->elim_used;
+    // the layout's rows (the loaded layout itself is kept on one rank only) and
+    // their classes: 0 this rank's subtrees, 1 the replicated top, 2 another rank's
+    std::vector<int> rows(h->has_f ? h->nR : 0), cls(rows.size(), 1);
     if (h->has_f) {
-      arslam::launch_schur(h->P, h->x, h->d_scale.p, h->d_diag.p, radius, h->Sp, h->stream, true, h->plan.n_tiles,
-                           reset_in_schur ? &er : nullptr);
-      if (h->est_loaded) arslam::launch_schur_cam(h->P, h->CL, h->d_scale.p, h->d_diag.p, radius, h->Sp, h->stream);
-      if (S) {
-        d_dense.alloc(N * N);
-        arslam::debug_reduced_dense(h->P, h->Sp, d_dense.p, h->stream);
-      }
-      h->factor_reduced(LONG_MAX, false);
-    }
-    h->back_substitute(radius);
-    const double seq = h->reduce_step_scalars();
-    HIP_CHECK(hipGetLastError());
-    h->flag_sync(h->h_step.p + arslam::kHostSeq, seq);
-    const double *red = h->h_step.p;
-    if (red[arslam::NPART + 3] != 0.0)
-      throw Error(ARSLAM_E_DEVICE, executor_fault_message((int)red[arslam::NPART + 4], h->rank, 0, h->plan, h->stream));
-    info->model_cost_change = red[arslam::P_MODEL];
-    info->candidate_cost = red[arslam::P_COST];
-    info->candidate_fixed_cost = red[arslam::P_FIXED];
-    info->e_step2 = red[arslam::P_STEP2];
-    info->f_step2 = red[arslam::NPART];
-    info->e_step_bad = red[arslam::P_YBAD] != 0.0;
-    info->candidate_bad = red[arslam::P_CBAD] != 0.0;
-    info->f_step_bad = red[arslam::NPART + 1] != 0.0;
-    info->indefinite = red[arslam::NPART + 2] != 0.0;
-    // the device vectors by the caller's slots
-    std::vector<double> tmp(h->n);
-    const struct { const double *src; double *dst; } vecs[5] = {
-        {h->d_g.p, g}, {h->d_colnorm.p, colnorm}, {h->d_scale.p, scale}, {h->d_diag.p, diag}, {h->xc, xc}};
-    for (const auto &v : vecs) {
-      if (!v.dst) continue;
-      HIP_CHECK(hipMemcpyAsync(tmp.data(), v.src, h->n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIP_CHECK(hipMemcpyAsync(rows.data(), h->u_row_slot, rows.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
       HIP_CHECK(hipStreamSynchronize(h->stream));
-      std::fill(v.dst, v.dst + info->n, 0.0);
-      for (long i = 0; i < h->n; ++i)
-        if (map[i] >= 0) v.dst[map[i]] = tmp[i];
+      for (size_t r = 0; r < rows.size(); ++r) cls[r] = h->plan.h_col_class[r / arslam::kTile];
     }
-    if (h->has_f) {
-      if (S) HIP_CHECK(hipMemcpyAsync(S, d_dense.p, N * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      if (y) HIP_CHECK(hipMemcpyAsync(y, h->d_yF.p, h->nR * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      HIP_CHECK(hipStreamSynchronize(h->stream));
-      for (long r = 0; r < h->nR && row_slot; ++r)
-        row_slot[r] = h->lay.row_slot[r] < 0 ? -1 : (int)map[h->lay.row_slot[r]];
+    std::memset(shard, 0, 8 * sizeof(int));
+    shard[0] = h->rank;
+    shard[1] = h->nranks;
+    shard[2] = h->has_f ? (int)h->plan.n_top_tiles : 0;
+    shard[4] = h->nc;
+    shard[5] = h->split_active;
+    shard[6] = lin_exchange;
+    // held: this rank's captures, and an f-side slot unless its row is another
+    // rank's (a slot without a row -- a constant or unseen block, or any slot of
+    // a problem with no reduced system -- keeps the same bits on every rank)
+    std::vector<int> slot_cls(h->n, 1);
+    for (size_t r = 0; r < rows.size(); ++r) {
+      if (rows[r] < 0) continue;
+      slot_cls[rows[r]] = cls[r];
+      shard[3] += cls[r] == 1;
     }
+    if (held) {
+      std::fill(held, held + info->n, (unsigned char)0);
+      for (long sl = 0; sl < h->n; ++sl) held[map[sl]] = slot_cls[sl] != 2;
+    }
+    for (size_t r = 0; r < rows.size() && row_class; ++r) row_class[r] = cls[r];
+    step_stages(h, radius, lin_exchange == 1, map, rows, info, g, colnorm, scale, diag, S, row_slot, y, xc);
   });
 }
 

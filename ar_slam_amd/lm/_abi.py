@@ -291,6 +291,8 @@ SIGNATURES = {
     "arslam_lm_debug_camera_rows": [_vp, _d, _l, _dp, _ip],
     "arslam_lm_debug_cov_camera_rows": [_vp, _l, _dp, _ip],
     "arslam_lm_debug_step_stages": [_vp, _d, P(StepInfo), _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp],
+    "arslam_lm_debug_step_stages_sharded": [_vp, _d, _i, P(StepInfo), _ip, _dp, _dp, _dp, _dp, _up, _dp, _ip, _ip, _dp,
+                                            _dp],
     "arslam_lm_debug_evaluate_times": [_vp, _dp],
     "arslam_debug_schur_stamps": [P(C.c_ulonglong)],
     "arslam_lm_debug_force_indefinite": [_vp, C.c_ulonglong],

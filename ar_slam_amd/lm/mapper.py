@@ -151,6 +151,7 @@ class _Handle(_Owner):
         """Test hook: the multi-rank path (split, two-phase factorization, every collective) with
         one rank, so set_comm(0, 1, uid) makes a one-rank RCCL communicator on a one-GPU box."""
         _check(lib().arslam_lm_debug_force_multirank(self._h, 1 if on else 0))
+        self._forced_multirank, self._sharded_ranks = bool(on), 1   # (the call resets the communicator)
 
     def debug_evaluate_times(self):
         """The last evaluate()'s device times under phase_timing=1, ms: {upload, k_eval_obs,
@@ -159,31 +160,53 @@ class _Handle(_Owner):
         _check(lib().arslam_lm_debug_evaluate_times(self._h, _ptr(ms)))
         return dict(zip(("upload", "k_eval_obs", "k_eval_blocks", "k_eval_tree", "copy_back"), ms.tolist()))
 
-    def debug_step_stages(self, radius):
+    def debug_step_stages(self, radius, lin_exchange="packed"):
         """Every stage of one LM step of the loaded problem at its loaded point under `radius`
         (arslam_lm_debug_step_stages): a dict of the arslam_lm_step_info fields and
         ``g``, ``colnorm``, ``scale``, ``diag``, ``xc`` (n,) by the caller's slots; ``S``
         (n_reduced, n_reduced) the assembled system before the factorization, ``rhs``
         (n_reduced,) its right-hand side row, ``S_padded`` (n_padded, n_padded) every row of the
         padded system; ``row_slot`` (n_reduced,) the caller's slot of a row, -1 for padding; ``y``
-        (n_reduced,) the reduced solution."""
+        (n_reduced,) the reduced solution.
+
+        On a sharded handle (made with ``comm=`` of several ranks, or ``force_multirank``) it is
+        arslam_lm_debug_step_stages_sharded: a collective call, every rank with the same `radius`
+        and `lin_exchange` ("packed": iteration 0's sums by the packed all-reduce; "ride": a second
+        linearization's top sums in front of the top tiles).  ``S`` and ``rhs`` are then this
+        rank's share, ``y`` is masked, and the dict also has ``held`` (n,) bool, ``row_class``
+        (n_reduced,) 0 own / 1 top / 2 another rank's, and ``rank``, ``n_ranks``, ``n_top_tiles``,
+        ``n_top_rows``, ``n_owned_captures``, ``n_active_ranks`` (see the header)."""
         info = StepInfo()
         L = lib()
-        _check(L.arslam_lm_debug_step_stages(self._h, float(radius), C.byref(info), None, None, None, None, None,
-                                             None, None, None))
+        sharded = getattr(self, "_sharded_ranks", 1) > 1 or getattr(self, "_forced_multirank", False)
+        shard = np.zeros(8, np.int32)
+        ride = {"packed": 0, "ride": 1}[lin_exchange]
+
+        def call(g, colnorm, scale, diag, held, S, slot, cls, y, xc):
+            if sharded:
+                return L.arslam_lm_debug_step_stages_sharded(self._h, float(radius), ride, C.byref(info), _ptr(shard),
+                                                             g, colnorm, scale, diag, held, S, slot, cls, y, xc)
+            return L.arslam_lm_debug_step_stages(self._h, float(radius), C.byref(info), g, colnorm, scale, diag, S, slot,
+                                                 y, xc)
+        _check(call(*[None] * 10))
         n, nR, N = info.n, info.n_reduced, info.n_padded
         v = {k: np.zeros(n) for k in ("g", "colnorm", "scale", "diag", "xc")}
         S = np.zeros((max(N, 1), max(N, 1)))
         slot = np.zeros(max(nR, 1), np.int32)
+        cls = np.zeros(max(nR, 1), np.int32)
+        held = np.zeros(max(n, 1), np.uint8)
         y = np.zeros(max(nR, 1))
-        _check(L.arslam_lm_debug_step_stages(self._h, float(radius), C.byref(info), _ptr(v["g"]), _ptr(v["colnorm"]),
-                                             _ptr(v["scale"]), _ptr(v["diag"]), _ptr(S), _ptr(slot), _ptr(y),
-                                             _ptr(v["xc"])))
+        _check(call(_ptr(v["g"]), _ptr(v["colnorm"]), _ptr(v["scale"]), _ptr(v["diag"]), _ptr(held), _ptr(S), _ptr(slot),
+                    _ptr(cls), _ptr(y), _ptr(v["xc"])))
         out = info.to_dict()
         out.update(v)
         S = S[:N, :N]
         out.update(S_padded=S, S=S[:nR, :nR].copy(), rhs=S[nR, :nR].copy() if N else np.zeros(0),
                    row_slot=slot[:nR], y=y[:nR])
+        if sharded:
+            out.update(held=held[:n].astype(bool), row_class=cls[:nR],
+                       **dict(zip(("rank", "n_ranks", "n_top_tiles", "n_top_rows", "n_owned_captures",
+                                   "n_active_ranks"), (int(s) for s in shard[:6]))), lin_exchange=lin_exchange)
         return out
 
     def set_comm(self, rank, nranks, uid):
@@ -205,6 +228,7 @@ class _Handle(_Owner):
             _check(lib().arslam_lm_set_comm_callback(self._h, rank, nranks, self._comm_cb, None))
         else:
             _check(lib().arslam_lm_set_comm(self._h, rank, nranks, uid))
+        self._sharded_ranks = int(nranks)
 
 
 def comm_unique_id() -> bytes:

@@ -203,6 +203,51 @@ typedef struct {
 int arslam_lm_debug_step_stages(arslam_lm *h, double radius, arslam_lm_step_info *info, double *g, double *colnorm,
                                 double *scale, double *diag, double *S, int *row_slot, double *y, double *xc);
 
+/* The same on a sharded handle (several ranks, or arslam_lm_debug_force_multirank):
+ * a COLLECTIVE call -- every rank calls it with the same radius and lin_exchange,
+ * and it performs the step's collectives.  From the loaded point it runs the
+ * launches of solve()'s iteration 0 and first step on that path: the
+ * linearization of the rank's own captures with its packed exchange, the Jacobi
+ * scale with the LM diagonal, the Schur elimination assembling this rank's share,
+ * D^2 on its own-subtree rows, phase 0 of the factorization, the all-reduce of
+ * the top tiles, D^2 on the top rows, phase 1, the backward solve with its mask,
+ * the back-substitution, and the all-gathered step scalars.
+ * lin_exchange: 0 = iteration 0's sums are complete before the step (the packed
+ *   all-reduce, used when no step follows a linearization); 1 = besides, a
+ *   linearization of the same point is enqueued again as after an accepted step
+ *   and its top-tag sums and camera partials ride in front of the top tiles, its
+ *   cost and norms with the step's scalars (what a step that follows a
+ *   linearization does).  g, colnorm and diag are then that linearization's.
+ * info: as above, by the whole problem's blocks; n_groups, n_big_groups,
+ *   n_chunk_groups, n_split_dest, max_contrib, n_tiles, n_assembled_tiles are this
+ *   rank's; the scalars and flags are the exchanged ones (every rank's the same).
+ * shard: {rank, n_ranks, n_top_tiles, n_top_rows (real rows of the replicated
+ *   top), n_owned_captures, n_active_ranks, lin_exchange, 0}.
+ * g, colnorm, scale, diag, xc [info.n]: by the whole problem's slots, 0 for the
+ *   captures of other ranks.  held [info.n]: 1 where a slot's values mean
+ *   something on this rank -- the captures it owns; the camera and tag slots whose
+ *   reduced row lies in its own subtrees or in the replicated top (the top and,
+ *   with it, the camera are held by EVERY rank); slots without a reduced row
+ *   (constant or unseen blocks: the loaded bits on every rank).  A tag of another
+ *   rank's subtree is not held: its sums are partial and its xc may be stale.
+ * S [info.n_padded^2]: this rank's SHARE of the system, copied after D^2 went on
+ *   its own-subtree rows and before phase 0.  Rows of class 0 (own subtrees) are
+ *   final: their D^2, alignment padding rows as identity rows.  Top tiles (class
+ *   1) hold the sum over this rank's captures alone: no D^2, and the rows the top
+ *   carries besides -- padding, the right-hand side's pivot, the rows past it --
+ *   have 0 on the diagonal (their pivots go on after the exchange).  The
+ *   right-hand side row holds this rank's captures' part.  Rows of class 2
+ *   (another rank's subtrees) have no tile here: 0.
+ * row_slot, row_class [info.n_reduced]: the whole problem's slot of a row (-1:
+ *   padding) and its class 0 / 1 / 2.  y [info.n_reduced]: the reduced solution
+ *   after the mask -- the top rows and this rank's own rows, 0 elsewhere.
+ * Sizes first: call with every array null (a collective call like any other).
+ * The next solve on every rank gives the bits of a fresh handle's. */
+int arslam_lm_debug_step_stages_sharded(arslam_lm *h, double radius, int lin_exchange, arslam_lm_step_info *info,
+                                        int shard[8], double *g, double *colnorm, double *scale, double *diag,
+                                        unsigned char *held, double *S, int *row_slot, int *row_class, double *y,
+                                        double *xc);
+
 /* The device times of the handle's last arslam_lm_evaluate / _evaluate_blocks
  * under options.phase_timing = 1 (HIP events on its stream), ms: the parameter
  * upload, k_eval_obs, k_eval_blocks, k_eval_tree (both launches), the copy

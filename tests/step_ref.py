@@ -203,6 +203,7 @@ def _groups(R, elim, scale, dtype):
         fs = fs[f_side[fs]]
         pos = {int(sl): k for k, sl in enumerate(fs)}
         g.e, g.f = e_slots, fs
+        g.cap = int(R.P.obs_cap[R.obs[idx[0]]]) if e_slots is None or e_slots[0] < 3 + 6 * R.P.nc else -1
         g.E = np.zeros((8 * len(idx), 6), dtype)
         g.F = np.zeros((8 * len(idx), len(fs)), dtype)
         g.r = np.zeros(8 * len(idx), dtype)
@@ -236,9 +237,11 @@ class Reduced:
     groups (for back_substitute), D2 [n]."""
 
 
-def reduce(R, elim, scale, diag, radius, longdouble=True, drop=None):
+def reduce(R, elim, scale, diag, radius, longdouble=True, drop=None, only_caps=None, d2_slots=None):
     """The reduced system.  drop = (group index, a, b) is for the self-test of the measures only:
-    that group's contribution to the diagonal block of its local f-slots [a, b) is left out."""
+    that group's contribution to the diagonal block of its local f-slots [a, b) is left out.
+    only_caps (bool [nc]) and d2_slots (bool [n]) make it a rank's share (reduce_shares): the
+    groups of those captures alone, D_f^2 on those slots alone; H and rr are then the share's."""
     dtype = LD if longdouble else np.float64
     P = R.P
     groups, f_side = _groups(R, elim, scale, dtype)
@@ -254,6 +257,8 @@ def reduce(R, elim, scale, diag, radius, longdouble=True, drop=None):
     out.struct = np.zeros((nf, nf), bool)
     out.rr = dtype(0.0)
     for gi, g in enumerate(groups):
+        if only_caps is not None and not only_caps[g.cap]:
+            continue
         p = pos[g.f]
         FF, Fr = g.F.T @ g.F, g.F.T @ g.r
         out.H[p] += np.diag(FF)
@@ -279,11 +284,36 @@ def reduce(R, elim, scale, diag, radius, longdouble=True, drop=None):
         fb = np.where(slots < 3, 0, 1 + (slots - 3) // 6)
         touched = np.isin(fb, blk)
         out.struct |= np.outer(touched, touched)
-    out.S[np.arange(nf), np.arange(nf)] += D2[slots]
-    out.H += D2[slots]
-    out.struct[np.arange(nf), np.arange(nf)] = True
+    on = np.ones(nf, bool) if d2_slots is None else np.asarray(d2_slots, bool)[slots]
+    out.S[np.arange(nf)[on], np.arange(nf)[on]] += D2[slots][on]
+    out.H[on] += D2[slots][on]
+    out.struct[np.arange(nf)[on], np.arange(nf)[on]] = True
     out.slots, out.groups, out.D2, out.f_side = slots, groups, D2, f_side
     return out
+
+
+def reduce_shares(R, elim, scale, diag, radius, owners, slot_rank, n_ranks, longdouble=True):
+    """The sharded reduction: rank k's share is the sum over the captures it owns (owners [nc]) of
+    F'F - W'U^-1 W and of the rhs terms, plus D_f^2 on the f-side slots of its own subtrees
+    (slot_rank [n] == k; -1: the replicated top, whose D^2 no share carries).  The e-set is the
+    captures (the ranks own captures).  One Reduced per rank, by the same slots as reduce()."""
+    P = R.P
+    assert not np.any(np.asarray(elim)[P.nc:]), "the sharded path eliminates captures"
+    owners, slot_rank = np.asarray(owners), np.asarray(slot_rank)
+    return [reduce(R, elim, scale, diag, radius, longdouble, only_caps=owners == k, d2_slots=slot_rank == k)
+            for k in range(n_ranks)]
+
+
+def sum_shares(shares, top_d2):
+    """The shares summed in rank order, then top_d2 [nf] (D_f^2 of the top slots, 0 elsewhere) on
+    the diagonal, in the shares' dtype: the device's two-level sum (captures within a rank, then
+    the ranks), and in long double the whole problem's system to the rounding of the sum."""
+    S, rhs = shares[0].S.copy(), shares[0].rhs.copy()
+    for sh in shares[1:]:
+        S += sh.S
+        rhs += sh.rhs
+    S[np.arange(len(rhs)), np.arange(len(rhs))] += np.asarray(top_d2, S.dtype)
+    return S, rhs
 
 
 def errors(test_S, test_rhs, ref):
@@ -381,6 +411,42 @@ def pair_graph(n_cap, both, seed):
                        np.ascontiguousarray(corners), camera_true, cap_true, tag_true, "pair")
 
 
+# The sharded step's inputs: name -> world size.  The smallest with a real split (a replicated top
+# and two ranks owning subtrees): `medium`; the same with outliers under a Cauchy loss, and with a
+# constant tag and camera; sh400 x 3, whose third rank owns two top-only captures and no subtree
+# (the shape of the split at 4 and 8 ranks); shmix200, captures of 8 .. 30 tags on both ranks
+# (k_schur<true> and the chunked instances).  tests/test_step_ref.py holds the split facts.
+SHARDED = {"medium": 2, "medium_cauchy": 2, "medium_const": 2, "sh400": 3, "shmix200": 2}
+
+
+def sharded_graph(name):
+    if name == "sh400":
+        return synth.make_graph(400, 14, 10, 31)
+    if name == "shmix200":
+        return synth.make_graph(200, 16, 12, 31, k=(8, 11, 16, 8, 8, 30, 8, 8), depth=(1.5, 3.5))
+    g = synth.config_graph("medium")
+    return loss_ref.outliers(g)[0] if name == "medium_cauchy" else g
+
+
+@functools.lru_cache(maxsize=None)
+def rank_split(name, world=None):
+    """(infos [world] of arslam_split_info as dicts, cap_owner [nc]) of a sharded input, by the
+    host-only arslam_debug_rank_split on the problem as the ranks load it (constants included)."""
+    import ctypes as C
+    from ar_slam_amd import build
+    from ar_slam_amd.lm import _abi, mapper
+    build.build()
+    s = spec(name)
+    A = mapper._Soa(*tag_size_ref.arrays(s["g"]), s["camera_const"], s["cap_const"], s["tag_const"])
+    world = SHARDED[name] if world is None else world
+    infos, owner = [], np.zeros(A.cap.shape[0], np.int32)
+    for r in range(world):
+        info = _abi.SplitInfo()
+        _abi._check(_abi.lib().arslam_debug_rank_split(C.byref(A.s), world, r, C.byref(info), _abi._ptr(owner)))
+        infos.append(info.to_dict())
+    return infos, owner
+
+
 LATE_SPECS = {}   # specs a GPU test builds from what the device told it (the appended problem)
 
 
@@ -403,6 +469,14 @@ def spec(name):
         s["g"] = pair_graph(170, True, 2)
     elif name == "single1030":   # the camera diagonal and camera x rhs: 1030 > 1024
         s["g"] = pair_graph(1030, False, 3)
+    elif name in SHARDED:   # the sharded step's inputs (tests/test_gpu_step_stages_sharded.py)
+        s["g"] = sharded_graph(name)
+        if name == "medium_cauchy":
+            s["loss"] = (loss_ref.CAUCHY, 3.0)
+        if name == "medium_const":   # a constant tag (one a rank's subtree holds) and a constant camera
+            s["camera_const"] = True
+            s["tag_const"] = np.zeros(s["g"].n_tag, np.uint8)
+            s["tag_const"][5] = 1
     elif name == "small":
         s["g"] = synth.config_graph("small")
     elif name == "small_cauchy":
@@ -443,4 +517,7 @@ INPUT_RADII = {"k1to11": ALL_RADII, "small": ALL_RADII, "k1to11_const": ALL_RADI
                "pair70": ALL_RADII[:2], "pair170": ALL_RADII[:2], "single1030": ALL_RADII[:2],
                "small_cauchy": ALL_RADII[:2], "small_sized": ALL_RADII[:2], "g20_radial": ALL_RADII[:2],
                "g20_radial_est": ALL_RADII[:2], "g20_cap_const": ALL_RADII[:2], "g20_tag_const": ALL_RADII[:2],
-               "g20_camera_const": ALL_RADII[:2], "g20_f_const": ALL_RADII[:2]}
+               "g20_camera_const": ALL_RADII[:2], "g20_f_const": ALL_RADII[:2],
+               # ... and of tests/test_gpu_step_stages_sharded.py
+               "medium": ALL_RADII, "medium_cauchy": ALL_RADII[:2], "medium_const": ALL_RADII[:2],
+               "sh400": ALL_RADII[:2], "shmix200": ALL_RADII[:2]}

@@ -32,14 +32,21 @@ def _free_port():
         return s.getsockname()[1]
 
 
+def _graph(name):
+    """The graph of a case: one of synth's configs, or one of step_ref's sharded inputs."""
+    from ar_slam_amd import synth
+    import step_ref
+    return step_ref.sharded_graph(name) if name in step_ref.SHARDED else synth.config_graph(name)
+
+
 def _worker(rank, world, port, name, q, abort_rank=-1):
     import torch.distributed as dist
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        from ar_slam_amd import lm, synth
-        g = synth.config_graph(name)
+        from ar_slam_amd import lm
+        g = _graph(name)
         part = dict(camera=g.camera, cap=g.cap, tag=g.tag, obs_cap=g.obs_cap, obs_tag=g.obs_tag,
                     corners=g.corners)   # every rank loads the whole problem
 
@@ -105,13 +112,23 @@ def _same_on_every_rank(res):
         np.testing.assert_array_equal(r[3], res[0][3])
 
 
-@pytest.mark.parametrize("name,world", [("medium", 2), ("cfg2", 2), ("cfg2", 3), ("cfg2", 4), ("kvar", 2),
-                                        ("k24", 2)])
+# (graph, world): the ranks that own subtrees, by the host-only arslam_debug_rank_split.  One active
+# rank is a degenerate split -- no replicated top, no exchange of tiles, the other rank owns nothing:
+# kvar and k24 (the captures of more than 10 tags) stay as "a rank that owns nothing"; shmix200 x 2
+# runs such captures through a real split, sh400 x 3 a third rank of two top-only captures.
+ACTIVE_RANKS = {("medium", 2): 2, ("cfg2", 2): 2, ("cfg2", 3): 2, ("cfg2", 4): 2, ("kvar", 2): 1, ("k24", 2): 1,
+                ("shmix200", 2): 2, ("sh400", 3): 2}
+
+
+@pytest.mark.parametrize("name,world", list(ACTIVE_RANKS))
 def test_sharded_gpu_solve_matches_oracle(oracle, name, world):
     if torch.cuda.device_count() < 1:
         pytest.skip("no GPU")
-    from ar_slam_amd import synth
-    g = synth.config_graph(name)
+    from ar_slam_amd import lm
+    g = _graph(name)
+    info, owner = lm.debug_rank_split(g.camera, g.cap, g.tag, g.obs_cap, g.obs_tag, g.corners, world, 0)
+    assert info["n_active"] == ACTIVE_RANKS[(name, world)], "the split model changed: this case's kind with it"
+    assert (info["n_top_tiles"] > 0) == (info["n_active"] > 1) and len(set(owner.tolist())) >= info["n_active"]
     cam0, cap0, tag0, s0 = oracle.solve_graph(g)
     res = _run_ranks(name, world)
     costs0 = [it["cost"] for it in s0["iterations"]]

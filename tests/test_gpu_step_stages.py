@@ -77,6 +77,15 @@ def _reference(name, oracle, elim_bytes, radius):
     return dict(s=s, d=d, s64=s64, d64=d64, ref=ref, e64=sr.errors(r64.S, r64.rhs, ref))
 
 
+@functools.lru_cache(maxsize=4)
+def _reduce_at(name, oracle, elim_bytes, scale_bytes, diag_bytes, radius):
+    """The reduction from a device's own scale and diagonal, long double and float64 (two outputs
+    with the same bits of both -- a sharded step's two exchange modes -- share it)."""
+    R = _rows(name, oracle)[1]
+    elim, scale, diag = np.frombuffer(elim_bytes, bool), np.frombuffer(scale_bytes), np.frombuffer(diag_bytes)
+    return sr.reduce(R, elim, scale, diag, radius, True), sr.reduce(R, elim, scale, diag, radius, False)
+
+
 def _load(lm, name, **opts):
     s = _spec(name)
     kw = {}
@@ -145,27 +154,36 @@ def check_case(lm, oracle, name, radius, label, expect=None, handle=None, **opts
     """One loaded problem, one radius: every stage output against the reference.  Returns the
     device's outputs and the figures (also printed).  handle: a problem already loaded (else
     the named one is loaded with opts)."""
-    spec = _spec(name)
     rp = handle if handle is not None else _load(lm, name, **opts)
     out = rp.debug_step_stages(radius)
-    P, R, (g, cn, rr), (g64, cn64, g_floor, cn_floor) = _rows(name, oracle)
+    P = _rows(name, oracle)[0]
     assert out["n"] == P.n
     if expect:
         expect(out)
-    rows = _block_rows(out, P)
-    cam_row = out["cam_row"]
     if hasattr(rp, "debug_reduced_rows"):   # arslam_lm_debug_reduced_rows says the same, a mixed set included
         cap_row, tag_row, cam_row = rp.debug_reduced_rows()
-        assert np.array_equal(np.concatenate([cap_row, tag_row]), rows) and cam_row == out["cam_row"]
-    elim = sr.e_set(P, rows[:P.nc], rows[P.nc:])
-    c = _reference(name, oracle, elim.tobytes(), float(radius))
-    ref = c["ref"]
-    fig = {}
+        assert np.array_equal(np.concatenate([cap_row, tag_row]), _block_rows(out, P)) and cam_row == out["cam_row"]
+    fig = stage_figures(name, oracle, radius, out)
+    report("step_stages", name, label, radius, out["n_reduced"], fig)
+    return rp, out
 
-    # -- the linearization's sums, the scale, the LM diagonal
+
+def reference_of(name, oracle, radius, out):
+    """The reference of the elimination the device's reduced rows (out["row_slot"]) say."""
+    P = _rows(name, oracle)[0]
+    rows = _block_rows(out, P)
+    elim = sr.e_set(P, rows[:P.nc], rows[P.nc:])
+    return elim, _reference(name, oracle, elim.tobytes(), float(radius))
+
+
+def lin_figures(name, oracle, c, out, fr=None, sm=None):
+    """The linearization's sums, the scale, the LM diagonal of one output, over the free slots fr
+    (default: all of them; the scale over sm, default every slot).  Returns (figures, g's floor)."""
+    P, R, (g, cn, rr), (g64, cn64, g_floor, cn_floor) = _rows(name, oracle)
+    fig = {}
     rn = np.sqrt(rr)
     gden = np.where(cn > 0, np.sqrt(cn) * rn, 1)
-    fr = P.free
+    fr = P.free if fr is None else fr
     # (the restatement's floor takes in the rounding of the rows themselves, which the device
     # performs and the restatement, sharing the reference's rows, does not: step_ref.Rows.rerr
     # and wrel, by slot for g and colnorm; scale = 1 / (1 + sqrt(colnorm)) carries at most half
@@ -173,14 +191,30 @@ def check_case(lm, oracle, name, radius, label, expect=None, handle=None, **opts
     gf, cf = float(np.max(g_floor[fr])), float(np.max(cn_floor[fr]))
     fig["g"] = (float(np.max((np.abs(out["g"] - g) / gden)[fr])), float(np.max((np.abs(g64 - g) / gden)[fr])) + gf)
     fig["colnorm"] = (_rel(out["colnorm"], cn, fr), _rel(cn64, cn, fr) + cf)
-    fig["scale"] = (_rel(out["scale"], c["s"]), _rel(c["s64"], c["s"]) + 0.5 * cf)
+    fig["scale"] = (_rel(out["scale"], c["s"], sm), _rel(c["s64"], c["s"], sm) + 0.5 * cf)
     fig["diag"] = (_rel(out["diag"], c["d"], fr), _rel(c["d64"], c["d"], fr) + cf)
+    return fig, gf
+
+
+def stage_figures(name, oracle, radius, out, padded=True, system_floor=None):
+    """{stage: (e_dev, e_ref64)} of one step's outputs `out` (debug_step_stages' keys) against the
+    reference, with every exact property asserted on the way.  padded=False: out has no
+    S_padded to look at (a system summed from the ranks' shares); system_floor = (e_S, e_rhs):
+    the restatement's errors to hold S and rhs to instead of the one-level restatement's."""
+    spec = _spec(name)
+    P, R, (g, cn, rr), (g64, cn64, g_floor, cn_floor) = _rows(name, oracle)
+    elim, c = reference_of(name, oracle, radius, out)
+    ref = c["ref"]
+    e64 = c["e64"] if system_floor is None else system_floor
+
+    # -- the linearization's sums, the scale, the LM diagonal
+    fig, gf = lin_figures(name, oracle, c, out)
 
     # -- the assembled system
     nR, N = out["n_reduced"], out["n_padded"]
-    Sp, slot = out["S_padded"], out["row_slot"]
+    slot = out["row_slot"]
     if spec["camera_const"]:
-        assert out["cam_row"] == -1 and cam_row == -1 and not np.any((slot >= 0) & (slot < 3))
+        assert out["cam_row"] == -1 and not np.any((slot >= 0) & (slot < 3))
     if len(ref.slots):
         real = np.nonzero(slot >= 0)[0]
         assert sorted(slot[real].tolist()) == ref.slots.tolist(), "the reduced rows are the free f-side slots"
@@ -189,16 +223,18 @@ def check_case(lm, oracle, name, radius, label, expect=None, handle=None, **opts
         ix = row_of[ref.slots]
         S_dev, rhs_dev = out["S"][np.ix_(ix, ix)], out["rhs"][ix]
         assert np.array_equal(out["S"], out["S"].T)
-        fig["S"] = (sr.errors(S_dev, rhs_dev, ref)[0], c["e64"][0])
-        fig["rhs"] = (sr.errors(S_dev, rhs_dev, ref)[1], c["e64"][1] + 2 * gf)
+        fig["S"] = (sr.errors(S_dev, rhs_dev, ref)[0], e64[0])
+        fig["rhs"] = (sr.errors(S_dev, rhs_dev, ref)[1], e64[1] + 2 * gf)
         assert fig["S"][1] <= CAPS[float(radius)], f"the restatement's own S error {fig['S'][1]:.2e}: replace the input"
         # exactly zero wherever no e-block couples the two blocks, fill tiles included
         assert np.all(S_dev[~ref.struct] == 0.0)
-        # the padding rows are identity rows, the right-hand side's row has its pivot and nothing after it
-        pad = np.concatenate([np.nonzero(slot < 0)[0], np.arange(nR + 1, N)])
-        eye = np.eye(N)
-        assert np.array_equal(Sp[pad], eye[pad]) and np.array_equal(Sp[:, pad], eye[:, pad])
-        assert Sp[nR, nR] == 1e300
+        if padded:
+            # the padding rows are identity rows, the right-hand side's row has its pivot and nothing after it
+            Sp = out["S_padded"]
+            pad = np.concatenate([np.nonzero(slot < 0)[0], np.arange(nR + 1, N)])
+            eye = np.eye(N)
+            assert np.array_equal(Sp[pad], eye[pad]) and np.array_equal(Sp[:, pad], eye[:, pad])
+            assert Sp[nR, nR] == 1e300
         # the diagonal carries D^2: where nothing else lands it is D^2 alone, bit for bit
         d2 = np.sqrt(out["diag"] / radius) ** 2
         lone = np.nonzero(np.asarray(ref.H - ref.D2[ref.slots] == 0))[0]
@@ -224,8 +260,8 @@ def check_case(lm, oracle, name, radius, label, expect=None, handle=None, **opts
             Lc = np.linalg.cholesky(S_dev)
             fig["y"] = (eta(out["y"][ix]), eta(np.linalg.solve(Lc.T, np.linalg.solve(Lc, rhs_dev))))
         # -- the candidate, from the device's own y and scale
-        red_ld = sr.reduce(R, elim, out["scale"], out["diag"], radius, True)
-        red_64 = sr.reduce(R, elim, out["scale"], out["diag"], radius, False)
+        red_ld, red_64 = _reduce_at(name, oracle, elim.tobytes(), out["scale"].tobytes(), out["diag"].tobytes(),
+                                    float(radius))
         y_dev = out["y"][ix] if len(ref.slots) else np.zeros(0)
         st = sr.back_substitute(R, red_ld, y_dev, out["scale"], True)
         st64 = sr.back_substitute(R, red_64, y_dev, out["scale"], False)
@@ -256,17 +292,21 @@ def check_case(lm, oracle, name, radius, label, expect=None, handle=None, **opts
         s2, s1, rows = _plain_cost_terms(P, out["xc"])
         cost_bound = 1e-12 * s2 + 1e-9 * s1 + 1e-18 * rows + rows * sr.U64 * (act + fix)
         fig["cost"] = (abs(out["candidate_cost"] - act) + abs(out["candidate_fixed_cost"] - fix), cost_bound)
+    return fig
 
+
+def report(prefix, name, label, radius, nR, fig):
+    """Print the case's line (e_dev / e_ref64 per stage, the worst e_dev / bound) and hold every
+    stage to the rule; the candidate cost to its own bound."""
     worst = {}
     for k, (e_dev, e_ref) in fig.items():
         b = e_ref if k == "cost" else _bound(e_ref)
         worst[k] = e_dev / b
-    print("step_stages: %-16s %-10s r=%-6g nR=%-4d " % (name, label, radius, nR) +
+    print("%s: %-16s %-10s r=%-6g nR=%-4d " % (prefix, name, label, radius, nR) +
           " ".join("%s %.1e/%.1e" % (k, v[0], v[1]) for k, v in fig.items()) +
           "  worst %s %.2f" % max(((k, v) for k, v in worst.items()), key=lambda kv: kv[1]))
     for k, v in worst.items():
         assert v <= 1.0, f"{name} {label} radius {radius}: {k} e_dev {fig[k][0]:.3e} over its bound ({v:.2f} x)"
-    return rp, out
 
 
 def _same_bits(a, b):
